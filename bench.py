@@ -9,7 +9,17 @@ all-gather over RCCL, the root's apportionment, this server's grants), pipelined
 beside the next leaf tick (dm_hier_pipeline).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c1ps|c2|c3|c4] [--hier on|off|auto]
-                  [--layout auto|sharded|replicated]
+                  [--layout auto|sharded|replicated] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric,
+value, ms_per_step, the configuration).  --dump-outputs DIR then also writes what the
+last timed step left (dump_outputs: leases, running sums, templates) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments compare file by file.
+--full adds everything else the line can carry, each in runs of its own after the timed
+steps: K profiled steps (per-class kernel times, the dominant kernel's roofline, the
+tick's HBM fractions), the exchange self-check, configs[4]'s busy-GPU probe, the CPU
+baseline, and the C1 / C2 / C4 lines (N = 1) or weak scaling and sharded configs[2]
+(N > 1) under `extra`.  A rehearsal (--rehearse-shard) always runs in full.
 
 configs[3] (c3, the default): ONE 100M-lease snapshot (100k resources x 1k
 clients) sharded by resource id over the N GPUs (hierarchy.partition), each GPU
@@ -425,18 +435,33 @@ def cpu_baseline(snap, now_ns, budget_s=12.0):
 # ---------------------------------------------------------------------------
 # timing
 # ---------------------------------------------------------------------------
-def timed_steps(torch, eng, step, steps, warmup, sync_ranks, extra_warm=True, also=()):
+WARM_S = 0.3               # back-to-back ticks before the timed ones (timed_steps)
+WARM_S_PER_LEASE = 4e-12   # a writeback tick's time per lease on one MI355X (C3: 0.43 ms per 100M leases)
+
+
+def warm_steps(n_leases: int) -> int:
+    """The untimed steps after the W warm-up steps: about WARM_S of ticks, counted from
+    the store's size and not from a clock, so that a run's steps before its last timed
+    one -- and with them the bits --dump-outputs writes (a tick's `has` feeds the next
+    tick's sums) -- are the same from run to run."""
+    return min(20000, int(np.ceil(WARM_S / max(n_leases * WARM_S_PER_LEASE, 1e-6))))
+
+
+def timed_steps(torch, eng, step, steps, warmup, sync_ranks, extra_warm=True, also=(), profile=True,
+                after_timed=None, warm=None):
     """W untimed warm-up steps, then more until ~0.3 s of ticks have run (the first
     milliseconds of back-to-back ticks run ~10% slow: C3 measured 843 us/tick after 3
-    warm-up ticks, 765 after 30; the count is agreed over ranks), then K timed steps
-    between barrier + synchronize, then K profiled steps (HIP events around every
-    launch, on the stream each kernel runs on)."""
+    warm-up ticks, 765 after 30; `warm` steps (warm_steps), or a count from the W steps'
+    time; agreed over ranks), then K timed steps between barrier + synchronize;
+    after_timed() then sees the state the last timed step left (--dump-outputs); then,
+    with profile, K profiled steps (HIP events around every launch, on the stream each
+    kernel runs on; ktimes is empty without)."""
     t_w = time.perf_counter()
     for _ in range(max(warmup, 1)):
         step()
     eng.sync()
     per_step = (time.perf_counter() - t_w) / max(warmup, 1)
-    extra = min(20000, int(0.3 / max(per_step, 1e-6))) if extra_warm else 0
+    extra = (min(20000, int(WARM_S / max(per_step, 1e-6))) if warm is None else int(warm)) if extra_warm else 0
     extra = sync_ranks("max_int", extra)
     for i in range(extra):
         step()
@@ -459,20 +484,61 @@ def timed_steps(torch, eng, step, steps, warmup, sync_ranks, extra_warm=True, al
     sync_ranks("barrier", None)
     elapsed = time.perf_counter() - t0
     stream_ms = ev0.elapsed_time(ev1)
-    prof = [eng] + list(also)  # the exchange's root round runs on the root engine
+    if after_timed is not None:
+        after_timed()
+    ktimes = {}
+    prof = [eng] + list(also) if profile else []  # the exchange's root round runs on the root engine
     for e in prof:
         e.set_profiling(True)
         e.reset_kernel_times()
-    for _ in range(steps):
+    for _ in range(steps if profile else 0):
         step()
     torch.cuda.synchronize()
-    ktimes = {}
     for e in prof:
         e.sync()
         ktimes.update(e.kernel_times())
         e.set_profiling(False)
     return {"elapsed": elapsed, "stream_ms": stream_ms, "ktimes": ktimes, "warm_run": max(warmup, 1) + extra,
             "host_enqueue_s": t_enq}
+
+
+DUMP_ROWS = 500_000  # --dump-outputs: leases sampled from a store too large to write whole
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirpath, eng, now, ht=None, step=None, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after its last timed step,
+    as DIR/<name>.npy (float64; under 64 MB for every workload):
+      lease_rows / lease_gets / lease_expiry_rel_ns   the leases (dm_read_leases_rows) of
+                         a fixed seeded sample of DUMP_ROWS rows (every row of a smaller
+                         store), expiry as ns after the tick's time (a released row: -2^63);
+      resource_count / _sum_has / _sum_wants / _safe_capacity   every resource's running
+                         sums and safe capacity (dm_read_resources);
+      template_<field>   with the exchange, the leaf's configuration as the root's grants
+                         left it (dm_read_config).
+    Reads only: the store goes on as the timed steps left it."""
+    if step is not None and hasattr(step, "finish"):
+        step.finish()
+    if ht is not None:
+        ht.sync()
+    eng.sync()
+    os.makedirs(dirpath, exist_ok=True)
+    N = eng.n_leases
+    rows = np.arange(N, dtype=np.int64)
+    if N > DUMP_ROWS:
+        rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, N, DUMP_ROWS))
+    gets, exp = eng.leases_rows(rows)
+    released = exp == W_RELEASED
+    rel = (np.where(released, now, exp) - now).astype(np.float64)
+    rel[released] = float(W_RELEASED)
+    out = {"lease_rows": rows, "lease_gets": gets, "lease_expiry_rel_ns": rel}
+    for k, v in eng.resources(safe=True).items():
+        out["resource_" + k] = v
+    if ht is not None:
+        for k, v in eng.config().items():
+            out["template_" + k] = v
+    for k, v in out.items():
+        np.save(os.path.join(dirpath, f"{k}{suffix}.npy"), np.asarray(v, dtype=np.float64))
 
 
 def roofline_of(workload, snap, run, steps, single_kernel_tick):
@@ -840,7 +906,7 @@ def c2_shard_step(torch, Engine, dev_index, args, world, rank, sync_ranks, steps
         eng.load(snap)
         now = W.NOW_NS
         step = lambda: eng.apportion(now, writeback=True, asynchronous=True, defer_join=True)  # noqa: E731
-        run = timed_steps(torch, eng, step, steps, args.warmup, sync_ranks)
+        run = timed_steps(torch, eng, step, steps, args.warmup, sync_ranks, warm=warm_steps(len(snap["wants"])))
         sizes = np.diff(snap["seg_off"])
         return {"rank": rank, "resources": len(sizes), "leases": int(sizes.sum()),
                 "predicted_bytes": int(tick_cost(sizes).sum()),
@@ -920,8 +986,16 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra C1 line of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: profiled steps "
+                         "(kernels, roofline, HBM fractions), the exchange self-check, the busy-GPU probe, the CPU "
+                         "baseline and the other workloads' lines under extra (see --no-cpu-baseline, --no-extra, "
+                         "--no-busy-probe)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one left (a seeded sample of the leases, every "
+                         "resource's sums, the exchange's templates) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the other workloads' lines under extra")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) on a node; gloo + --same-device rehearses N>1 on one GPU")
@@ -961,6 +1035,10 @@ def main():
                     help="test only: the exchange self-check's step corrupts one rank's gathered copy (expect "
                          "dist.consistent false)")
     args = ap.parse_args()
+    if args.rehearse_shard:
+        args.full = True  # a rehearsal is its kernel times and its self-check
+    if args.check_corrupt and not args.full:
+        raise SystemExit("--check-corrupt corrupts the exchange self-check's step: it needs --full")
     if args.rehearse_shard:
         if args.workload not in ("c2", "c3") or args.gpus != 1 or args.rehearse_shard < 2:
             raise SystemExit("--rehearse-shard N (N >= 2) rehearses ranks of an N-GPU configs[3] (c3) or configs[2] "
@@ -1086,9 +1164,10 @@ def main():
                                                           if args.rehearse_shard else ")")
         return "local", None
 
-    def measure(layout):
-        """Load this rank's store (and root copy), run the timed steps; returns the run,
-        the snapshot and the engines (closed by the caller)."""
+    def measure(layout, dump_dir=None):
+        """Load this rank's store (and root copy), run the timed steps (and write their
+        outputs to dump_dir); returns the run, the snapshot and the engines (closed by
+        the caller)."""
         snap = make_workload(args.workload, s_rank, s_world, layout, args.c2_partition)
         R = len(snap["seg_off"]) - 1
         eng = Engine(dev_index, args.lib)
@@ -1098,7 +1177,9 @@ def main():
         step = lambda: eng.apportion(now, writeback=True, asynchronous=True, defer_join=True)  # noqa: E731
         root = ht = None
         if args.workload == "c4":
-            step = streaming_step(eng, snap, rank, 2 * args.steps + args.warmup + 1, not args.c4_sync_apply)
+            # a round's batch for every warm-up, timed and (--full) profiled step, and one more
+            step = streaming_step(eng, snap, rank, (2 if args.full else 1) * args.steps + args.warmup + 1,
+                                  not args.c4_sync_apply)
         if hier:
             from doorman_amd.hierarchy import HierarchicalTick, root_snapshot
             root = Engine(dev_index, args.lib)
@@ -1119,9 +1200,16 @@ def main():
                                         lease_length_s=20))
                 ht = HierarchicalTick(torch, eng, root, R, world, rank, gather, pipelined=not args.no_pipeline)
             step = lambda: ht.tick(now, asynchronous=True)  # noqa: E731
+        dump = None
+        if dump_dir:
+            def dump():
+                dump_outputs(dump_dir, eng, getattr(step, "last_now", now), ht, step,
+                             f"_rank{rank}" if world > 1 else "")
         run = timed_steps(torch, eng, step, args.steps, args.warmup, sync_ranks, extra_warm=args.workload != "c4",
-                          also=[root] if root is not None else [])
-        run["dense_frac"] = tick_dense_fraction(eng, snap, step)
+                          also=[root] if root is not None else [], profile=args.full, after_timed=dump,
+                          warm=warm_steps(len(snap["wants"])))
+        if args.full:
+            run["dense_frac"] = tick_dense_fraction(eng, snap, step)
         run["last_now"] = getattr(step, "last_now", now)
         if hasattr(step, "finish"):
             step.finish()  # the C4 rounds' asynchronous batches: retired, none rejected
@@ -1129,7 +1217,7 @@ def main():
         if ht is not None:
             ht.sync()
             ht.check()  # any server whose request the root rejected (server.go:863-866) fails loudly
-            if layout == "sharded":
+            if layout == "sharded" and args.full:
                 run["self_check"] = exchange_self_check(torch, dist, ht, eng, root, c3_bounds(s_world), rank, world,
                                                         s_rank, now, red_dev, corrupt=args.check_corrupt)
         # what every rank saw: its step time, the ranks its RCCL communicator counts (the
@@ -1159,17 +1247,19 @@ def main():
         print(json.dumps(rehearse_c2_shards(torch, Engine, dev_index, args, s_world, ranks)), flush=True)
         return
 
-    run, snap, eng, root = measure(layout)
+    run, snap, eng, root = measure(layout, args.dump_outputs)
     R, N = len(snap["seg_off"]) - 1, len(snap["wants"])
     t_max, n_total = run["t_max"], run["n_total"]
-    roofline = roofline_of(args.workload, snap, run, args.steps,
-                           single_kernel_tick=not hier and args.workload != "c4")
+    roofline = None
+    if args.full:
+        roofline = roofline_of(args.workload, snap, run, args.steps,
+                               single_kernel_tick=not hier and args.workload != "c4")
     if args.workload == "c4" and roofline is not None and not args.no_busy_probe:
         roofline["busy_gpu"] = busy_kernel_probe(eng, snap, run["last_now"], run["dense_frac"])
     now = W.NOW_NS
 
     extra = {}
-    if args.rehearse_shard:
+    if args.rehearse_shard or not args.full:
         args.no_extra = True
         args.no_cpu_baseline = True
     cpu = None
@@ -1193,7 +1283,8 @@ def main():
             else:
                 kx = args.steps
                 stx = lambda: ex.apportion(now, writeback=True, asynchronous=True, defer_join=True)  # noqa: E731
-            rx = timed_steps(torch, ex, stx, kx, args.warmup, sync_ranks, extra_warm=name != "c4")
+            rx = timed_steps(torch, ex, stx, kx, args.warmup, sync_ranks, extra_warm=name != "c4",
+                             warm=warm_steps(len(snapx["wants"])))
             rx["dense_frac"] = tick_dense_fraction(ex, snapx, stx)
             if hasattr(stx, "finish"):
                 stx.finish()
@@ -1258,14 +1349,19 @@ def main():
             "exchange": exchange_used["mode"] if hier else None,
             # (a rehearsal reports its exchange self-check too: one rank of the rehearsed node)
             "dist": dist_fields(dist_info, run) if world > 1 or args.rehearse_shard else None,
-            **tick_fracs(snap, run["dense_frac"], t_max / args.steps),
             "host_enqueue_us_per_step": round(run["host_enqueue_s"] / args.steps * 1e6, 2),
-            "kernels": {k: {"launches": v[0], "avg_us": round(v[1] / max(v[0], 1) * 1e3, 2)}
-                        for k, v in run["ktimes"].items()},
-            "roofline": roofline,
-            "extra": extra or None,
-            "cpu_baseline": cpu,
+            "full": bool(args.full),
+            "outputs": args.dump_outputs,
         }
+        if args.full:  # what the runs after the timed steps measured
+            line.update({
+                **tick_fracs(snap, run["dense_frac"], t_max / args.steps),
+                "kernels": {k: {"launches": v[0], "avg_us": round(v[1] / max(v[0], 1) * 1e3, 2)}
+                            for k, v in run["ktimes"].items()},
+                "roofline": roofline,
+                "extra": extra or None,
+                "cpu_baseline": cpu,
+            })
         if args.rehearse_shard:
             line["metric"] = "rehearsal: one rank's step of an N-GPU configs[3] node on one GPU (not a bench line)"
             line["value"] = N * args.steps / t_max

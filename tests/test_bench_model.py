@@ -158,3 +158,52 @@ def test_l3_resident_flag_c1_not_c3():
     run = {"ktimes": {"block128x8_dense": (20, 0.6)}, "stream_ms": 0.4, "dense_frac": 1.0, "parts": 2}
     r = bench.roofline_of("c1", snap, run, 10, True)
     assert r["l3_resident"] and r["frac"] is None and r["frac_l3"] > 0 and r["frac_of_copy_ceiling"] is None
+
+
+class _FakeEngine:
+    """The read calls --dump-outputs makes, answered from arrays."""
+
+    def __init__(self, n, r):
+        self.n_leases = n
+        self.gets = np.arange(n, dtype=np.float64) * 0.5
+        self.exp = np.full(n, W.NOW_NS + 20 * W.NS, np.int64)
+        self.exp[3] = W.RELEASED
+        self.res = {"count": np.arange(r, dtype=np.int64), "sum_has": np.ones(r), "sum_wants": np.full(r, 2.0),
+                    "safe_capacity": np.full(r, np.nan)}
+        self.synced = 0
+
+    def sync(self):
+        self.synced += 1
+
+    def leases_rows(self, rows):
+        return self.gets[rows], self.exp[rows]
+
+    def resources(self, safe=True):
+        return dict(self.res)
+
+
+def test_dump_outputs_writes_float64_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array float64; a small store whole, a larger one by a sample
+    that is the same from call to call; expiries relative to the tick's time, a released
+    row as -2^63."""
+    eng = _FakeEngine(10, 4)
+    bench.dump_outputs(str(tmp_path / "a"), eng, W.NOW_NS)
+    assert eng.synced >= 1
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["lease_expiry_rel_ns", "lease_gets", "lease_rows", "resource_count",
+                           "resource_safe_capacity", "resource_sum_has", "resource_sum_wants"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    np.testing.assert_array_equal(got["lease_rows"], np.arange(10))
+    np.testing.assert_array_equal(got["lease_gets"], eng.gets)
+    want = np.full(10, 20.0 * W.NS)
+    want[3] = -2.0 ** 63
+    np.testing.assert_array_equal(got["lease_expiry_rel_ns"], want)
+    np.testing.assert_array_equal(got["resource_count"], np.arange(4.0))
+    monkeypatch.setattr(bench, "DUMP_ROWS", 1000)
+    big = _FakeEngine(50_000, 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, W.NOW_NS, suffix="_rank1")
+    rb, rc = (np.load(tmp_path / d / "lease_rows_rank1.npy") for d in ("b", "c"))
+    np.testing.assert_array_equal(rb, rc)
+    assert 900 < len(rb) <= 1000 and (np.diff(rb) > 0).all() and rb.max() < 50_000
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "lease_gets_rank1.npy"), big.gets[rb.astype(np.int64)])

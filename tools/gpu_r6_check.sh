@@ -17,7 +17,7 @@ if [ -n "${SWEEP:-}" ]; then
   cat $OUT/size_sweep.jsonl | cut -c1-110
 fi
 for w in ${BENCH:-}; do
-  timeout -k 10 400 python -u bench.py --workload $w --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline $BENCHARGS \
+  timeout -k 10 400 python -u bench.py --full --workload $w --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline $BENCHARGS \
     > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail -8 $OUT/bench_$w.err; exit 1; }
   python3 -c "
 import json

@@ -13,6 +13,6 @@ for w in ${WORKLOADS:-c3 c1}; do
   echo "profiled $w"
 done
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 600 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -8 $OUT/bench_default.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -8 $OUT/bench_default.err; exit 1; }
   tail -c 600 $OUT/bench_default.json
 fi
