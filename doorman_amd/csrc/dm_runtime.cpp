@@ -1392,8 +1392,9 @@ int dm_sync(dm_ctx* c) {
   return rc;
 }
 
-// Asynchronous store batches still in flight finish before the store or its
-// configuration is replaced (their outcome is dropped with the store they updated).
+// Asynchronous store batches still in flight finish before the store is replaced.  Their
+// outcome is dropped with the store they updated: a rejected batch's error is lost here
+// on purpose, and the load's own scan sets maybe_general / all_sub_one anew.
 static void async_drain(dm_ctx* c) {
   for (int i = 1; i <= dm_ctx::kAsyncSets; ++i)
     if (c->aset[i].pending) {
@@ -1499,9 +1500,18 @@ int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
   return DM_OK;
 }
 
+// Retire every in-flight asynchronous set, oldest first (defined with dm_store_apply_wait).
+static int async_retire_all(dm_ctx* c);
+
 int dm_config_load(dm_ctx* c, int64_t R, const dm_resource_cfg* cfg) {
   DM_ENTER(c);
-  async_drain(c);  // (an in-flight batch's arrivals take the lease lengths they were sent under)
+  // In-flight batches finish first (their arrivals take the lease lengths they were sent
+  // under).  The store stays, so their outcome counts: every set is retired through
+  // apply_check, which keeps maybe_general / all_sub_one true to the rows (a drained NaN
+  // wants or other subclient count would otherwise leave later ticks on the non-general
+  // path: tests/test_general_transitions_gpu.py), and a rejected batch's error is
+  // returned instead of loading the configuration -- the caller calls again.
+  if (int ra = async_retire_all(c)) return ra;
   c->rows_changed();
   if (!cfg || R < 0 || !cfg->kind || !cfg->capacity || !cfg->lease_length_s || !cfg->refresh_interval_s ||
       !cfg->learning_end_ns || !cfg->parent_expiry_ns || !cfg->safe_capacity)
@@ -2785,8 +2795,9 @@ int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) {
   return DM_OK;
 }
 
-int dm_store_apply_wait(dm_ctx* c) {
-  DM_ENTER(c);
+// Every set is retired (the flags of sets after a rejected one still count); the first
+// failure and its message are returned.
+static int async_retire_all(dm_ctx* c) {
   int first = DM_OK;
   std::string msg;
   for (int64_t k = c->async_seq - dm_ctx::kAsyncSets; k < c->async_seq; ++k) {  // oldest first
@@ -2799,6 +2810,11 @@ int dm_store_apply_wait(dm_ctx* c) {
   }
   if (first != DM_OK) c->err = msg;
   return first;
+}
+
+int dm_store_apply_wait(dm_ctx* c) {
+  DM_ENTER(c);
+  return async_retire_all(c);
 }
 
 int dm_host_alloc(dm_ctx* c, size_t bytes, void** out) {

@@ -175,7 +175,13 @@ int dm_join(dm_ctx* ctx);
 int dm_stream_wait(dm_ctx* ctx, void* hip_stream);
 
 /* ---- LeaseStore: device-resident columnar table ---- */
+/* Replaces the store.  In-flight dm_store_apply_async batches finish first; their outcome
+   (a rejected batch's error included) is dropped with the store they updated. */
 int dm_store_load(dm_ctx* ctx, const dm_snapshot* snap);
+/* Replaces the configuration; the store stays.  In-flight dm_store_apply_async batches
+   are retired first, oldest first, every one of them (as dm_store_apply_wait).  If one
+   was rejected, its error is returned (DM_E_RANGE / DM_E_INVAL, "an earlier asynchronous
+   batch's ...") and the configuration is not loaded: call again. */
 int dm_config_load(dm_ctx* ctx, int64_t n_resources, const dm_resource_cfg* cfg);
 /* Assign (store.go:153-167) on existing rows: sums += new - old; expiry_ns as given */
 int dm_store_upsert(dm_ctx* ctx, int64_t n, const int64_t* rows, const double* has, const double* wants,
@@ -211,9 +217,12 @@ int dm_store_apply(dm_ctx* ctx, const dm_store_batch* batch);
    and the batch's later parts are not applied, its earlier parts are, and so is every
    batch enqueued after it.  While a batch with a refresh or arrivals is in flight, ticks
    are prepared for heterogeneous subclients (k_general) as for a maybe-general store.
-   dm_store_load and dm_config_load wait for in-flight batches first (their outcome is
-   dropped).  The C4 streaming round: its PCIe copies back to back from round to round
-   (DESIGN.md §5). */
+   dm_store_load waits for in-flight batches first and drops their outcome with the store
+   they updated (a rejected batch's error included, on purpose).  dm_config_load keeps
+   the store, so it retires them as dm_store_apply_wait does: their NaN wants / other
+   subclient counts keep later ticks prepared for k_general, and a rejected batch's
+   error is returned by dm_config_load, which then loads nothing (call it again).  The
+   C4 streaming round: its PCIe copies back to back from round to round. */
 int dm_store_apply_async(dm_ctx* ctx, const dm_store_batch* batch);
 /* Retire every in-flight dm_store_apply_async batch, oldest first; returns the first
    failure (DM_OK if none). */
