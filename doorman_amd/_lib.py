@@ -17,6 +17,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "doorman_hip.h")
 DM_OK, DM_E_INVAL, DM_E_HIP, DM_E_STATE, DM_E_KIND, DM_E_RANGE, DM_E_ARGUMENT, DM_E_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7
 DM_HIER_INVALID, DM_HIER_COUNT_RANGE = 1, 2
 DM_RCCL_ID_BYTES = 128
+DM_RELAYOUT_COMPACT = 1
 DM_WRITEBACK, DM_AGG_RECOMPUTE, DM_ASYNC, DM_WB_INPLACE, DM_WB_ALTERNATE, DM_DEFER_JOIN = 1, 2, 4, 8, 16, 32
 
 
@@ -87,6 +88,8 @@ _SIGS = {
     "dm_store_update_wants_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                                   ctypes.c_int64, ctypes.c_void_p]),
     "dm_store_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Snapshot)]),
+    "dm_store_relayout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.c_void_p]),
     "dm_config_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ResourceCfg)]),
     "dm_store_upsert": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
     "dm_store_release": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -143,6 +146,7 @@ _SIGS = {
     "dm_server_resource": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64),
                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double)]),
+    "dm_server_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),
     "dm_server_ctx": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
 

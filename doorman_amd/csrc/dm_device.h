@@ -262,6 +262,39 @@ struct ResAgg {  // 32 B, read and written by every tick
   int64_t follow_exp;
 };
 
+// dm_store_relayout (dm_relayout.hip): the old table and its index, the new layout and
+// the fresh columns the moved rows are written into.  Rows are handled in scan blocks
+// of 2^kRowBlkShift old rows (one 256-thread workgroup each, every wave 16 x 64
+// consecutive rows).
+constexpr int kRlBlkRows = 1 << kRowBlkShift;
+constexpr uint32_t kRlDrop = 1u;      // default mode: a shrink would drop a row that is not released
+constexpr uint32_t kRlOver = 2u;      // compact mode: a resource's live rows exceed its new length
+constexpr uint32_t kRlGeneral = 4u;   // a resource leaving the small tiles holds NaN wants or subclients != 1
+constexpr uint32_t kRlInternal = 8u;  // a rank below its resource's base (never)
+constexpr uint32_t kRlReject = kRlDrop | kRlOver | kRlInternal;
+struct RelayoutArgs {
+  int64_t N, R;             // the old table
+  RowIndex ix;              // its seg_off and block index
+  const double* wants;
+  const double* has;
+  const int32_t* sub;
+  const int64_t* expiry;
+  const ResAgg* agg;        // follow_exp of the follower rows
+  int64_t Nn, Rn;           // the new table
+  const int64_t* new_off;   // [Rn + 1]
+  double* n_wants;
+  double* n_has;
+  int32_t* n_sub;
+  int64_t* n_expiry;
+  // compact mode: moved rows per scan block -> their exclusive prefix (in place), and per
+  // resource the moved rows of its first row's block before that row
+  int64_t* blk_pre;         // [blocks + 1]
+  int32_t* seg_local;       // [R]
+  int64_t* row_map;         // [N] or nullptr
+  uint32_t* flags;          // kRl*
+  unsigned long long* bad;  // the first rejected resource (atomicMin; starts all ones)
+};
+
 struct DevParams {
   const int64_t* seg_off;
   // lease table (SoA).  out_* alias these in writeback mode, so no __restrict__.

@@ -77,6 +77,7 @@ hipError_t fd_sort_pairs(void* temp, size_t* bytes, const double* kin, double* k
                          int32_t* vout, int64_t n, int nseg, const int64_t* begin, const int64_t* end,
                          hipStream_t st);
 hipError_t launch_hier_tick(const DevParams& p, const HierArgs& ha, hipStream_t st);
+hipError_t launch_relayout(const RelayoutArgs& a, int32_t* nblk, ResAgg* n_agg, bool compact, hipStream_t st);
 }  // namespace dm
 
 using namespace dm;
@@ -489,6 +490,12 @@ struct dm_ctx {
       if (aset[i].pending && aset[i].may_general) return true;
     return false;
   }
+  // dm_store_relayout: the rejection flags and the first rejected resource, compact mode's
+  // block counts / prefix and per-resource bases, the row map's device staging
+  DBuf<uint32_t> rl_flags;
+  DBuf<unsigned long long> rl_bad;
+  DBuf<int64_t> rl_blk_pre, rl_map;
+  DBuf<int32_t> rl_seg_local;
   DBuf<uint32_t> row_bits;     // device row bitmap for the uniqueness check, all-zero between calls
   DBuf<uint32_t> upd_flags;    // k_check_rows result (device)
   // dm_decide: a round's requests (grouped by resource), per-resource work items, results
@@ -691,6 +698,7 @@ struct dm_ctx {
       a.release();
       a.pending = false;
     }
+    rl_flags.release(); rl_bad.release(); rl_blk_pre.release(); rl_map.release(); rl_seg_local.release();
     row_bits.release(); upd_flags.release(); hier_status.release(); hier_lo.release(); pub_sync.release();
     for (int i = 0; i < kTplSlots; ++i) {
       tpl_cfg[i].release();
@@ -1126,7 +1134,7 @@ static hipError_t download(T* dst, const T* src, int64_t off, int64_t n, hipStre
 // ---------------------------------------------------------------------------
 extern "C" {
 
-const char* dm_version(void) { return "doorman-hip 0.6 (gfx950, abi 6)"; }
+const char* dm_version(void) { return "doorman-hip 0.7 (gfx950, abi 7)"; }
 
 int dm_device_count(int* out) {
   if (!out) return DM_E_INVAL;
@@ -2815,6 +2823,156 @@ static int async_retire_all(dm_ctx* c) {
 int dm_store_apply_wait(dm_ctx* c) {
   DM_ENTER(c);
   return async_retire_all(c);
+}
+
+// The store re-laid out in HBM (dm_relayout.hip): fresh columns take every row that
+// stays, the kernels flag what the new layout cannot hold, and the fresh columns become
+// the store's only when nothing was flagged -- a rejected call leaves the old columns,
+// index, sums and plan as they were.  What crosses PCIe: the new seg_off, two flag words
+// and, when asked for, the row map.
+int dm_store_relayout(dm_ctx* c, int64_t n_resources, const int64_t* new_seg_off, uint32_t flags, int64_t* row_map) {
+  DM_ENTER(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  (void)c->check_device();
+  if (c->store_lost)
+    return c->fail(DM_E_STATE, "the store is lost (" + c->lost_msg + "): reload it (dm_store_load), a re-layout would carry its rows over");
+  // in-flight batches name rows of the old layout: they finish first, and a rejected one's
+  // error is returned before anything moves (as dm_config_load)
+  if (int ra = async_retire_all(c)) return ra;
+  const int64_t R = c->R, N = c->N, Rn = n_resources;
+  if (!new_seg_off || (flags & ~DM_RELAYOUT_COMPACT)) return c->fail(DM_E_INVAL, "bad re-layout arguments");
+  if (Rn < R) return c->fail(DM_E_INVAL, "a re-layout keeps every resource: n_resources below the store's count");
+  if (Rn > INT32_MAX - 1) return c->fail(DM_E_INVAL, "too many resources for one context (max 2^31-2)");
+  if (new_seg_off[0] != 0) return c->fail(DM_E_INVAL, "new_seg_off must start at 0");
+  for (int64_t r = 0; r < Rn; ++r)
+    if (new_seg_off[r + 1] < new_seg_off[r]) return c->fail(DM_E_INVAL, "new_seg_off must be non-decreasing");
+  if (Rn != R && (!c->pub_ring.empty() || c->hs_leaf))
+    return c->fail(DM_E_STATE, "a publish ring or hierarchy pair is bound to this store (blocks of 1 + R records): "
+                               "the number of resources cannot change");
+  const int64_t Nn = new_seg_off[Rn];
+  const bool compact = flags & DM_RELAYOUT_COMPACT;
+  DM_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  hipStream_t st = c->stream;
+  DBuf<int64_t> n_off, n_exp;
+  DBuf<int32_t> n_blk, n_sub;
+  DBuf<double> n_wants, n_has;
+  DBuf<ResAgg> n_agg;
+  DBuf<uint8_t> n_expl;
+  auto drop = [&] {
+    n_off.release(); n_exp.release(); n_blk.release(); n_sub.release();
+    n_wants.release(); n_has.release(); n_agg.release(); n_expl.release();
+  };
+  auto hip_drop = [&](hipError_t e, const char* what) {
+    (void)hipStreamSynchronize(st);
+    drop();
+    return c->hip_fail(e, what);
+  };
+#define RL_HIP(expr, what)                                   \
+  do {                                                       \
+    const hipError_t _e = (expr);                            \
+    if (_e != hipSuccess) return hip_drop(_e, what);         \
+  } while (0)
+  RL_HIP(upload(n_off, new_seg_off, (size_t)Rn + 1, st), "upload seg_off");
+  RL_HIP(n_blk.ensure((size_t)((Nn >> kRowBlkShift) + 2)), "alloc row index");
+  RL_HIP(n_wants.ensure((size_t)Nn), "alloc wants");
+  RL_HIP(n_has.ensure((size_t)Nn), "alloc has");
+  RL_HIP(n_sub.ensure((size_t)Nn), "alloc subclients");
+  RL_HIP(n_exp.ensure((size_t)Nn), "alloc expiry");
+  RL_HIP(n_agg.ensure((size_t)Rn), "alloc running sums");
+  RL_HIP(n_expl.ensure((size_t)std::max<int64_t>(Rn, 1)), "alloc explicit flags");
+  RL_HIP(hipMemsetAsync(n_expl.p, 1, n_expl.n, st), "explicit flags");  // every row leaves with an expiry of its own
+  RL_HIP(c->rl_flags.ensure(1), "re-layout flags");
+  RL_HIP(c->rl_bad.ensure(1), "re-layout flags");
+  const int64_t nb = (N + kRlBlkRows - 1) / kRlBlkRows;
+  if (compact) {
+    RL_HIP(c->rl_blk_pre.ensure((size_t)nb + 1), "block prefix");
+    RL_HIP(c->rl_seg_local.ensure((size_t)std::max<int64_t>(R, 1)), "resource bases");
+  }
+  if (row_map && N > 0) RL_HIP(c->rl_map.ensure((size_t)N), "row map");
+  RelayoutArgs a{};
+  a.N = N;
+  a.R = R;
+  a.ix = c->row_index();
+  a.wants = c->wants.p;
+  a.has = c->has.p;
+  a.sub = c->sub.p;
+  a.expiry = c->expiry.p;
+  a.agg = c->agg.p;
+  a.Nn = Nn;
+  a.Rn = Rn;
+  a.new_off = n_off.p;
+  a.n_wants = n_wants.p;
+  a.n_has = n_has.p;
+  a.n_sub = n_sub.p;
+  a.n_expiry = n_exp.p;
+  a.blk_pre = compact ? c->rl_blk_pre.p : nullptr;
+  a.seg_local = compact ? c->rl_seg_local.p : nullptr;
+  a.row_map = row_map && N > 0 ? c->rl_map.p : nullptr;
+  a.flags = c->rl_flags.p;
+  a.bad = c->rl_bad.p;
+  RL_HIP(launch_relayout(a, n_blk.p, n_agg.p, compact, st), "re-layout");
+  uint32_t f = 0;
+  unsigned long long bad = 0;
+  RL_HIP(hipMemcpyAsync(&f, c->rl_flags.p, sizeof f, hipMemcpyDeviceToHost, st), "re-layout flags");
+  RL_HIP(hipMemcpyAsync(&bad, c->rl_bad.p, sizeof bad, hipMemcpyDeviceToHost, st), "re-layout flags");
+  RL_HIP(hipStreamSynchronize(st), "re-layout");
+  if (f & kRlReject) {
+    drop();
+    char buf[160];
+    if (f & kRlInternal) {
+      snprintf(buf, sizeof buf, "re-layout: inconsistent ranks at resource %llu", bad);
+      return c->fail(DM_E_INTERNAL, buf);
+    }
+    if (f & kRlDrop)
+      snprintf(buf, sizeof buf, "resource %llu: the new segment would drop a row that is not released", bad);
+    else
+      snprintf(buf, sizeof buf, "resource %llu: more live rows than its new segment holds", bad);
+    return c->fail(DM_E_RANGE, buf);
+  }
+  if (row_map && N > 0) {
+    RL_HIP(hipMemcpyAsync(row_map, c->rl_map.p, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, st), "row map");
+    RL_HIP(hipStreamSynchronize(st), "row map");
+  }
+#undef RL_HIP
+  // the fresh table becomes the store; the old one is freed
+  std::swap(c->seg_off, n_off);
+  std::swap(c->blk_seg, n_blk);
+  std::swap(c->wants, n_wants);
+  std::swap(c->has, n_has);
+  std::swap(c->sub, n_sub);
+  std::swap(c->expiry, n_exp);
+  std::swap(c->agg, n_agg);
+  std::swap(c->expl, n_expl);
+  drop();
+  if (Nn != N) {  // the alternate columns and lease outputs follow N at the next tick that needs them
+    c->out_gets.release();
+    c->out_expiry.release();
+  }
+  c->R = Rn;
+  c->N = Nn;
+  c->h_seg_off.assign(new_seg_off, new_seg_off + Rn + 1);
+  c->seg_uniform = 0;
+  if (Rn > 0) {
+    const int64_t g = new_seg_off[1];
+    bool same = g > 0;
+    for (int64_t r = 1; r < Rn && same; ++r) same = new_seg_off[r + 1] - new_seg_off[r] == g;
+    c->seg_uniform = same ? g : 0;
+  }
+  // maybe_general / all_sub_one are carried: no live row was added.  One case the rows
+  // themselves decide (kRlGeneral): a resource of the small tiles, which the load's scan
+  // never looked at, now in a bin that hands heterogeneous rows to k_general.
+  if (f & kRlGeneral)
+    if (int rg = mark_maybe_general(c)) return rg;
+  DM_HIP(c, c->rmask.ensure((size_t)(Nn / 2 + 64)), "alloc released-row masks");  // zeroed by upload_plan
+  build_plan(c);
+  if (int rc = upload_plan(c)) return rc;  // (with R unchanged: bin 4's shape by the kept kinds, update_bin4_shape)
+  DM_HIP(c, hipStreamSynchronize(st), "re-layout");
+  c->expl_rows = true;
+  c->rows_changed();
+  c->have_result = false;
+  c->hints_set = false;
+  if (Rn != R) c->cfg_loaded = false;  // the caller loads a configuration for the new count
+  return DM_OK;
 }
 
 int dm_host_alloc(dm_ctx* c, size_t bytes, void** out) {

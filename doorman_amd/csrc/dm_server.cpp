@@ -23,8 +23,8 @@
 // sums) until they expire.  The host keeps the client -> row maps, the rows'
 // lease mirror (has, expiry) and a min-heap of expiries, so Clean costs
 // O(expired log N), not a scan.  A resource that runs out of free rows grows:
-// the table is re-laid out with the resource's segment doubled, the running
-// sums carried over exactly (dm_read_resources -> dm_store_load aggregates).
+// the table is re-laid out on the device with the resource's segment doubled
+// (dm_store_relayout: rows, running sums and configuration stay in HBM).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -74,6 +74,7 @@ struct dm_server {
   std::vector<Req> pending;
   std::vector<std::pair<int64_t, std::string>> releases;
   std::vector<Out> results;
+  int64_t relayouts = 0;  // dm_server_stats
   std::string broken;  // set when a re-layout failed half way: every later tick refuses
 
   int fail(int code, const std::string& m) {
@@ -93,57 +94,41 @@ struct dm_server {
 
 namespace {
 
-// (Re)load the table with segment sizes `sizes`, carrying every client's row
-// (wants, has, subclients, expiry) and the running sums of the old layout.
+// Re-lay out the table with segment sizes `sizes` (none shorter than its resource's
+// last client row): dm_store_relayout moves the rows in HBM, order-preserving, with the
+// running sums and the configuration kept, and the host mirror's rows shift the same
+// way: new = new_off[r] + (old - old_off[r]).  No store row crosses PCIe.
 int relayout(dm_server* s, const std::vector<int64_t>& sizes) {
-  const int64_t R = s->R, oldN = s->N();
-  std::vector<double> o_has(oldN), o_wants(oldN);
-  std::vector<int64_t> o_sub(oldN), o_exp(oldN);
-  std::vector<int64_t> cnt(R, 0);
-  std::vector<double> sh(R, 0.0), sw(R, 0.0);
-  if (oldN > 0) {
-    int rc = dm_read_store(s->ctx, 0, oldN, o_has.data(), o_wants.data(), o_sub.data(), o_exp.data());
-    if (rc) return s->ctx_fail(rc);
-    rc = dm_read_resources(s->ctx, 0, R, cnt.data(), sh.data(), sw.data(), nullptr);
-    if (rc) return s->ctx_fail(rc);
-  }
+  const int64_t R = s->R;
   std::vector<int64_t> off(R + 1, 0);
   for (int64_t r = 0; r < R; ++r) off[r + 1] = off[r] + sizes[r];
   const int64_t N = off[R];
-  std::vector<double> n_has(N, 0.0), n_wants(N, 0.0);
-  std::vector<int64_t> n_sub(N, 0), n_exp(N, DM_RELEASED);
+  const int rc = dm_store_relayout(s->ctx, R, off.data(), 0, nullptr);
+  if (rc) return s->ctx_fail(rc);
+  s->relayouts += 1;
+  std::vector<double> n_has(N, 0.0);
+  std::vector<int64_t> n_exp(N, DM_RELEASED);
   std::vector<std::string> n_client(N);
-  std::vector<double> m_has(N, 0.0);
   for (int64_t r = 0; r < R; ++r) {
-    int64_t next = off[r];
-    auto& cl = s->clients[r];
-    for (auto& kv : cl) {
-      const int64_t o = kv.second, row = next++;
-      n_has[row] = o_has[o];
-      n_wants[row] = o_wants[o];
-      n_sub[row] = o_sub[o];
-      n_exp[row] = o_exp[o];
-      n_client[row] = kv.first;
-      m_has[row] = s->has[o];
-      kv.second = row;
+    const int64_t o0 = s->seg_off[r], olen = s->seg_off[r + 1] - o0, keep = std::min(olen, sizes[r]);
+    for (int64_t k = 0; k < keep; ++k) {
+      n_has[off[r] + k] = s->has[o0 + k];
+      n_exp[off[r] + k] = s->expiry[o0 + k];
+      n_client[off[r] + k] = std::move(s->row_client[o0 + k]);
     }
-    s->free_rows[r].clear();
-    for (int64_t row = off[r + 1] - 1; row >= next; --row) s->free_rows[r].push_back(row);
+    for (auto& kv : s->clients[r]) kv.second = off[r] + (kv.second - o0);
+    auto& fr = s->free_rows[r];
+    for (int64_t& row : fr) row = off[r] + (row - o0);
+    fr.erase(std::remove_if(fr.begin(), fr.end(), [&](int64_t row) { return row >= off[r + 1]; }), fr.end());
+    for (int64_t row = off[r + 1] - 1; row >= off[r] + olen; --row) fr.push_back(row);  // the new tail
   }
-  dm_snapshot snap{R, N, off.data(), n_wants.data(), n_has.data(), n_sub.data(), n_exp.data(),
-                   cnt.data(), sh.data(), sw.data()};
-  int rc = dm_store_load(s->ctx, &snap);
-  if (rc) return s->ctx_fail(rc);
-  const dm_resource_cfg cfg = s->cfg();
-  rc = dm_config_load(s->ctx, R, &cfg);
-  if (rc) return s->ctx_fail(rc);
   s->seg_off = off;
-  s->has = m_has;
-  s->expiry = n_exp;
-  s->row_client = n_client;
+  s->has.swap(n_has);
+  s->expiry.swap(n_exp);
+  s->row_client.swap(n_client);
   s->heap = {};
   for (int64_t row = 0; row < N; ++row)
-    if (n_exp[row] != DM_RELEASED) s->heap.push({n_exp[row], row});
+    if (s->expiry[row] != DM_RELEASED) s->heap.push({s->expiry[row], row});
   return DM_OK;
 }
 
@@ -195,11 +180,25 @@ int dm_server_create(int device, int64_t n_resources, const char* const* ids, co
   s->parent_expiry.assign(cfg->parent_expiry_ns, cfg->parent_expiry_ns + R);
   s->clients.assign(R, {});
   s->free_rows.assign(R, {});
+  // an empty table of R resources and their configuration, then its first layout:
+  // `slots` free rows each, made on the device
+  s->seg_off.assign(R + 1, 0);
+  const dm_snapshot empty{R, 0, s->seg_off.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  rc = dm_store_load(s->ctx, &empty);
+  if (!rc) {
+    const dm_resource_cfg c0 = s->cfg();
+    rc = dm_config_load(s->ctx, R, &c0);
+  }
+  if (rc) {
+    dm_server_destroy(s);
+    return rc;
+  }
   rc = relayout(s, std::vector<int64_t>(R, slots));
   if (rc) {
     dm_server_destroy(s);
     return rc;
   }
+  s->relayouts = 0;
   *out = s;
   return DM_OK;
 }
@@ -213,6 +212,13 @@ void dm_server_destroy(dm_server* s) {
 const char* dm_server_last_error(dm_server* s) { return s ? s->err.c_str() : "null server"; }
 
 dm_ctx* dm_server_ctx(dm_server* s) { return s ? s->ctx : nullptr; }
+
+int dm_server_stats(dm_server* s, int64_t* out, int max) {
+  if (!s || !out || max < 0) return DM_E_INVAL;
+  const int64_t v[2] = {s->relayouts, 0};  // the re-layouts move rows in HBM only
+  for (int i = 0; i < 2 && i < max; ++i) out[i] = v[i];
+  return 2;
+}
 
 int dm_server_get_capacity(dm_server* s, const char* client, const char* resource, double has, double wants,
                            int64_t subclients, int64_t* ticket) {

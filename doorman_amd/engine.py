@@ -126,6 +126,22 @@ class Engine:
         self.n_resources, self.n_leases = s.n_resources, s.n_leases
         self.seg_off = keep["seg_off"].copy()  # the table layout (host copy)
 
+    def relayout(self, seg_off, compact: bool = False, want_row_map: bool = False):
+        """dm_store_relayout: the same rows under a new seg_off, moved on the device (resources
+        grow, shrink or are appended: len(seg_off) - 1 >= n_resources).  Default: each
+        resource's rows keep their offsets, new tail rows are free; compact: its rows that are
+        not released move to the front of its segment.  Returns the row map (new row of every
+        old row, -1 for a dropped released row) when asked for, else None."""
+        off = _c(seg_off, np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise ValueError("seg_off must hold n_resources + 1 offsets")
+        row_map = np.empty(self.n_leases, np.int64) if want_row_map else None
+        self._chk(self._L.dm_store_relayout(self._ctx, len(off) - 1, _ptr(off),
+                                            _lib.DM_RELAYOUT_COMPACT if compact else 0, _ptr(row_map)))
+        self.n_resources, self.n_leases = len(off) - 1, int(off[-1])
+        self.seg_off = off.copy()
+        return row_map
+
     def load_config(self, snap: dict):
         R = len(snap["kind"])
         keep = {

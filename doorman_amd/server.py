@@ -88,6 +88,13 @@ class TickServer:
                                           ctypes.byref(s)))
         return Lease(c.value, e.value, r.value, s.value)
 
+    def stats(self) -> dict:
+        """dm_server_stats: re-layouts of the table since creation and the store rows that
+        crossed PCIe in them (0: dm_store_relayout moves them on the device)."""
+        arr = (ctypes.c_int64 * 2)()
+        self._chk(self._L.dm_server_stats(self._srv, arr, 2))
+        return {"relayouts": int(arr[0]), "pcie_rows": int(arr[1])}
+
     def resource(self, resource: str) -> dict:
         n, cnt, sh, sw = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
         self._chk(self._L.dm_server_resource(self._srv, resource.encode(), ctypes.byref(n), ctypes.byref(cnt),

@@ -7,6 +7,8 @@
  * Go side):
  *
  *   LeaseStore interface        go/server/doorman/store.go:68-103   -> dm_store_* / dm_read_*
+ *   a growing client map        go/server/doorman/store.go:153-167  -> dm_store_relayout (a longer segment)
+ *   resources made on first use go/server/doorman/resource.go:153-163 -> dm_store_relayout (appended segments)
  *   NewLeaseStore               go/server/doorman/store.go:114      -> dm_create + dm_store_load
  *   Algorithm (per request)     go/server/doorman/algorithm.go:44   -> dm_apportion (batch of every client)
  *   GetAlgorithm / algorithms   go/server/doorman/algorithm.go:304-313 -> dm_resource_cfg.kind
@@ -38,7 +40,9 @@
 extern "C" {
 #endif
 
-/* 6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
+/* 7: dm_store_relayout (the device store re-laid out in place: resources grow, shrink, are
+   compacted or appended without a row crossing PCIe) and dm_server_stats.
+   6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
    without waiting; its outcome reported by a later call).
    5 (round 6): dm_store_lost (the read calls work on a lost store); dm_plan_info's slot 18 is the class streams' hardware-queue assignment the
    context's queue calibration chose (-1 before it finished); returns 19.
@@ -48,7 +52,7 @@ extern "C" {
    record 0 holds two 32-bit flags words (their OR is the request's flags); the DM_*
    environment switches other than the test hooks are gone.  3 (round 4): dm_hier_attach / dm_hier_step / dm_rccl_unique_id /
    dm_hier_comm_init and DM_E_INTERNAL added, dm_set_large_path and DM_LARGE_* removed. */
-#define DM_ABI_VERSION 6
+#define DM_ABI_VERSION 7
 
 /* return codes */
 #define DM_OK 0
@@ -178,6 +182,36 @@ int dm_stream_wait(dm_ctx* ctx, void* hip_stream);
 /* Replaces the store.  In-flight dm_store_apply_async batches finish first; their outcome
    (a rejected batch's error included) is dropped with the store they updated. */
 int dm_store_load(dm_ctx* ctx, const dm_snapshot* snap);
+/* Re-lays out the store on the device: the same rows under a new seg_off, with room for a
+   growing, shrinking or new population, and no row over PCIe (a gather of 28 B per row in
+   HBM; dm_store_load stays the only way to bring rows from the host).
+     n_resources >= the store's count R; resources [R, n_resources) are new: every row free,
+     running sums {0, 0.0, 0.0}.  new_seg_off: n_resources + 1 entries, non-decreasing, from 0.
+     Default (order-preserving): row old_off[r] + k moves to new_off[r] + k for
+       k < min(old length, new length); the new tail rows are free (has 0, wants 0,
+       subclients 0, expiry DM_RELEASED).  A shrink that would drop a row that is not
+       released is rejected: DM_E_RANGE, the message naming the resource.
+     DM_RELAYOUT_COMPACT: each resource's rows that are not released move, in their old
+       order, to the front of its new segment; the rest of the segment is free.  DM_E_RANGE
+       when a resource holds more such rows than its new segment.
+     row_map (or NULL): [old n_leases], row_map[i] = the new row of old row i, or -1 for a
+       released row that was dropped; computed on the device, the only per-row data to cross
+       PCIe.
+   A rejected call (DM_E_RANGE, DM_E_INVAL for a bad seg_off or n_resources < R) leaves
+   the store exactly as it was.  After a successful one the context is in the state this
+   host route would leave: dm_read_store of every row, the permutation above, dm_store_load
+   with agg_* = the dm_read_resources values -- the running sums carried bit for bit, not
+   recomputed; dm_read_store returning the same four columns; the last tick's leases gone
+   (dm_read_leases: DM_E_STATE until the next tick); every row holding its own expiry until
+   the next writeback tick makes it a follower again.  In-flight dm_store_apply_async
+   batches are retired first, as by dm_config_load: a rejected batch's error is returned
+   and nothing is re-laid.  With n_resources == R the configuration is kept; otherwise it
+   is stale, as after dm_store_load with another R: load one for the new count.
+   DM_E_STATE: no store, a lost store (dm_store_lost), or n_resources != R while a
+   dm_publish_ring / dm_hier_attach pair is bound (their blocks hold 1 + R records). */
+#define DM_RELAYOUT_COMPACT 1u
+int dm_store_relayout(dm_ctx* ctx, int64_t n_resources, const int64_t* new_seg_off, uint32_t flags,
+                      int64_t* row_map);
 /* Replaces the configuration; the store stays.  In-flight dm_store_apply_async batches
    are retired first, oldest first, every one of them (as dm_store_apply_wait).  If one
    was rejected, its error is returned (DM_E_RANGE / DM_E_INVAL, "an earlier asynchronous
@@ -462,7 +496,8 @@ int dm_store_stats(dm_ctx* ctx, int64_t* out, int max);
  * (dm_server_lease then reports an error for its tickets) and forgets the new
  * clients it had placed.  Resources are configured up front (the outcome of
  * the reference's LoadConfig; config parsing and glob matching stay there);
- * every resource's segment of the table grows when it runs out of free rows. */
+ * every resource's segment of the table grows when it runs out of free rows
+ * (dm_store_relayout: the rows stay in HBM, the host mirror's rows shift with them). */
 typedef struct dm_server dm_server;
 
 /* resource_ids: R NUL-terminated ids; cfg: their configuration (dm_config_load);
@@ -488,6 +523,10 @@ int dm_server_lease(dm_server* srv, int64_t ticket, double* capacity, int64_t* e
 /* store state: number of clients holding a lease on a resource, and its running sums */
 int dm_server_resource(dm_server* srv, const char* resource, int64_t* clients, int64_t* count, double* sum_has,
                        double* sum_wants);
+/* counters since dm_server_create: out[0] = re-layouts of the table (resources that ran out
+ * of free rows), out[1] = store rows that crossed PCIe in them (0: they are re-laid out on
+ * the device); fills up to max entries, returns 2 */
+int dm_server_stats(dm_server* srv, int64_t* out, int max);
 /* the underlying context (profiling, dm_read_*) */
 dm_ctx* dm_server_ctx(dm_server* srv);
 
