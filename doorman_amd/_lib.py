@@ -18,6 +18,8 @@ DM_OK, DM_E_INVAL, DM_E_HIP, DM_E_STATE, DM_E_KIND, DM_E_RANGE, DM_E_ARGUMENT, D
 DM_HIER_INVALID, DM_HIER_COUNT_RANGE = 1, 2
 DM_RCCL_ID_BYTES = 128
 DM_RELAYOUT_COMPACT = 1
+DM_CLEAN_PEEK = 1
+DM_NO_EXPIRY = 2**63 - 1  # INT64_MAX: dm_clean_result.next_expiry_ns when no live row is left
 DM_WRITEBACK, DM_AGG_RECOMPUTE, DM_ASYNC, DM_WB_INPLACE, DM_WB_ALTERNATE, DM_DEFER_JOIN = 1, 2, 4, 8, 16, 32
 
 
@@ -67,6 +69,11 @@ class ResourceCfg(ctypes.Structure):
     ]
 
 
+class CleanResult(ctypes.Structure):
+    """dm_clean_result: what one dm_store_clean did."""
+    _fields_ = [("released", ctypes.c_int64), ("next_expiry_ns", ctypes.c_int64)]
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("launches", ctypes.c_int64), ("total_ms", ctypes.c_double)]
 
@@ -90,6 +97,8 @@ _SIGS = {
     "dm_store_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Snapshot)]),
     "dm_store_relayout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32,
                                          ctypes.c_void_p]),
+    "dm_store_clean": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.POINTER(CleanResult)]),
+    "dm_read_cleaned": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "dm_config_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ResourceCfg)]),
     "dm_store_upsert": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
     "dm_store_release": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),

@@ -295,6 +295,26 @@ struct RelayoutArgs {
   unsigned long long* bad;  // the first rejected resource (atomicMin; starts all ones)
 };
 
+// dm_store_clean (dm_clean.hip): Clean (store.go:169-181) over the whole table, in the
+// re-layout's scan blocks of 2^kRowBlkShift rows.  A row lapses when it is not released
+// and now > its resolved expiry (the followers' for a follower, its own for an explicit row).
+struct CleanArgs {
+  int64_t N;
+  RowIndex ix;
+  double* has;
+  double* wants;
+  int32_t* sub;
+  const int64_t* expiry;
+  ResAgg* agg;
+  uint8_t* expl;
+  int64_t now;
+  int64_t* blk_pre;   // [blocks + 2]: lapsed rows per block -> their exclusive prefix (in place),
+                      // then the total and the earliest expiry among the rows that stay
+  int64_t* blk_min;   // [blocks]: each block's earliest expiry among the rows that stay
+  int64_t* list;      // [list_n]: the lapsed rows, ascending
+  int64_t list_n;
+};
+
 struct DevParams {
   const int64_t* seg_off;
   // lease table (SoA).  out_* alias these in writeback mode, so no __restrict__.

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_kernel_util.h"
+#include "dm_update_util.h"
 
 namespace dm {
 
@@ -2347,59 +2348,8 @@ __global__ __launch_bounds__(256) void k_large_map_het(DevParams p, const Chunk*
 // --------------------------------------------------------------------------
 // Assign on existing rows (store.go:153-167): running sums += new - old.
 // Rows of one call may hit the same resource, so the deltas reach the sums
-// through atomics — one per run of a resource within a wave (wave_seg_add).
-// resource owning row r: last s with seg_off[s] <= r.  A coarse index (the
-// resource holding the first row of every 2^kRowBlkShift-row block) narrows the
-// binary search to the few resources of r's block.
-__device__ __forceinline__ int seg_of_row(const RowIndex& ix, int64_t r) {
-  const int64_t* __restrict__ seg_off = ix.seg_off;
-  const int64_t b = r >> kRowBlkShift;
-  int64_t lo = ix.blk_seg[b];
-  int64_t hi = (int64_t)ix.blk_seg[b + 1] + 1;  // invariant: seg_off[lo] <= r < seg_off[hi]
-  if (hi > ix.R) hi = ix.R;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= r)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return (int)lo;
-}
-
-// Add per-row deltas to their resources' running sums: lanes of a wave that hit
-// the same resource are summed first (DPP) and add once; a wave whose rows spread
-// over many resources adds per lane.  Every lane of the wave must call this.
-__device__ __forceinline__ void wave_seg_add(ResAgg* agg, bool active, int seg, double dh, double dw, long long ds,
-                                             bool with_has, bool with_count) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long act = __ballot(active);
-  const int prev = __shfl(seg, lane > 0 ? lane - 1 : 0, 64);
-  const bool head = active && (lane == 0 || !((act >> (lane - 1)) & 1) || prev != seg);
-  if (__popcll(__ballot(head)) > 8) {
-    if (active) {
-      if (with_has) atomicAdd(&agg[seg].sum_has, dh);
-      atomicAdd(&agg[seg].sum_wants, dw);
-      if (with_count) atomicAdd((unsigned long long*)&agg[seg].count, (unsigned long long)ds);
-    }
-    return;
-  }
-  unsigned long long rem = act;
-  while (rem) {
-    const int h = __builtin_ctzll(rem);
-    const int s0 = __builtin_amdgcn_readlane(seg, h);
-    const unsigned long long m = __ballot(active && seg == s0) & rem;
-    const bool in = (m >> lane) & 1;
-    AggR v{in ? ds : 0, in ? dh : 0.0, in ? dw : 0.0};
-    v = wave_reduce(v, OpR());
-    if (lane == h) {
-      if (with_has) atomicAdd(&agg[s0].sum_has, v.h);
-      atomicAdd(&agg[s0].sum_wants, v.w);
-      if (with_count) atomicAdd((unsigned long long*)&agg[s0].count, (unsigned long long)v.cnt);
-    }
-    rem &= ~m;
-  }
-}
+// through atomics — one per run of a resource within a wave (wave_seg_add,
+// dm_update_util.h, with seg_of_row and the dense-state helpers).
 
 // Validation of one store-update call on the device (no O(n) host pass): rows in
 // range and unique within the call (a row bitmap, all-zero between calls), and
@@ -2445,36 +2395,6 @@ __global__ void k_clear_rows(int64_t n, const int64_t* __restrict__ rows, int64_
 // Narrow arrivals (dm_store_batch): has == nullptr -> 0; sub32 instead of sub;
 // expiry == nullptr -> the resource's now + lease length (the Assign's expiry,
 // store.go:161).
-// one byte of a dense resource's masks (dm_device.h mask_pos), atomically: rows of one
-// resource share the mask words
-__device__ __forceinline__ void mask_bit(uint8_t* base, int32_t off, int32_t bit, bool set) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(base + off);
-  unsigned* w = reinterpret_cast<unsigned*>(a & ~uintptr_t(3));
-  const unsigned m = 1u << (bit + 8 * (int)(a & 3));
-  if (set)
-    atomicOr(w, m);
-  else
-    atomicAnd(w, ~m);
-}
-
-// The row's place in its dense resource's masks, or false when the resource is not in
-// a dense state its item describes (dm_device.h DenseUpd).
-__device__ __forceinline__ bool dense_row(const DenseUpd& du, const RowIndex& ix, int seg, int64_t r, uint8_t state,
-                                          MaskPos* mp, WorkItem** item) {
-  if (state < 2 || !du.item_of) return false;
-  const int32_t io = du.item_of[seg];
-  if (io < 0) return false;
-  const int bin = io >> 24;
-  WorkItem* it = du.bins[bin - 3] + (io & 0xFFFFFF);
-  if (((it->n >> 16) & 0xFF) != state - 1) return false;  // the hint is the state's (a new shape clears hints)
-  int G, R;
-  bin_shape(bin, du.bin4_wave, du.bin6_wide, &G, &R);
-  const int64_t lo = ix.seg_off[seg];
-  *mp = mask_pos(G, R, (int)(r - lo));
-  *item = it;
-  return true;
-}
-
 __global__ void k_upsert(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ has,
                          const double* __restrict__ wants, const int64_t* __restrict__ sub,
                          const int32_t* __restrict__ sub32, const int64_t* __restrict__ expiry,
@@ -2528,24 +2448,8 @@ __global__ void k_release(int64_t n, const int64_t* __restrict__ rows, RowIndex 
   if (active) {
     const int64_t r = rows[i];
     seg = seg_of_row(ix, r);
-    dh = -s_has[r];
-    dw = -s_wants[r];
-    ds = -(long long)sub_value(s_sub[r]);
-    s_has[r] = 0.0;
-    s_wants[r] = 0.0;
-    s_sub[r] = (int32_t)kSubReleased;  // the mark every reader decodes first: the expiry column is left alone
     (void)s_exp;
-    MaskPos mp;
-    WorkItem* it;
-    const uint8_t st = expl[seg];
-    if (dense_row(du, ix, seg, r, st, &mp, &it)) {  // stays dense: the row into the released-row mask
-      uint8_t* mb = du.rmask + rel_mask_offset(ix.seg_off[seg]);
-      mask_bit(mb, mp.roff, mp.rbit, true);
-      mask_bit(mb, mp.aoff, mp.abit, false);  // (a row that arrived since the last tick)
-      atomicOr(&it->n, 1 << 24);
-    } else if (st >= 2) {
-      expl[seg] = 0;  // no longer dense: the next tick reads the subclients column
-    }
+    release_row(ix, seg, r, s_has, s_wants, s_sub, expl, du, &dh, &dw, &ds);
   }
   wave_seg_add(agg, active, seg, dh, dw, ds, true, true);
 }

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_kernel_util.h"
+#include "dm_update_util.h"
 
 namespace dm {
 
@@ -31,32 +32,12 @@ constexpr int kRlWaveRows = kRlBlkRows / 4;   // 4 waves per workgroup
 constexpr int kRlIter = kRlWaveRows / 64;     // rows per lane
 static_assert(kRlIter == 16, "a wave's moved-row masks are kept in 16 registers");
 
-// resource owning row r: last s with seg_off[s] <= r (seg_of_row, dm_kernels.hip)
-__device__ __forceinline__ int rl_seg_of_row(const RowIndex& ix, int64_t r) {
-  const int64_t b = r >> kRowBlkShift;
-  int64_t lo = ix.blk_seg[b];
-  int64_t hi = (int64_t)ix.blk_seg[b + 1] + 1;
-  if (hi > ix.R) hi = ix.R;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ix.seg_off[mid] <= r)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return (int)lo;
-}
-
 // A row as dm_read_store reports it: its resource and its resolved expiry
 // (k_resolve_rows); a row is released when that expiry is DM_RELEASED.
 __device__ __forceinline__ void rl_row(const RelayoutArgs& a, int64_t i, int32_t* raw, int* seg, int64_t* e) {
   *raw = a.sub[i];
-  *seg = rl_seg_of_row(a.ix, i);
+  *seg = seg_of_row(a.ix, i);
   *e = sub_released(*raw) ? kReleased : (*raw < 0 ? a.expiry[i] : a.agg[*seg].follow_exp);
-}
-
-__device__ __forceinline__ int rl_lanes_below(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 __device__ __forceinline__ void rl_reject(const RelayoutArgs& a, uint32_t why, int seg) {
@@ -109,11 +90,11 @@ __global__ __launch_bounds__(256) void k_rl_fill(RelayoutArgs a, RowIndex nix, i
   bool fr[4] = {true, true, true, true};
   if (!all) {
     const int64_t last = j + 3 < a.Nn ? j + 3 : a.Nn - 1;
-    const int r0 = rl_seg_of_row(nix, j), r3 = rl_seg_of_row(nix, last);
+    const int r0 = seg_of_row(nix, j), r3 = seg_of_row(nix, last);
     for (int q = 0; q < 4; ++q) {
       const int64_t row = j + q;
       if (row >= a.Nn) break;
-      const int r = r0 == r3 ? r0 : rl_seg_of_row(nix, row);
+      const int r = r0 == r3 ? r0 : seg_of_row(nix, row);
       fr[q] = r >= a.R || row - a.new_off[r] >= a.ix.seg_off[r + 1] - a.ix.seg_off[r];
     }
   }
@@ -170,7 +151,7 @@ __global__ __launch_bounds__(256) void k_rl_count(RelayoutArgs a) {
   for (int v = 0; v < w; ++v) run += wtot[v];
 #pragma unroll
   for (int k = 0; k < kRlIter; ++k) {
-    if (first >> k & 1) a.seg_local[segs[k]] = run + rl_lanes_below(m[k]);
+    if (first >> k & 1) a.seg_local[segs[k]] = run + lanes_below(m[k]);
     run += __popcll(m[k]);
   }
   if (threadIdx.x == 0) a.blk_pre[blockIdx.x] = (int64_t)wtot[0] + wtot[1] + wtot[2] + wtot[3];
@@ -201,6 +182,12 @@ __global__ __launch_bounds__(1024) void k_rl_scan(int64_t* v, int64_t n) {
     run += x;
   }
   if (t == 1023) v[n] = s[1023];
+}
+
+// (for the other scans over blocks of kRlBlkRows rows: dm_clean.hip)
+hipError_t launch_rl_scan(int64_t* v, int64_t n, hipStream_t st) {
+  k_rl_scan<<<1, 1024, 0, st>>>(v, n);
+  return hipGetLastError();
 }
 
 // One old row to its place in the new table.  rank: (compact mode) the moved rows before
@@ -284,7 +271,7 @@ __global__ __launch_bounds__(256) void k_rl_scatter(RelayoutArgs a) {
 #pragma unroll
     for (int k = 0; k < kRlIter; ++k) {
       const int64_t i = row0 + k * 64 + lane;
-      if (i < a.N) rl_move<true>(a, i, raws[k], segs[k], es[k], run + rl_lanes_below(m[k]));
+      if (i < a.N) rl_move<true>(a, i, raws[k], segs[k], es[k], run + lanes_below(m[k]));
       run += __popcll(m[k]);
     }
   }

@@ -78,6 +78,8 @@ hipError_t fd_sort_pairs(void* temp, size_t* bytes, const double* kin, double* k
                          hipStream_t st);
 hipError_t launch_hier_tick(const DevParams& p, const HierArgs& ha, hipStream_t st);
 hipError_t launch_relayout(const RelayoutArgs& a, int32_t* nblk, ResAgg* n_agg, bool compact, hipStream_t st);
+hipError_t launch_clean_count(const CleanArgs& a, hipStream_t st);
+hipError_t launch_clean_apply(const CleanArgs& a, const DenseUpd& du, bool peek, hipStream_t st);
 }  // namespace dm
 
 using namespace dm;
@@ -496,7 +498,13 @@ struct dm_ctx {
   DBuf<unsigned long long> rl_bad;
   DBuf<int64_t> rl_blk_pre, rl_map;
   DBuf<int32_t> rl_seg_local;
-  DBuf<uint32_t> row_bits;     // device row bitmap for the uniqueness check, all-zero between calls
+  // dm_store_clean: the scan blocks' counts / prefix and minima, and the last clean's list
+  // of released rows (sized from its count, never from N), kept for dm_read_cleaned until
+  // the next clean, load or re-layout
+  DBuf<int64_t> cl_blk_pre, cl_blk_min, cl_list;
+  bool cl_valid = false;
+  int64_t cl_n = 0;
+  DBuf<uint32_t> row_bits;    // device row bitmap for the uniqueness check, all-zero between calls
   DBuf<uint32_t> upd_flags;    // k_check_rows result (device)
   // dm_decide: a round's requests (grouped by resource), per-resource work items, results
   DBuf<int64_t> rq_rows, rq_sub, rq_exp;
@@ -699,6 +707,8 @@ struct dm_ctx {
       a.pending = false;
     }
     rl_flags.release(); rl_bad.release(); rl_blk_pre.release(); rl_map.release(); rl_seg_local.release();
+    cl_blk_pre.release(); cl_blk_min.release(); cl_list.release();
+    cl_valid = false;
     row_bits.release(); upd_flags.release(); hier_status.release(); hier_lo.release(); pub_sync.release();
     for (int i = 0; i < kTplSlots; ++i) {
       tpl_cfg[i].release();
@@ -1499,6 +1509,7 @@ int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
     c->all_sub_one = s->subclients[i] == 1 || s->expiry_ns[i] == DM_RELEASED;
   DM_HIP(c, hipStreamSynchronize(st), "store load");
   c->store_loaded = true;
+  c->cl_valid = false;  // the last clean's list named rows of the store this one replaced
   c->store_lost = false;  // upload_plan cleared the device's failure words
   c->expl_rows = true;
   c->rows_changed();
@@ -2971,7 +2982,75 @@ int dm_store_relayout(dm_ctx* c, int64_t n_resources, const int64_t* new_seg_off
   c->rows_changed();
   c->have_result = false;
   c->hints_set = false;
+  c->cl_valid = false;  // the last clean's list named rows of the old layout
   if (Rn != R) c->cfg_loaded = false;  // the caller loads a configuration for the new count
+  return DM_OK;
+}
+
+// Clean (store.go:169-181) on the device (dm_clean.hip): a count pass, the 16-B result to
+// the host (which sizes the list from it), then the apply pass.  What crosses PCIe: that
+// result, and 8 B per listed row when dm_read_cleaned asks for them.
+int dm_store_clean(dm_ctx* c, int64_t now_ns, uint32_t flags, dm_clean_result* out) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  if (flags & ~DM_CLEAN_PEEK) return c->fail(DM_E_INVAL, "unknown clean flags");
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  // in-flight batches change which rows are live: they finish first, and a rejected one's
+  // error is returned before anything is cleaned (as dm_config_load)
+  if (int ra = async_retire_all(c)) return ra;
+  const bool peek = flags & DM_CLEAN_PEEK;
+  hipStream_t st = c->stream;
+  const int64_t nb = (c->N + kRlBlkRows - 1) / kRlBlkRows;
+  c->cl_valid = false;
+  c->cl_n = 0;
+  int64_t res[2] = {0, DM_NO_EXPIRY};
+  CleanArgs a{};
+  if (nb > 0) {
+    DM_HIP(c, c->cl_blk_pre.ensure((size_t)nb + 2), "clean block prefix");
+    DM_HIP(c, c->cl_blk_min.ensure((size_t)nb), "clean block minima");
+    a.N = c->N;
+    a.ix = c->row_index();
+    a.has = c->has.p;
+    a.wants = c->wants.p;
+    a.sub = c->sub.p;
+    a.expiry = c->expiry.p;
+    a.agg = c->agg.p;
+    a.expl = c->expl.p;
+    a.now = now_ns;
+    a.blk_pre = c->cl_blk_pre.p;
+    a.blk_min = c->cl_blk_min.p;
+    DM_HIP(c, c->timed(KC_RELEASE, st, [&] { return launch_clean_count(a, st); }), "clean count");
+    DM_HIP(c, hipMemcpyAsync(res, c->cl_blk_pre.p + nb, sizeof res, hipMemcpyDeviceToHost, st), "clean result");
+    if (int rs = c->synced("clean")) return rs;
+  }
+  const int64_t total = res[0];
+  if (total < 0 || total > c->N) return c->fail(DM_E_INTERNAL, "clean: inconsistent count of lapsed rows");
+  if (total > 0) {
+    DM_HIP(c, c->cl_list.ensure((size_t)total), "clean list");
+    a.list = c->cl_list.p;
+    a.list_n = total;
+    if (!peek) c->rows_changed();
+    DM_HIP(c, c->timed(KC_RELEASE, st, [&] { return launch_clean_apply(a, c->dense_upd(), peek, st); }),
+           "clean apply");
+    if (!peek) c->have_result = false;
+    if (int rs = c->synced("clean")) return rs;
+  }
+  c->cl_valid = true;
+  c->cl_n = total;
+  if (out) {
+    out->released = total;
+    out->next_expiry_ns = res[1];
+  }
+  return DM_OK;
+}
+
+int dm_read_cleaned(dm_ctx* c, int64_t off, int64_t n, int64_t* rows) {
+  DM_ENTER(c);
+  if (!c->cl_valid) return c->fail(DM_E_STATE, "no dm_store_clean list (none yet, or the store was loaded or re-laid out since)");
+  if (int rc = check_range(c, off, n, c->cl_n)) return rc;
+  if (n > 0 && !rows) return c->fail(DM_E_INVAL, "null rows");
+  DM_HIP(c, download(rows, (const int64_t*)c->cl_list.p, off, n, c->stream), "read cleaned rows");
+  DM_HIP(c, hipStreamSynchronize(c->stream), "read cleaned rows");
   return DM_OK;
 }
 

@@ -233,6 +233,27 @@ class Engine:
         rows = _c(rows, np.int64)
         self._chk(self._L.dm_store_release(self._ctx, len(rows), _ptr(rows)))
 
+    def clean(self, now_ns: int, peek: bool = False, want_rows: bool = True) -> dict:
+        """Clean (store.go:169-181) on the device (dm_store_clean): every lease that has lapsed
+        at now_ns (now_ns > expiry) is released as by release().  Returns released (the
+        count), next_expiry_ns (the earliest expiry among the rows still live, DM_NO_EXPIRY
+        when none is) and rows (the released rows, ascending; None when want_rows is false:
+        read_cleaned fetches them later).  peek: the same report, the store unchanged."""
+        res = _lib.CleanResult()
+        self._chk(self._L.dm_store_clean(self._ctx, int(now_ns), _lib.DM_CLEAN_PEEK if peek else 0,
+                                         ctypes.byref(res)))
+        self._cleaned = int(res.released)
+        return {"released": int(res.released), "next_expiry_ns": int(res.next_expiry_ns),
+                "rows": self.read_cleaned(0, int(res.released)) if want_rows else None}
+
+    def read_cleaned(self, off: int = 0, n: int | None = None) -> np.ndarray:
+        """dm_read_cleaned: entries [off, off + n) of the last clean's list of released rows
+        (n None: from off to its end)."""
+        n = getattr(self, "_cleaned", 0) - off if n is None else n
+        rows = np.empty(max(int(n), 0), np.int64)
+        self._chk(self._L.dm_read_cleaned(self._ctx, int(off), int(n), _ptr(rows)))
+        return rows
+
     def read_store(self, off: int = 0, n: int | None = None) -> dict:
         n = self.n_leases - off if n is None else n
         out = {"has": np.empty(n), "wants": np.empty(n), "subclients": np.empty(n, np.int64),

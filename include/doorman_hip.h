@@ -7,6 +7,7 @@
  * Go side):
  *
  *   LeaseStore interface        go/server/doorman/store.go:68-103   -> dm_store_* / dm_read_*
+ *   LeaseStore.Clean            go/server/doorman/store.go:169-181  -> dm_store_clean
  *   a growing client map        go/server/doorman/store.go:153-167  -> dm_store_relayout (a longer segment)
  *   resources made on first use go/server/doorman/resource.go:153-163 -> dm_store_relayout (appended segments)
  *   NewLeaseStore               go/server/doorman/store.go:114      -> dm_create + dm_store_load
@@ -41,7 +42,9 @@ extern "C" {
 #endif
 
 /* 7: dm_store_relayout (the device store re-laid out in place: resources grow, shrink, are
-   compacted or appended without a row crossing PCIe) and dm_server_stats.
+   compacted or appended without a row crossing PCIe) and dm_server_stats; added since,
+   with no change to the existing calls: dm_store_clean / dm_read_cleaned (Clean on the
+   device, reporting the rows it freed).
    6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
    without waiting; its outcome reported by a later call).
    5 (round 6): dm_store_lost (the read calls work on a lost store); dm_plan_info's slot 18 is the class streams' hardware-queue assignment the
@@ -212,6 +215,44 @@ int dm_store_load(dm_ctx* ctx, const dm_snapshot* snap);
 #define DM_RELAYOUT_COMPACT 1u
 int dm_store_relayout(dm_ctx* ctx, int64_t n_resources, const int64_t* new_seg_off, uint32_t flags,
                       int64_t* row_map);
+/* Clean (store.go:169-181) on the device: drops the leases that have lapsed at now_ns and
+   reports how many, which rows, and when Clean next has work.  No row crosses PCIe: the
+   16-B result does, and 8 B per released row when dm_read_cleaned asks for the list.
+     A row lapses when it is not released and now_ns > its resolved expiry -- the one
+       dm_read_store reports: the followers' expiry for a follower row, the expiry column for
+       an explicit one.  The test is the reference's strict After (store.go:174): a row whose
+       expiry equals now_ns stays.
+     Every lapsed row is released as by dm_store_release: its resource's running sums lose
+       the row's has, wants and subclients; the row is zeroed and marked DM_RELEASED; a dense
+       resource of the workgroup bins stays dense (the row goes into its released-row mask),
+       any other dense resource is dense no longer.
+     out (or NULL): released = the rows released (the reference's Clean() summed over the
+       resources); next_expiry_ns = the earliest expiry among the rows live after the call,
+       DM_NO_EXPIRY when none is left -- a server can sleep until then.
+     DM_CLEAN_PEEK: the same result and the same list, and nothing is written to the store:
+       the last tick's leases stay readable (dm_read_leases).  A writeback dm_apportion at
+       the same now_ns then releases exactly the peeked rows in its own Clean, so a host
+       that keeps the client -> row map learns which rows that tick frees.
+   Like dm_store_release the call is synchronous on return and ordered after all earlier
+   work of the context (deferred-join ticks included); unless it is a peek or released
+   nothing, the last tick's leases are gone (dm_read_leases: DM_E_STATE until the next
+   tick).  In-flight dm_store_apply_async batches are retired first, as by dm_config_load:
+   a rejected batch's error is returned and nothing is cleaned.  No configuration is
+   needed: Clean reads none.  DM_E_INVAL: unknown flag bits, a NULL context; DM_E_STATE: no
+   store loaded; DM_E_INTERNAL: a lost store (dm_store_lost), as for the updates. */
+#define DM_NO_EXPIRY INT64_MAX /* next_expiry_ns when no live row is left */
+#define DM_CLEAN_PEEK 1u       /* report only: the store is not changed */
+typedef struct {
+  int64_t released;       /* rows Clean released (the reference's Clean() summed over the resources) */
+  int64_t next_expiry_ns; /* earliest expiry among the rows live after it; DM_NO_EXPIRY if none */
+} dm_clean_result;
+int dm_store_clean(dm_ctx* ctx, int64_t now_ns, uint32_t flags, dm_clean_result* out /* or NULL */);
+/* Entries [off, off + n) of the last dm_store_clean's list (peek or not): the released rows
+   in ascending row order.  DM_E_RANGE outside [0, released].  The list stays on the device
+   (8 B per released row: its buffer is sized from the count, never from n_leases) until the
+   next dm_store_clean, dm_store_load or successful dm_store_relayout on the context; after
+   one of those and before any clean: DM_E_STATE. */
+int dm_read_cleaned(dm_ctx* ctx, int64_t off, int64_t n, int64_t* rows);
 /* Replaces the configuration; the store stays.  In-flight dm_store_apply_async batches
    are retired first, oldest first, every one of them (as dm_store_apply_wait).  If one
    was rejected, its error is returned (DM_E_RANGE / DM_E_INVAL, "an earlier asynchronous
