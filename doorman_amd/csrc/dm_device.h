@@ -46,7 +46,8 @@ constexpr int kBin6Wide = 9;
 // -> 38.1-38.7 us; ProportionalShare 37.7-38.0 -> 39.0: profiles/r05_ab/b4_one_wave.txt).
 constexpr int kBin4Wave = 10;
 // Lease-table footprint (48 B per lease) above which a tick is taken to stream
-// from HBM rather than partly from the 256 MiB Infinity Cache (launch_bin).
+// from HBM rather than partly from the 256 MiB Infinity Cache (dm_apportion: such a
+// store writes the alternate gets column after a call that wrote rows).
 constexpr int64_t kStreamBytes = 1LL << 30;
 
 

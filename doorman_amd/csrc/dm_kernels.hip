@@ -39,7 +39,25 @@ enum { kMixed = 0, kDenseOnly = 1, kRest = 2 };
 template <int G> constexpr bool kGroupNT = G >= 128;
 constexpr bool kSpecNT = true;
 
-template <int G, int R, int MODE = kMixed>
+// One live row's gets in the skipping map of group_segment: the resource's algorithm on
+// the row's wants / has / subclients and the passes' sums, the same decisions as the
+// plain loop's (which keeps its inline form: every build without the skip is then the
+// code it was, register for register).
+__device__ __forceinline__ double row_gets(const Res& rs, bool ps, double C, double eq, const Clean& cl,
+                                           const AggB& b, const FsU& fu, double w, double h, int s) {
+  if (rs.learning) return h;             // Learn (algorithm.go:297-302)
+  if (rs.kind == 0) return w;            // NoAlgorithm
+  if (rs.kind == 1) return minF(C, w);   // Static
+  if (ps) {
+    const double epc = eq * (double)s;         // :233
+    const double unused = C - cl.sum_has + h;  // :239
+    return (cl.sum_wants <= C || w <= epc) ? minF(w, unused)                               // :245
+                                           : minF(epc + (w - epc) * (b.x / b.y), unused);  // :283
+  }
+  return fs_uniform_row(w, h, C, cl.sum_has, fu);
+}
+
+template <int G, int R, int MODE = kMixed, bool SKIP = false>
 __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
                                               Lds<G>& lds, int32_t* general_list, int32_t* general_count,
                                               int32_t* queue = nullptr, int32_t* qcount = nullptr,
@@ -273,11 +291,34 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   }
 
   // ---- map: decide and write every lease (store.go:153-167 Assign) ----
+  // SKIP (k_block_dense's second build, launched for a writeback tick in place: out_gets
+  // is the column h[] was loaded from) leaves out the gets store of a wave's 64-row run
+  // (512 B) when no row of the run changes: on a resource at its fixed point (no wants
+  // change, arrival, departure or capacity change since the last tick) the value is bit
+  // for bit the has just loaded, a third of the tick's bytes.  Bits, not values (-0.0,
+  // NaN payloads); a row Clean releases stores +0.0.  The ballot runs among the run's
+  // valid rows (lanes past n do not vote), so the store's branch is wave-uniform: whole
+  // runs, no partial lines.  The comparison reuses h[k] (live for delta) and leaves a
+  // scalar mask.  Every other store (subclients, wants of released rows, masks, the
+  // resource) stays.  Never on a non-writeback tick or on the alternate column, which
+  // holds the tick before last: those run the build without it, the loop as it always was.
   SumD delta{0.0};
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     if (!(valid >> k & 1)) continue;
     const unsigned u = (unsigned)(k * G + t);
+    if constexpr (SKIP) {
+      const bool lv = live >> k & 1;
+      const double g = lv ? row_gets(rs, ps, C, eq, cl, b, fu, w[k], h[k], s[k]) : 0.0;
+      const bool st = __ballot(__double_as_longlong(g) != __double_as_longlong(h[k])) != 0;
+      if (!lv) {  // released by Clean: no lease
+        put_released<kGroupNT<G>>(p, lo, u, (relm >> k & 1) ? (int)kSubReleased : sr[k], st);
+        continue;
+      }
+      put_live<kGroupNT<G>>(p, lo, u, g, rs, sr[k], st);
+      delta.v += g - h[k];
+      continue;
+    }
     if (!(live >> k & 1)) {  // released by Clean: no lease
       put_released<kGroupNT<G>>(p, lo, u, (relm >> k & 1) ? (int)kSubReleased : sr[k]);
       continue;
@@ -377,7 +418,9 @@ __global__ __launch_bounds__(G, (G <= 256 && R == 8) ? 5 : 1) void k_block(DevPa
 // or the rest kernel) is launched with the tick's stop event when another queue waits
 // for the tick (dm_runtime.cpp tick_ev).
 // (128 x 8 held to 7 waves per SIMD: 71 VGPRs + 20 B of spill, C3 430 -> 590 us; round 5.)
-template <int G, int R>
+// SKIP: the build a writeback tick in place runs (group_segment: unchanged runs of gets
+// are not stored); every other tick runs the build without it.
+template <int G, int R, bool SKIP = false>
 __global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __restrict__ items, int nitems,
                                                    int32_t* queue, int32_t* qcnt, int par,
                                                    int32_t* general_list, int32_t* general_count,
@@ -392,8 +435,8 @@ __global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __rest
         if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     } else {
-      group_segment<G, R, kDenseOnly>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list, general_count,
-                                      queue, qcnt + par, (int32_t)blockIdx.x, guard, nitems);
+      group_segment<G, R, kDenseOnly, SKIP>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
+                                            general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard, nitems);
     }
   }
 }
@@ -3068,33 +3111,26 @@ hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, 
                             int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const dim3 grid((unsigned)n);
+  // in place (the gets go to the column the has came from): the build that skips unchanged runs
+  const bool skip = p.writeback && p.out_gets == p.has;
+#define DM_LAUNCH_DENSE(G, R)                                                                                      \
+  if (skip)                                                                                                        \
+    hipExtLaunchKernelGGL((k_block_dense<G, R, true>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n, queue,  \
+                          qcnt, par, glist, gcount, guard);                                                        \
+  else                                                                                                             \
+    hipExtLaunchKernelGGL((k_block_dense<G, R, false>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n, queue, \
+                          qcnt, par, glist, gcount, guard);                                                        \
+  break
   switch (bin) {
-    case 3:
-      hipExtLaunchKernelGGL(k_block_dense<128, 4>, grid, dim3(128), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard);
-      break;
-    case 4:
-      hipExtLaunchKernelGGL(k_block_dense<128, 8>, grid, dim3(128), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard);
-      break;
-    case kBin4Wave:
-      hipExtLaunchKernelGGL(k_block_dense<64, 16>, grid, dim3(64), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard);
-      break;
-    case 5:
-      hipExtLaunchKernelGGL(k_block_dense<256, 8>, grid, dim3(256), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard);
-      break;
-    case 6:
-      hipExtLaunchKernelGGL(k_block_dense<256, 16>, grid, dim3(256), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard);
-      break;
-    case kBin6Wide:
-      hipExtLaunchKernelGGL(k_block_dense<512, 8>, grid, dim3(512), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard);
-      break;
+    case 3: DM_LAUNCH_DENSE(128, 4);
+    case 4: DM_LAUNCH_DENSE(128, 8);
+    case kBin4Wave: DM_LAUNCH_DENSE(64, 16);
+    case 5: DM_LAUNCH_DENSE(256, 8);
+    case 6: DM_LAUNCH_DENSE(256, 16);
+    case kBin6Wide: DM_LAUNCH_DENSE(512, 8);
     default: return hipErrorInvalidValue;
   }
+#undef DM_LAUNCH_DENSE
   return hipGetLastError();
 }
 

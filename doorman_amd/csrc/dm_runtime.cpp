@@ -292,6 +292,8 @@ struct dm_ctx {
   DBuf<int64_t> out_expiry;
   DBuf<ResAgg> res;
   bool last_writeback = false, have_result = false;
+  int wb_inplace = -1;  // the store's last writeback tick wrote the has column (1) or the alternate one (0)
+  uint64_t wb_epoch = 0;  // row_epoch at the last writeback tick (0: none yet)
   // the workgroup bins' items carry dense hints: set by a writeback tick, kept by the
   // store updates (which keep a dense resource's state or end it: DenseUpd), cleared by
   // a new store
@@ -1514,6 +1516,7 @@ int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
   c->expl_rows = true;
   c->rows_changed();
   c->have_result = false;
+  c->wb_inplace = -1;
   c->hints_set = false;
   if (c->cfg_loaded && (int64_t)c->h_refresh_s.size() != R) c->cfg_loaded = false;
   return DM_OK;
@@ -1779,13 +1782,18 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   p.agg = c->agg.p;
   p.expl = c->expl.p;
   p.rmask = c->rmask.p;
-  // Every tick writes every row's lease (released rows included).  On a store
-  // beyond the Infinity Cache a writeback tick writes its gets/expiry into the
-  // alternate pair of columns and the pairs swap afterwards: separate output
-  // columns stream faster than in-place read-then-write of the same lines (C3,
-  // 100M rows: 815 -> 760 us per tick, tools/ab.py).  A
-  // cache-resident store (C1, 440 MB) keeps in-place writes, which the cache
-  // serves better (72 vs 76 us).
+  // Every tick decides every row's lease (released rows included).  A writeback tick
+  // writes its gets in place, into the has column, where the dense kernels skip the
+  // gets store of every 64-row run the tick leaves unchanged (dm_kernels.hip
+  // group_segment: a third of a quiescent resource's bytes).  It writes the alternate
+  // column, which becomes the store's has after the tick, when the caller asks for it,
+  // when it may take the speculative large chain (below), and on a store beyond the
+  // Infinity Cache whose rows a call has written since the last writeback tick (the row
+  // epoch): such a tick has little to skip, and separate columns stream ~2 % faster than
+  // reading and writing the same lines (C3 without the skip 427 against 435 us, C4's
+  // kernel 616 against 630 us).  A cache-resident store (C1)
+  // always preferred in place.  A store's ticks switch modes freely: after either kind
+  // c->has is complete.
   if ((flags & DM_WB_INPLACE) && (flags & DM_WB_ALTERNATE))
     return c->fail(DM_E_INVAL, "DM_WB_INPLACE and DM_WB_ALTERNATE are exclusive");
   // The speculative large chain (below) writes its gets before they are verified, so a
@@ -1793,8 +1801,13 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   const bool spec_eligible = c->spec_chain && wb && !(flags & DM_AGG_RECOMPUTE) && !c->expl_rows &&
                              !((c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0) &&
                              !c->h_chunks.empty();
+  const bool stream_written = c->N * 48 > kStreamBytes && c->wb_epoch != c->row_epoch;
   const bool pingpong = wb && !(flags & DM_WB_INPLACE) &&
-                        ((flags & DM_WB_ALTERNATE) || c->N * 48 > kStreamBytes || spec_eligible);
+                        ((flags & DM_WB_ALTERNATE) || spec_eligible || stream_written);
+  if (wb) {
+    c->wb_inplace = pingpong ? 0 : 1;  // dm_plan_info slot 19
+    c->wb_epoch = c->row_epoch;
+  }
   // A writeback tick writes no per-lease expiry: the leases it grants follow their
   // resource's expiry (dm_device.h), so only gets (and rare subclients words) move.
   if (!wb) {
@@ -3518,7 +3531,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[10 + kNumBins];
+  int64_t v[11 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -3534,7 +3547,10 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   // the class streams' queue assignment the calibration chose (dm_ctx::calib): perm[0] +
   // 4 perm[1] + 16 perm[2] + 64 perm[3], or -1 before it has finished (or with shared queues)
   v[9 + kNumBins] = c->calib_best;
-  const int n = 10 + kNumBins;
+  // the column the last writeback tick wrote: 1 the has column (in place), 0 the alternate
+  // column, -1 before any writeback tick
+  v[10 + kNumBins] = c->wb_inplace;
+  const int n = 11 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

@@ -44,7 +44,10 @@ extern "C" {
 /* 7: dm_store_relayout (the device store re-laid out in place: resources grow, shrink, are
    compacted or appended without a row crossing PCIe) and dm_server_stats; added since,
    with no change to the existing calls: dm_store_clean / dm_read_cleaned (Clean on the
-   device, reporting the rows it freed).
+   device, reporting the rows it freed); dm_plan_info's slot 19 is the column the store's
+   last writeback tick wrote (1 the has column, in place; 0 the alternate column; -1
+   before any writeback tick), and the call returns 20.  (An added slot, as slot 18 was:
+   the version stays 7, which the clean and re-layout additions pinned.)
    6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
    without waiting; its outcome reported by a later call).
    5 (round 6): dm_store_lost (the read calls work on a lost store); dm_plan_info's slot 18 is the class streams' hardware-queue assignment the
@@ -82,9 +85,12 @@ extern "C" {
                                running sums updated as the Assigns would (store.go:153-167) */
 #define DM_AGG_RECOMPUTE 2u /* ignore the store's running sums; recompute them from the rows */
 #define DM_ASYNC 4u         /* enqueue on the context stream and return without waiting */
-/* Where a writeback tick writes gets/expiry.  Default: in place for a store that
-   fits the Infinity Cache, else into a second pair of has/expiry columns that
-   becomes the store's after the tick (faster streaming; 16 B per lease of HBM). */
+/* Where a writeback tick writes its gets.  Default: in place (the has column; runs of
+   64 rows the tick leaves bit for bit unchanged are then not stored at all).  A tick that
+   may take the speculative large chain (a store with a resource above 4096 rows), and on
+   a store beyond the Infinity Cache the first writeback tick after a call that wrote
+   rows, writes a second has column that becomes the store's after the tick (8 B per
+   lease of HBM).  dm_plan_info slot 19 reports which one the last tick wrote. */
 #define DM_WB_INPLACE 8u    /* force in-place writeback */
 #define DM_WB_ALTERNATE 16u /* force the alternate columns */
 #define DM_DEFER_JOIN 32u   /* with DM_ASYNC: a tick whose work classes run on the context's
@@ -508,7 +514,8 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * streams, unjoined from tick to tick; else 1), and the queue assignment the context chose
  * for its class streams (perm[0] + 4 perm[1] + 16 perm[2] + 64 perm[3]: class stream i
  * runs on the i-th auxiliary queue's perm[i]-th creation; timed on the context's first
- * forked writeback ticks, -1 until then); returns 19 */
+ * forked writeback ticks, -1 until then), and the column the store's last writeback tick
+ * wrote (1: the has column, in place; 0: the alternate column; -1: none yet); returns 20 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
