@@ -8,9 +8,13 @@
 //   FairShare      algorithm.go:95-206    pass B: extra / wantExtra (round 1),
 //                                         pass C: extraExtra / wantExtraExtra at T (round 2), then map
 //   NoAlgorithm / Static / Learn  algorithm.go:66-84,297-302  map only
-// The path is HBM-bound (48 B per lease, ~15 flops): no MFMA.  Rows are read once
-// from HBM into VGPRs and every pass runs from registers; the large-resource path
-// re-reads from L2 / Infinity Cache.
+// No MFMA: the arithmetic is binary64 compares, adds and a few divisions per row, and
+// the segmented reductions.  Rows are read once from HBM into VGPRs and every pass runs
+// from registers; the large-resource path re-reads from L2 / Infinity Cache.  Bytes set
+// the floor (24-48 B per lease), but the dense tick that skips unchanged stores is bound
+// by vector issue, not HBM: ~160 VALU instructions per row slot keep every SIMD's VALU
+// busy for the kernel's whole duration (profiles/steady_pmc.md), hence the steady builds
+// below, which leave out the pass whose result is known.
 //
 // Float semantics follow Go on amd64: binary64, no FMA contraction (built with
 // -ffp-contract=off), minF = `l > r ? r : l`, IEEE division by zero.
@@ -57,7 +61,7 @@ __device__ __forceinline__ double row_gets(const Res& rs, bool ps, double C, dou
   return fs_uniform_row(w, h, C, cl.sum_has, fu);
 }
 
-template <int G, int R, int MODE = kMixed, bool SKIP = false>
+template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false>
 __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
                                               Lds<G>& lds, int32_t* general_list, int32_t* general_count,
                                               int32_t* queue = nullptr, int32_t* qcount = nullptr,
@@ -66,6 +70,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // only the 128-thread mixed kernel and the dense-only kernels load by the hint
   constexpr bool kDense = G >= 128 || (G == 64 && R >= 16);  // (64 x 16: kBin4Wave)
   constexpr bool kHintLoad = (G == 128 && MODE == kMixed) || MODE == kDenseOnly;
+  static_assert(!STEADY || MODE == kDenseOnly, "the steady build is a dense-only build");
   const int seg = wi.seg;
   const int64_t lo = wi.lo;
   const int n = kDense ? wi.n & 0xFFFF : wi.n;
@@ -106,7 +111,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // rows upserted since the dense state was set (dm_device.h mask_pos): the high nibble
   // of the released-row entry for R <= 4, else G entries after the released-row ones
   constexpr unsigned kRowBits = R >= 32 ? ~0u : (1u << R) - 1u;
-  const bool arrivals = kDense && ((hw >> 9) & 1);
+  const bool arrivals = !STEADY && kDense && ((hw >> 9) & 1);
   bool by_hint = MODE == kDenseOnly;  // the rows' states come from the hint and the masks, not the column
   if (MODE != kDenseOnly && !hint) {
 #pragma unroll
@@ -119,7 +124,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
       sr[k] = *col_at(sb, u);
     }
   } else {
-    if (hw >> 8 & 1) relm = (unsigned)mrow[t] & kRowBits;
+    if (!STEADY && (hw >> 8 & 1)) relm = (unsigned)mrow[t] & kRowBits;
     by_hint = true;
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -135,7 +140,14 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // needs their own expiries, from the columns
   const bool arr_lapse = arrivals && p.now > rs.follow_exp;
   if constexpr (MODE == kDenseOnly) {
-    if (dense_subclients(rs) != hint || arr_lapse) {  // stale hint: k_block_rest reads the column
+    // STEADY (k_block_dense's steady builds, launched when the host knows of no released
+    // row, arrival or recompute in the part: dm_runtime.cpp): an item with a released-row
+    // or arrival bit after all, or whose followers have lapsed (lease lengths change on
+    // the device, so only the kernel can tell), goes to k_block_rest like a stale hint.
+    // What is left has a known Clean (below), with no row examined.
+    const bool stale = dense_subclients(rs) != hint;
+    const bool rest = STEADY ? stale || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute : stale || arr_lapse;
+    if (rest) {  // stale hint: k_block_rest reads the column
       if (t == 0) {
         const int q = atomicAdd(qcount, 1);
         if (q < qcap) queue[q] = qidx;  // at most one entry per item and tick (a guarded tick's count may grow)
@@ -157,52 +169,70 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // reads the 8-B expiry column.  The test is the resource's flag, not the rows'
   // subclients words, which would make every wave wait for its loads to decide.
   int64_t e[R];
-#pragma unroll
-  for (int k = 0; k < R; ++k) e[k] = rs.follow_exp;
-  if (MODE != kDenseOnly && (any_explicit(rs) || arr_lapse)) {  // a dense resource: only its lapsing arrivals
+  if constexpr (STEADY) {  // every row a live follower of hint subclients: no expiry, no released row
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-      const int i = k * G + t;
-      const int64_t x = *col_at(eb, (unsigned)(i < n ? i : n - 1));
-      if (sub_explicit(sr[k])) e[k] = x;
+      valid |= ((k * G + t < n) ? 1u : 0u) << k;
+      s[k] = hint;
     }
-  }
+    live = valid;
+  } else {
 #pragma unroll
-  for (int k = 0; k < R; ++k) {  // rows past the end stay out of valid/live, so every pass skips them
-    const unsigned vk = (k * G + t < n) ? 1u : 0u;
-    valid |= vk << k;
-    if (sub_released(sr[k])) e[k] = kReleased;
-    live |= (vk & (p.now > e[k] ? 0u : 1u)) << k;  // store.go:174 when.After(expiry)
-    relb |= (sub_released(sr[k]) ? 1u : 0u) << k;
-    s[k] = sub_value(sr[k]);
+    for (int k = 0; k < R; ++k) e[k] = rs.follow_exp;
+    if (MODE != kDenseOnly && (any_explicit(rs) || arr_lapse)) {  // a dense resource: only its lapsing arrivals
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = k * G + t;
+        const int64_t x = *col_at(eb, (unsigned)(i < n ? i : n - 1));
+        if (sub_explicit(sr[k])) e[k] = x;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {  // rows past the end stay out of valid/live, so every pass skips them
+      const unsigned vk = (k * G + t < n) ? 1u : 0u;
+      valid |= vk << k;
+      if (sub_released(sr[k])) e[k] = kReleased;
+      live |= (vk & (p.now > e[k] ? 0u : 1u)) << k;  // store.go:174 when.After(expiry)
+      relb |= (sub_released(sr[k]) ? 1u : 0u) << k;
+      s[k] = sub_value(sr[k]);
+    }
+    live &= ~relm;
   }
-  live &= ~relm;
 
   // ---- pass A: Clean ----
+  // STEADY: Clean releases nothing (exact zeros: nothing is ever added) and every row is
+  // live with hint subclients, so the loop, its reduction and its barrier are left out.
+  // Only "any NaN wants" depends on the rows: FairShare (the one user) counts them with
+  // pass B's reduction, in bits 48 and up of AggB::i (the sum itself stays below 2^43).
   AggA a = zeroA();
+  if constexpr (STEADY) {
+    a.smin = a.smax = hint;
+    a.nlive = n;
+  } else {
 #pragma unroll
-  for (int k = 0; k < R; ++k) {
-    if (!(valid >> k & 1)) continue;
-    const bool lv = live >> k & 1;
-    const int sk = (relm >> k & 1) ? 0 : s[k];  // a released row counts nothing (its wants and has are 0)
-    if (!lv) {
-      a.cnt += sk;
-      a.h += h[k];
-      a.w += w[k];
-    }
-    if (p.recompute) {
-      a.all.cnt += sk;
-      a.all.h += h[k];
-      a.all.w += w[k];
-    }
-    if (lv) {
-      a.smin = s[k] < a.smin ? s[k] : a.smin;
-      a.smax = s[k] > a.smax ? s[k] : a.smax;
-      a.nan |= __builtin_isnan(w[k]) ? 1 : 0;
-      a.nlive += 1;
+    for (int k = 0; k < R; ++k) {
+      if (!(valid >> k & 1)) continue;
+      const bool lv = live >> k & 1;
+      const int sk = (relm >> k & 1) ? 0 : s[k];  // a released row counts nothing (its wants and has are 0)
+      if (!lv) {
+        a.cnt += sk;
+        a.h += h[k];
+        a.w += w[k];
+      }
+      if (p.recompute) {
+        a.all.cnt += sk;
+        a.all.h += h[k];
+        a.all.w += w[k];
+      }
+      if (lv) {
+        a.smin = s[k] < a.smin ? s[k] : a.smin;
+        a.smax = s[k] > a.smax ? s[k] : a.smax;
+        a.nan |= __builtin_isnan(w[k]) ? 1 : 0;
+        a.nlive += 1;
+      }
     }
   }
-  {
+  if constexpr (!STEADY) {
     const AggR all_part = a.all;
     bool fast_a = false;
     if constexpr (G <= 64) {
@@ -230,13 +260,15 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
     if (!fast_a) a = group_reduce<G, AggA, OpA, false>(a, OpA(), lds.a);
     if (p.recompute) a.all = group_reduce<G, AggR, OpR, false>(all_part, OpR(), lds.r);
   }
-  const Clean cl = clean_from(p, rs, a);
+  // (STEADY: the running sums as they are; never in recompute mode)
+  const Clean cl = STEADY ? Clean{rs.agg_count, rs.agg_has, rs.agg_wants} : clean_from(p, rs, a);
   const double C = rs.C;
   const double eq = C / (double)cl.count;  // algorithm.go:123,229 equalShare
   const bool ps = !rs.learning && rs.kind == 2;
   const bool fs = !rs.learning && rs.kind == 3;
   const bool fs_uniform = fs && a.smin >= a.smax && !a.nan;  // no live rows counts as uniform
-  if (fs && !fs_uniform) {
+  constexpr long long kNanOne = 1ll << 48;  // STEADY: a NaN wants in AggB::i
+  if (!STEADY && fs && !fs_uniform) {
     // heterogeneous subclients (GetServerCapacity, server.go:850-879) or NaN wants:
     // one round-2 threshold per distinct subclient count.  Rare (the hierarchy's
     // root level), so the whole resource goes to k_general, untouched here.
@@ -265,9 +297,19 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
           b.x += d - w[k];  // :164
         else if (w[k] > d)
           b.i += s[k];  // :168
+        if constexpr (STEADY) b.i += __builtin_isnan(w[k]) ? kNanOne : 0;  // (adds to neither sum above)
       }
     }
     b = group_reduce<G, AggB, OpB, false>(b, OpB(), lds.b);
+    if constexpr (STEADY) {
+      if (b.i >= kNanOne) {  // FairShare with a NaN wants: k_general, as above (nothing is stored yet)
+        if (t == 0) {
+          general_list[atomicAdd(general_count, 1)] = seg;
+          if (p.writeback && (wi.n >> 16)) item->n = n;
+        }
+        return;
+      }
+    }
   }
 
   // ---- pass C (uniform subclients): FairShare round 2 at the resource's one threshold ----
@@ -369,6 +411,10 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
                  : (a.smin == a.smax && a.smin >= 1 && a.smin <= 254) ? a.smin : 0;
   const int hw_next = dn ? (dn | (nlive < n ? 1 << 8 : 0)) : 0;
   delta = group_reduce<G, SumD, OpSumD, false>(delta, OpSumD(), lds.d);
+  if constexpr (STEADY) {  // the state stays as it is: dn == hint, hw_next == hw, no mask to write
+    if (t == 0) write_resource(p, seg, rs, cl, delta.v, hint);
+    return;
+  }
   // A dense tick changes the mask only by a lapse; a writeback tick that changes the
   // state word writes it whole (a later release ORs its row in, so it must be valid
   // whenever the hint is set) and clears the arrivals it turned into followers.
@@ -402,9 +448,9 @@ __global__ __launch_bounds__(G, (G <= 256 && R == 8) ? 5 : 1) void k_block(DevPa
 
 // The workgroup bins split by the dense hint (launch_bin_dense / launch_bin_rest):
 // k_block_dense decides the items whose hint is set without the subclients column
-// (128 x 8: 70 VGPRs, 7 waves per SIMD instead of 5, 14336 rows in flight per CU)
-// and queues the others; k_block_rest decides the queue with the mixed body, a grid
-// striding over it (sized from the last split tick's queue; an empty queue costs
+// (128 x 8: 73 VGPRs, 6 waves per SIMD instead of 5; its steady builds 66 and 7: 14336
+// rows in flight per CU) and queues the others; k_block_rest decides the queue with the
+// mixed body, a grid striding over it (sized from the last split tick's queue; an empty queue costs
 // one small launch).  qcnt is a two-slot ring: this tick's count in qcnt[par], and
 // k_block_rest clears qcnt[par ^ 1] for the next tick (stream order); host_count
 // (host-mapped) tells the host how many items went to the queue (its choice of
@@ -420,7 +466,11 @@ __global__ __launch_bounds__(G, (G <= 256 && R == 8) ? 5 : 1) void k_block(DevPa
 // (128 x 8 held to 7 waves per SIMD: 71 VGPRs + 20 B of spill, C3 430 -> 590 us; round 5.)
 // SKIP: the build a writeback tick in place runs (group_segment: unchanged runs of gets
 // are not stored); every other tick runs the build without it.
-template <int G, int R, bool SKIP = false>
+// STEADY: the builds for a part the host knows to hold only dense items without released
+// rows or arrivals, outside recompute mode (group_segment: Clean's result is known; an item
+// it is not known for is queued, so the rest kernel follows every steady launch).  As a
+// run-time branch in one build the two bodies need 84-87 VGPRs (5 waves per SIMD).
+template <int G, int R, bool SKIP = false, bool STEADY = false>
 __global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __restrict__ items, int nitems,
                                                    int32_t* queue, int32_t* qcnt, int par,
                                                    int32_t* general_list, int32_t* general_count,
@@ -435,8 +485,9 @@ __global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __rest
         if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     } else {
-      group_segment<G, R, kDenseOnly, SKIP>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
-                                            general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard, nitems);
+      group_segment<G, R, kDenseOnly, SKIP, STEADY>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
+                                                    general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
+                                                    nitems);
     }
   }
 }
@@ -464,19 +515,32 @@ __global__ __launch_bounds__(G) void k_block_rest(DevParams p, WorkItem* __restr
 // One workgroup: how many items of a workgroup bin are not dense after a writeback
 // tick, published to host-mapped memory as {count, epoch} (count first, the epoch
 // with release order) -- the host's once-per-epoch check before it skips the bin's
-// k_block_rest (dm_runtime.cpp).
+// k_block_rest (dm_runtime.cpp).  The count word's high half counts the dense items
+// whose hint word carries released rows or arrivals (bits 8, 9): with both halves zero
+// the host may launch the steady builds.
 __global__ __launch_bounds__(1024) void k_count_undense(const WorkItem* __restrict__ items, int n,
                                                         unsigned long long* rec, unsigned long long epoch) {
-  __shared__ int part[16];
-  int c = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) c += (items[i].n >> 16) == 0 ? 1 : 0;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __shared__ int part[16], part_f[16];
+  int c = 0, f = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int hw = items[i].n >> 16;
+    c += hw == 0 ? 1 : 0;
+    f += (hw >> 8 & 3) != 0 ? 1 : 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_down(c, o, 64);
+    f += __shfl_down(f, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6] = c;
+    part_f[threadIdx.x >> 6] = f;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += part[w];
-    __hip_atomic_store(rec, (unsigned long long)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    unsigned long long tot = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w)
+      tot += (unsigned long long)(unsigned)part[w] | (unsigned long long)(unsigned)part_f[w] << 32;
+    __hip_atomic_store(rec, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(rec + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -3107,19 +3171,27 @@ hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, in
 // timed separately).
 // done (optional): an event the launch itself completes (hipExtLaunchKernel's stop
 // event: no marker packet of its own on the queue), for another stream to wait on
+// steady: the builds that take Clean's result as known and queue every item it is not
+// known for (group_segment STEADY); the caller launches the rest kernel after them.
 hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, hipStream_t st) {
+                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
+                            hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const dim3 grid((unsigned)n);
   // in place (the gets go to the column the has came from): the build that skips unchanged runs
   const bool skip = p.writeback && p.out_gets == p.has;
-#define DM_LAUNCH_DENSE(G, R)                                                                                      \
-  if (skip)                                                                                                        \
-    hipExtLaunchKernelGGL((k_block_dense<G, R, true>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n, queue,  \
-                          qcnt, par, glist, gcount, guard);                                                        \
-  else                                                                                                             \
-    hipExtLaunchKernelGGL((k_block_dense<G, R, false>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n, queue, \
-                          qcnt, par, glist, gcount, guard);                                                        \
+#define DM_LAUNCH_DENSE_AS(G, R, SKIP, STEADY)                                                                    \
+  hipExtLaunchKernelGGL((k_block_dense<G, R, SKIP, STEADY>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n,  \
+                        queue, qcnt, par, glist, gcount, guard)
+#define DM_LAUNCH_DENSE(G, R)                         \
+  if (steady && skip)                                 \
+    DM_LAUNCH_DENSE_AS(G, R, true, true);             \
+  else if (steady)                                    \
+    DM_LAUNCH_DENSE_AS(G, R, false, true);            \
+  else if (skip)                                      \
+    DM_LAUNCH_DENSE_AS(G, R, true, false);            \
+  else                                                \
+    DM_LAUNCH_DENSE_AS(G, R, false, false);           \
   break
   switch (bin) {
     case 3: DM_LAUNCH_DENSE(128, 4);
@@ -3131,6 +3203,7 @@ hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, 
     default: return hipErrorInvalidValue;
   }
 #undef DM_LAUNCH_DENSE
+#undef DM_LAUNCH_DENSE_AS
   return hipGetLastError();
 }
 

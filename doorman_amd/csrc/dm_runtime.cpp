@@ -27,7 +27,8 @@ hipError_t launch_bin(int bin, const DevParams& p, WorkItem* segs, int n, int32_
                       hipStream_t st);
 hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, int32_t* gcount, hipStream_t st);
 hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, hipStream_t st);
+                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
+                            hipStream_t st);
 int redo_blocks_per_cu();
 hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls,
                              const Partials& P, const SpecArgs& S, int redo_grid, int32_t* glist, int32_t* gcount,
@@ -374,6 +375,13 @@ struct dm_ctx {
   // thousands of items).  DM_DENSE_SPLIT=0: never split.
   int dense_split = 0xF;  // bit i: bin 3+i runs in the split form (DM_DENSE_SPLIT: 0 off, 1 all, else the mask)
   static constexpr int kSplitBins = 4;  // bins 3..6
+  // A split part whose items are all verified dense, none with released rows or arrivals
+  // (k_count_undense's two counts), runs the steady builds of k_block_dense outside
+  // recompute mode: Clean's result is known, so its pass is left out (dm_kernels.hip
+  // group_segment STEADY).  DM_STEADY=0: never; 2 (A/B only): the steady ticks' launches,
+  // dense then rest, with the plain builds: what the trailing rest launch costs.
+  int steady_ok = 1;
+  unsigned steady_mask = 0;  // bit i: split slot i's last tick ran a steady build (dm_plan_info slot 20)
   // Stream parts: a workgroup bin that is the store's only work class, and small enough
   // that a launch's ramp and drain are a visible share of it, runs as kParts launches
   // over contiguous halves of its items on two auxiliary streams, never joined from
@@ -1299,6 +1307,7 @@ int dm_create(int device, dm_ctx** out) {
     const int v = (int)strtol(ds, nullptr, 0);
     c->dense_split = v == 1 ? 0xF : (v & 0xF);
   }
+  if (const char* sd = getenv("DM_STEADY")) c->steady_ok = atoi(sd);
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
   // hardware queue.  Plain streams share the process's GPU_MAX_HW_QUEUES (4) queues
@@ -1978,6 +1987,7 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
       DM_HIP(c, timed(KC_SUBS, s, [&] { return launch_subs(p, sb, gl, gc, s); }), "sub-wave kernel");
     }
   }
+  c->steady_mask = 0;
   for (int b = kNumBins - 1; b >= 0; --b) {
     if (c->h_bins[b].empty()) continue;
     if (b == 7 || b == 8 || b <= 2) continue;  // k_subs
@@ -2021,11 +2031,23 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
           // Every item verified dense in this row epoch: nothing can be queued, so the
           // dense kernel is the part's only launch (the guard catches the impossible).
           const uint64_t* rec = c->h_rec + 2 * i;
-          const bool skip = __atomic_load_n(rec + 1, __ATOMIC_ACQUIRE) == c->row_epoch &&
-                            __atomic_load_n(rec, __ATOMIC_RELAXED) == 0;
+          const bool verified = __atomic_load_n(rec + 1, __ATOMIC_ACQUIRE) == c->row_epoch;
+          const uint64_t counts = __atomic_load_n(rec, __ATOMIC_RELAXED);  // low half: items not dense
+          // The steady builds: every item verified dense and none with released rows or
+          // arrivals (the counts' high half), no recompute.  What the host cannot rule out
+          // is a lapse of the followers (lease lengths change on the device), so the steady
+          // kernel queues such an item and the rest kernel always follows it, with the
+          // tick's event; the guard is for launches that queue nothing.
+          // Not for a bin in stream parts: its ticks are short enough for the rest launch to
+          // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
+          // profiles/steady_ab.md).
+          const bool steady_form = c->steady_ok && nparts == 1 && verified && counts == 0 && !p.recompute;
+          const bool steady = steady_form && c->steady_ok != 2;
+          const bool skip = !steady_form && verified && (uint32_t)counts == 0;
+          if (steady) c->steady_mask |= 1u << i;
           DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
                    return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
-                                           skip ? c->d_guard + i : nullptr, skip ? done : nullptr, s);
+                                           skip ? c->d_guard + i : nullptr, skip ? done : nullptr, steady, s);
                  }),
                  "group kernel (dense split)");
           if (!skip) {
@@ -3531,7 +3553,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[11 + kNumBins];
+  int64_t v[12 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -3550,7 +3572,8 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   // the column the last writeback tick wrote: 1 the has column (in place), 0 the alternate
   // column, -1 before any writeback tick
   v[10 + kNumBins] = c->wb_inplace;
-  const int n = 11 + kNumBins;
+  v[11 + kNumBins] = __builtin_popcount(c->steady_mask);  // bin parts whose last tick ran a steady build
+  const int n = 12 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

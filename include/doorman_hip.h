@@ -46,8 +46,11 @@ extern "C" {
    with no change to the existing calls: dm_store_clean / dm_read_cleaned (Clean on the
    device, reporting the rows it freed); dm_plan_info's slot 19 is the column the store's
    last writeback tick wrote (1 the has column, in place; 0 the alternate column; -1
-   before any writeback tick), and the call returns 20.  (An added slot, as slot 18 was:
-   the version stays 7, which the clean and re-layout additions pinned.)
+   before any writeback tick); slot 20 is the number of workgroup-bin parts whose last
+   tick ran the steady builds of the dense kernel (every item dense with no released row
+   or arrival: Clean's pass is left out; DM_STEADY=0 in the environment, read when the
+   context is created, keeps them off), and the call returns 21.  (Added slots, as slot
+   18 was: the version stays 7, which the clean and re-layout additions pinned.)
    6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
    without waiting; its outcome reported by a later call).
    5 (round 6): dm_store_lost (the read calls work on a lost store); dm_plan_info's slot 18 is the class streams' hardware-queue assignment the
@@ -515,7 +518,8 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * for its class streams (perm[0] + 4 perm[1] + 16 perm[2] + 64 perm[3]: class stream i
  * runs on the i-th auxiliary queue's perm[i]-th creation; timed on the context's first
  * forked writeback ticks, -1 until then), and the column the store's last writeback tick
- * wrote (1: the has column, in place; 0: the alternate column; -1: none yet); returns 20 */
+ * wrote (1: the has column, in place; 0: the alternate column; -1: none yet), and the
+ * workgroup-bin parts whose last tick ran the dense kernel's steady builds; returns 21 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
