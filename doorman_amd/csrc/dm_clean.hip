@@ -16,11 +16,10 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_kernel_util.h"
+#include "dm_launch.h"
 #include "dm_update_util.h"
 
 namespace dm {
-
-hipError_t launch_rl_scan(int64_t* v, int64_t n, hipStream_t st);  // dm_relayout.hip
 
 namespace {
 

@@ -35,6 +35,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "dm_kernel_util.h"
+#include "dm_launch.h"
 
 namespace dm {
 

@@ -1,4 +1,4 @@
-// dm_kernel_util.h — device helpers shared by the gfx950 kernels (dm_kernels.hip,
+// dm_kernel_util.h — device helpers shared by the gfx950 kernels (the dm_tick_*.hip units,
 // dm_round.hip): Go float semantics, DPP/readlane wave reductions, the
 // per-resource aggregates and the FairShare per-row stages.
 #pragma once

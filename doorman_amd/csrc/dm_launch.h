@@ -1,0 +1,79 @@
+// dm_launch.h — the host-side launchers the kernel units define and dm_runtime.cpp calls.
+// Every unit that defines one includes this header, so a definition that drifts from its
+// declaration fails to compile instead of failing to link.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dm_device.h"
+
+namespace dm {
+// dm_tick_group.hip
+hipError_t launch_tile_small(const DevParams& p, const Tile* tiles, const TileEntry* list, int n, hipStream_t st);
+hipError_t launch_bin(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* glist, int32_t* gcount,
+                      hipStream_t st);
+hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, int32_t* gcount, hipStream_t st);
+hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
+                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
+                            hipStream_t st);
+hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,
+                                hipStream_t st);
+hipError_t launch_bin_rest(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
+                           int32_t* host_count, int rest_grid, int32_t* glist, int32_t* gcount, hipEvent_t done,
+                           hipStream_t st);
+// dm_tick_large.hip
+int redo_blocks_per_cu();
+hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls,
+                             const Partials& P, const SpecArgs& S, int redo_grid, int32_t* glist, int32_t* gcount,
+                             hipStream_t st);
+hipError_t launch_large(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls, int nls,
+                        const Partials& P, int32_t* glist, int32_t* gcount, hipStream_t st);
+// dm_tick_general.hip
+hipError_t launch_general(const DevParams& p, const int32_t* glist, const int32_t* gcount, int blocks,
+                          hipStream_t st);
+// dm_update.hip
+hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
+                         const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
+                         const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
+                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st);
+hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
+                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du,
+                          hipStream_t st);
+hipError_t launch_check_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, const double* wants,
+                             const int64_t* sub, const int32_t* sub32, uint32_t* flags, hipStream_t st);
+hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, hipStream_t st);
+hipError_t launch_resolve_rows(int64_t n, const int64_t* rows, int64_t off, const int32_t* sub, const int64_t* expiry,
+                               const RowIndex& ix, const ResAgg* agg, int64_t* out_exp, int64_t* out_sub,
+                               hipStream_t st);
+hipError_t launch_gather_leases(int64_t n, const int64_t* rows, const double* gets, const int64_t* expiry,
+                               double* out_gets, int64_t* out_exp, hipStream_t st);
+hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
+                               const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
+                               hipStream_t st);
+hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
+                                    int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
+                                    const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
+                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi);
+hipError_t launch_carry_reject(const uint32_t* from, uint32_t* to, hipStream_t st);
+// dm_hier.hip
+hipError_t launch_publish(int64_t R, const ResAgg* agg, void* dst, uint32_t* sync, hipStream_t st);
+hipError_t launch_hier_tick(const DevParams& p, const HierArgs& ha, hipStream_t st);
+// dm_round.hip
+hipError_t launch_decide(const DevParams& p, const ReqItem* items, int nitems, const ReqArgs& q, hipStream_t st);
+// dm_decide_fast.hip
+hipError_t fd_rows(const DevParams& p, const ReqItem& it, const FastItem& fi, int slot, const ReqArgs& q,
+                   const FastArgs& fa, hipStream_t st);
+hipError_t fd_item(const DevParams& p, const ReqItem& it, const FastItem& fi, int slot, const ReqArgs& q,
+                   const FastArgs& fa, FdScan* part, hipStream_t st);
+hipError_t fd_item_sorted(const DevParams& p, const ReqItem& it, const FastItem& fi, int slot, const ReqArgs& q,
+                          const FastArgs& fa, FdScan* part, hipStream_t st);
+hipError_t fd_sort_keys(void* temp, size_t* bytes, const double* in, double* out, int64_t n, hipStream_t st);
+hipError_t fd_sort_pairs(void* temp, size_t* bytes, const double* kin, double* kout, const int32_t* vin,
+                         int32_t* vout, int64_t n, int nseg, const int64_t* begin, const int64_t* end,
+                         hipStream_t st);
+// dm_relayout.hip (launch_rl_scan: the in-place scan dm_clean.hip shares)
+hipError_t launch_rl_scan(int64_t* v, int64_t n, hipStream_t st);
+hipError_t launch_relayout(const RelayoutArgs& a, int32_t* nblk, ResAgg* n_agg, bool compact, hipStream_t st);
+// dm_clean.hip
+hipError_t launch_clean_count(const CleanArgs& a, hipStream_t st);
+hipError_t launch_clean_apply(const CleanArgs& a, const DenseUpd& du, bool peek, hipStream_t st);
+}  // namespace dm

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_kernel_util.h"
+#include "dm_launch.h"
 #include "dm_update_util.h"
 
 namespace dm {

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_kernel_util.h"
+#include "dm_launch.h"
 
 namespace dm {
 

@@ -20,68 +20,8 @@
 
 #include "../../include/doorman_hip.h"
 #include "dm_device.h"
+#include "dm_launch.h"
 
-namespace dm {
-hipError_t launch_tile_small(const DevParams& p, const Tile* tiles, const TileEntry* list, int n, hipStream_t st);
-hipError_t launch_bin(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* glist, int32_t* gcount,
-                      hipStream_t st);
-hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, int32_t* gcount, hipStream_t st);
-hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
-                            hipStream_t st);
-int redo_blocks_per_cu();
-hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls,
-                             const Partials& P, const SpecArgs& S, int redo_grid, int32_t* glist, int32_t* gcount,
-                             hipStream_t st);
-hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,
-                                hipStream_t st);
-hipError_t launch_bin_rest(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                           int32_t* host_count, int rest_grid, int32_t* glist, int32_t* gcount, hipEvent_t done,
-                           hipStream_t st);
-hipError_t launch_large(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls, int nls,
-                        const Partials& P, int32_t* glist, int32_t* gcount, hipStream_t st);
-hipError_t launch_general(const DevParams& p, const int32_t* glist, const int32_t* gcount, int blocks,
-                          hipStream_t st);
-hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
-                         const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
-                         const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
-                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st);
-hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
-                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du,
-                          hipStream_t st);
-hipError_t launch_check_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, const double* wants,
-                             const int64_t* sub, const int32_t* sub32, uint32_t* flags, hipStream_t st);
-hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, hipStream_t st);
-hipError_t launch_resolve_rows(int64_t n, const int64_t* rows, int64_t off, const int32_t* sub, const int64_t* expiry,
-                               const RowIndex& ix, const ResAgg* agg, int64_t* out_exp, int64_t* out_sub,
-                               hipStream_t st);
-hipError_t launch_gather_leases(int64_t n, const int64_t* rows, const double* gets, const int64_t* expiry,
-                               double* out_gets, int64_t* out_exp, hipStream_t st);
-hipError_t launch_publish(int64_t R, const ResAgg* agg, void* dst, uint32_t* sync, hipStream_t st);
-hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
-                               const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
-                               hipStream_t st);
-hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
-                                    int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
-                                    const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
-                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi);
-hipError_t launch_carry_reject(const uint32_t* from, uint32_t* to, hipStream_t st);
-hipError_t launch_decide(const DevParams& p, const ReqItem* items, int nitems, const ReqArgs& q, hipStream_t st);
-hipError_t fd_rows(const DevParams& p, const ReqItem& it, const FastItem& fi, int slot, const ReqArgs& q,
-                   const FastArgs& fa, hipStream_t st);
-hipError_t fd_item(const DevParams& p, const ReqItem& it, const FastItem& fi, int slot, const ReqArgs& q,
-                   const FastArgs& fa, FdScan* part, hipStream_t st);
-hipError_t fd_item_sorted(const DevParams& p, const ReqItem& it, const FastItem& fi, int slot, const ReqArgs& q,
-                          const FastArgs& fa, FdScan* part, hipStream_t st);
-hipError_t fd_sort_keys(void* temp, size_t* bytes, const double* in, double* out, int64_t n, hipStream_t st);
-hipError_t fd_sort_pairs(void* temp, size_t* bytes, const double* kin, double* kout, const int32_t* vin,
-                         int32_t* vout, int64_t n, int nseg, const int64_t* begin, const int64_t* end,
-                         hipStream_t st);
-hipError_t launch_hier_tick(const DevParams& p, const HierArgs& ha, hipStream_t st);
-hipError_t launch_relayout(const RelayoutArgs& a, int32_t* nblk, ResAgg* n_agg, bool compact, hipStream_t st);
-hipError_t launch_clean_count(const CleanArgs& a, hipStream_t st);
-hipError_t launch_clean_apply(const CleanArgs& a, const DenseUpd& du, bool peek, hipStream_t st);
-}  // namespace dm
 
 using namespace dm;
 
@@ -262,7 +202,7 @@ struct dm_ctx {
   bool chain_live_ok = false;
   // Row epoch: bumped by every call that writes rows (loads, plans, upserts, releases,
   // wants refreshes, decide, the root's tick) -- never by a tick.  Within one epoch a
-  // writeback tick leaves every dense workgroup-bin resource dense (dm_kernels.hip),
+  // writeback tick leaves every dense workgroup-bin resource dense (dm_tick_group.hip),
   // so a bin verified all-dense once in the epoch (k_count_undense) can skip its
   // k_block_rest: nothing can be queued.
   uint64_t row_epoch = 1;
@@ -377,7 +317,7 @@ struct dm_ctx {
   static constexpr int kSplitBins = 4;  // bins 3..6
   // A split part whose items are all verified dense, none with released rows or arrivals
   // (k_count_undense's two counts), runs the steady builds of k_block_dense outside
-  // recompute mode: Clean's result is known, so its pass is left out (dm_kernels.hip
+  // recompute mode: Clean's result is known, so its pass is left out (dm_tick_group.hip
   // group_segment STEADY).  DM_STEADY=0: never; 2 (A/B only): the steady ticks' launches,
   // dense then rest, with the plain builds: what the trailing rest launch costs.
   int steady_ok = 1;
@@ -437,7 +377,7 @@ struct dm_ctx {
   uint64_t spec_seq = 0;
   int32_t* h_serr = nullptr;  // [0] the give-up flag, [1] SpecArgs::seen
   int32_t* d_serr = nullptr;
-  // k_large_redo's light build (dm_kernels.hip) while the last redo the host saw found
+  // k_large_redo's light build (dm_tick_large.hip) while the last redo the host saw found
   // nothing marked and no row changed since (DM_REDO_LIGHT: 0 never, 1 so, 2 always)
   int redo_light = 1;
   uint64_t redo_epoch = 0;  // row_epoch at the last speculative tick
@@ -1772,16 +1712,41 @@ static hipError_t calib_step(dm_ctx* c) {
   return calib_apply(c, best);
 }
 
-int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
-  DM_CHECK_CTX(c);
-  int rc = ready(c);
-  if (rc) return rc;
-  if (c->tpl_pipe && (rc = commit_templates(c))) return rc;
-  c->ticks_issued += 1;
-  c->tick_seq += 1;
-  c->tick_flagged = false;
-  const bool wb = flags & DM_WRITEBACK;
+extern "C++" {  // (a member template, inside this file's extern "C" block)
+namespace {
+// One dm_apportion call: what its steps share, and the steps in the order they run.  Each
+// step returns DM_OK or the failure dm_apportion returns (DM_HIP returns from the step).
+struct Tick {
+  dm_ctx* c;
+  int64_t now_ns;
+  uint32_t flags;
+  bool wb = false, pingpong = false;
   DevParams p{};
+  Partials P{};
+  hipStream_t st = nullptr, s_large = nullptr, s_small = nullptr;
+  int nch = 0;
+  int32_t *gl = nullptr, *gc = nullptr;  // k_general's worklist and its count
+  bool general = false, fork = false, one_class = false;
+  bool live_ok = false;
+  bool chain_live = false;  // this tick ran the (non-heterogeneous) chain
+
+  template <typename F>
+  hipError_t timed(int cls, hipStream_t s, F&& fn) {
+    return c->timed(cls, s, fn);
+  }
+  hipStream_t cls_stream(int cls) const { return fork ? c->aux[c->class_stream[cls]] : st; }
+
+  int outputs();      // the output columns and DevParams
+  int streams();      // the worklist, the streams in use and the fork
+  int large_chain();  // the large-resource chain
+  int subs();         // the sub-wave launch
+  int bins();         // the workgroup bins ...
+  int bin_part(int b, int lb, int nparts, bool split_dense, int j);  // ... and one stream part of one
+  int finish();       // the join, the general kernel and the state updates
+};
+
+int Tick::outputs() {
+  wb = flags & DM_WRITEBACK;
   p.seg_off = c->seg_off.p;
   p.wants = c->wants.p;
   p.has = c->has.p;
@@ -1793,7 +1758,7 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   p.rmask = c->rmask.p;
   // Every tick decides every row's lease (released rows included).  A writeback tick
   // writes its gets in place, into the has column, where the dense kernels skip the
-  // gets store of every 64-row run the tick leaves unchanged (dm_kernels.hip
+  // gets store of every 64-row run the tick leaves unchanged (dm_tick_group.hip
   // group_segment: a third of a quiescent resource's bytes).  It writes the alternate
   // column, which becomes the store's has after the tick, when the caller asks for it,
   // when it may take the speculative large chain (below), and on a store beyond the
@@ -1811,8 +1776,8 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
                              !((c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0) &&
                              !c->h_chunks.empty();
   const bool stream_written = c->N * 48 > kStreamBytes && c->wb_epoch != c->row_epoch;
-  const bool pingpong = wb && !(flags & DM_WB_INPLACE) &&
-                        ((flags & DM_WB_ALTERNATE) || spec_eligible || stream_written);
+  pingpong = wb && !(flags & DM_WB_INPLACE) &&
+             ((flags & DM_WB_ALTERNATE) || spec_eligible || stream_written);
   if (wb) {
     c->wb_inplace = pingpong ? 0 : 1;  // dm_plan_info slot 19
     c->wb_epoch = c->row_epoch;
@@ -1845,9 +1810,8 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   }
   p.now = now_ns;
   p.recompute = (flags & DM_AGG_RECOMPUTE) ? 1 : 0;
-  const bool live_ok = c->chain_live_ok;
+  live_ok = c->chain_live_ok;
   c->chain_live_ok = false;
-  bool chain_live = false;  // this tick ran the (non-heterogeneous) chain
   if (wb && !c->pub_ring.empty()) {
     const int64_t n = (int64_t)c->pub_ring.size();
     p.pub = c->pub_ring[(size_t)(c->pub_k % n)];
@@ -1856,19 +1820,21 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
     p.pub_first = 0;
     c->pub_k += 1;
   }
+  return DM_OK;
+}
 
-  Partials P{c->pa_cnt.p, c->pa_has.p, c->pa_wants.p, c->pa_cnt_all.p, c->pa_has_all.p, c->pa_wants_all.p,
-             c->pa_smin.p, c->pa_smax.p, c->pa_nan.p,
-             c->pb_x.p,   c->pb_y.p,   c->pb_w.p,     c->pc_ee.p,   c->pc_sgt.p,  c->pd_delta.p,
-             c->pa_live.p, c->p_tot.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipStream_t st = c->stream;
-  auto timed = [&](int cls, hipStream_t s, auto&& fn) -> hipError_t { return c->timed(cls, s, fn); };
-  const int nch = (int)c->h_chunks.size();
-  int32_t* gl = c->glist.p;
-  int32_t* gc = c->gcount.p;
+int Tick::streams() {
+  P = Partials{c->pa_cnt.p, c->pa_has.p, c->pa_wants.p, c->pa_cnt_all.p, c->pa_has_all.p, c->pa_wants_all.p,
+               c->pa_smin.p, c->pa_smax.p, c->pa_nan.p,
+               c->pb_x.p,   c->pb_y.p,   c->pb_w.p,     c->pc_ee.p,   c->pc_sgt.p,  c->pd_delta.p,
+               c->pa_live.p, c->p_tot.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  st = c->stream;
+  nch = (int)c->h_chunks.size();
+  gl = c->glist.p;
+  gc = c->gcount.p;
   // (an asynchronous store batch still in flight may bring NaN wants or other subclient
   // counts: the tick is ready for k_general until the batch is retired)
-  const bool general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
+  general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
   if (general) {  // only non-small resources are ever appended to the worklist
     DM_HIP(c, hipMemsetAsync(gc, 0, sizeof(int32_t), st), "worklist reset");
     c->main_dirty = true;
@@ -1884,17 +1850,17 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
     }
   if (!c->h_tiles.empty()) used |= 1u << c->class_stream[kNumBins];
   if (nch > 0) used |= 1u << c->class_stream[kNumBins + 1];
-  const bool fork = __builtin_popcount(used) > 1;
+  fork = __builtin_popcount(used) > 1;
   int nonempty_bins = 0;
   for (int b = 0; b < kNumBins; ++b) nonempty_bins += c->h_bins[b].empty() ? 0 : 1;
   // one work class (on the context stream, or in stream parts): its split bin's last
   // kernel completes the tick's event (only check_dense's hint count may follow it)
   bool parts_only = false;
   for (int b = 0; b < kNumBins; ++b) parts_only |= !c->h_bins[b].empty() && c->bin_parts[b] > 1;
-  const bool one_class = (!fork || parts_only) && nch == 0 && c->h_tiles.empty() && !general && nonempty_bins == 1;
+  one_class = (!fork || parts_only) && nch == 0 && c->h_tiles.empty() && !general && nonempty_bins == 1;
   if (fork && wb && c->tick_signal_wanted == false) DM_HIP(c, calib_step(c), "queue calibration");
-  auto cls_stream = [&](int cls) { return fork ? c->aux[c->class_stream[cls]] : st; };
-  hipStream_t s_large = cls_stream(kNumBins + 1), s_small = cls_stream(kNumBins);
+  s_large = cls_stream(kNumBins + 1);
+  s_small = cls_stream(kNumBins);
   if (!fork) {  // everything on the context stream, after any deferred class work
     DM_HIP(c, c->join_aux(), "join");
     c->main_dirty = true;
@@ -1905,88 +1871,171 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
     c->main_dirty = false;
   }
   if (fork) c->aux_unjoined |= used;
-  {
-    const int nls = (int)c->h_large.size();
-    // heterogeneous-subclient FairShare is decided on the chain when the store may
-    // hold it (k_large_t, k_large_c_het, k_large_e, k_large_map_het)
-    const bool het = general && nch > 0;
-    if (het) {
-      const size_t nc = (size_t)nch, nl = (size_t)std::max(nls, 1);
-      if (c->ph_set_ready < nl || c->ph_set.n < nl * 2 * kHetMaxS) {
-        DM_HIP(c, c->ph_set.ensure(nl * 2 * kHetMaxS), "heterogeneous partials");
-        DM_HIP(c, c->ph_n.ensure(nl), "heterogeneous partials");
-        DM_HIP(c, hipMemsetAsync(c->ph_set.p, 0xFF, nl * 2 * kHetMaxS * sizeof(uint32_t), s_large), "heterogeneous sets");
-        DM_HIP(c, hipMemsetAsync(c->ph_n.p, 0, nl * sizeof(int32_t), s_large), "heterogeneous sets");
-        c->ph_set_ready = nl;
-      }
-      DM_HIP(c, c->ph_het.ensure(nl * sizeof(HetRes)), "heterogeneous partials");
-      DM_HIP(c, c->ph_bkw.ensure(nc * kHetBuckets), "heterogeneous partials");
-      DM_HIP(c, c->ph_bks.ensure(nc * kHetBuckets), "heterogeneous partials");
-      DM_HIP(c, c->ph_bkc.ensure(nc * kHetBuckets), "heterogeneous partials");
-      P.s_set = c->ph_set.p;
-      P.s_n = c->ph_n.p;
-      P.het = c->ph_het.p;
-      P.bk_w = c->ph_bkw.p;
-      P.bk_s = c->ph_bks.p;
-      P.bk_c = c->ph_bkc.p;
+  return DM_OK;
+}
+
+int Tick::large_chain() {
+  const int nls = (int)c->h_large.size();
+  // heterogeneous-subclient FairShare is decided on the chain when the store may
+  // hold it (k_large_t, k_large_c_het, k_large_e, k_large_map_het)
+  const bool het = general && nch > 0;
+  if (het) {
+    const size_t nc = (size_t)nch, nl = (size_t)std::max(nls, 1);
+    if (c->ph_set_ready < nl || c->ph_set.n < nl * 2 * kHetMaxS) {
+      DM_HIP(c, c->ph_set.ensure(nl * 2 * kHetMaxS), "heterogeneous partials");
+      DM_HIP(c, c->ph_n.ensure(nl), "heterogeneous partials");
+      DM_HIP(c, hipMemsetAsync(c->ph_set.p, 0xFF, nl * 2 * kHetMaxS * sizeof(uint32_t), s_large), "heterogeneous sets");
+      DM_HIP(c, hipMemsetAsync(c->ph_n.p, 0, nl * sizeof(int32_t), s_large), "heterogeneous sets");
+      c->ph_set_ready = nl;
     }
-    P.b_first = (!het && !p.recompute && !c->expl_rows) ? 1 : 0;
-    P.s_live = (!het && live_ok && !c->expl_rows) ? 1 : 0;
-    P.uni = c->p_uni.p;
-    // A, B, [T], C, [C_het, E], map, [map_het], fin
-    static constexpr int kSeq[9] = {0, 1, 5, 2, 6, 7, 3, 8, 4};
-    static constexpr int kCls[9] = {KC_LARGE_A, KC_LARGE_B,   KC_LARGE_T,  KC_LARGE_C,  KC_LARGE_CH,
-                                    KC_LARGE_E, KC_LARGE_MAP, KC_LARGE_MH, KC_LARGE_FIN};
-    // the steady state: one speculative launch, verified per resource, and a redo launch
-    // that only the resources whose totals moved use (the store's rows must not be
-    // overwritten by the speculative gets: alternate output columns)
-    const bool spec = c->spec_chain && !het && P.b_first && wb && p.out_gets != p.has && nch > 0;
-    if (spec) {
-      const SpecArgs S{c->p_spec.p, c->spec_seq, c->d_serr, c->p_spec_ring.p, (int)(c->spec_seq & 1), nch,
-                       reinterpret_cast<uint32_t*>(c->d_serr + 1), c->p_team.p, c->nslots};
-      c->spec_seq += 1;
-      const bool light = c->redo_light == 2 || (c->redo_light == 1 && c->redo_epoch == c->row_epoch &&
-                                                __atomic_exchange_n(c->h_serr + 1, 0, __ATOMIC_RELAXED) == 0);
-      c->redo_epoch = c->row_epoch;
-      const int redo_phase = light ? 2 : 1;
-      const int redo_grid = light ? c->team_grid_light : c->team_grid_full;
-      for (int ph = 0; ph < 2; ++ph)
-        DM_HIP(c, timed(ph == 0 ? KC_LARGE_SPEC : KC_LARGE_REDO, s_large,
-                        [&] {
-                          return launch_large_spec(ph == 0 ? 0 : redo_phase, p, c->chunks.p, nch, c->large.p, P, S,
-                                                   redo_grid, gl, gc, s_large);
-                        }),
-               "large-resource kernels");
-    }
-    for (int i = 0; i < 9 && nch > 0 && !spec; ++i) {
-      const int ph = kSeq[i];
-      if (ph >= 5 && !het) continue;
-      if (ph == 4 && !het) continue;  // the map's last-arriving chunks did fin's work
-      DM_HIP(c, timed(kCls[i], s_large,
-                      [&] { return launch_large(ph, p, c->chunks.p, nch, c->large.p, nls, P, gl, gc, s_large); }),
-             "large-resource kernels");
-    }
-    chain_live = nch > 0 && !het;
+    DM_HIP(c, c->ph_het.ensure(nl * sizeof(HetRes)), "heterogeneous partials");
+    DM_HIP(c, c->ph_bkw.ensure(nc * kHetBuckets), "heterogeneous partials");
+    DM_HIP(c, c->ph_bks.ensure(nc * kHetBuckets), "heterogeneous partials");
+    DM_HIP(c, c->ph_bkc.ensure(nc * kHetBuckets), "heterogeneous partials");
+    P.s_set = c->ph_set.p;
+    P.s_n = c->ph_n.p;
+    P.het = c->ph_het.p;
+    P.bk_w = c->ph_bkw.p;
+    P.bk_s = c->ph_bks.p;
+    P.bk_c = c->ph_bkc.p;
   }
+  P.b_first = (!het && !p.recompute && !c->expl_rows) ? 1 : 0;
+  P.s_live = (!het && live_ok && !c->expl_rows) ? 1 : 0;
+  P.uni = c->p_uni.p;
+  // A, B, [T], C, [C_het, E], map, [map_het], fin
+  static constexpr int kSeq[9] = {0, 1, 5, 2, 6, 7, 3, 8, 4};
+  static constexpr int kCls[9] = {KC_LARGE_A, KC_LARGE_B,   KC_LARGE_T,  KC_LARGE_C,  KC_LARGE_CH,
+                                  KC_LARGE_E, KC_LARGE_MAP, KC_LARGE_MH, KC_LARGE_FIN};
+  // the steady state: one speculative launch, verified per resource, and a redo launch
+  // that only the resources whose totals moved use (the store's rows must not be
+  // overwritten by the speculative gets: alternate output columns)
+  const bool spec = c->spec_chain && !het && P.b_first && wb && p.out_gets != p.has && nch > 0;
+  if (spec) {
+    const SpecArgs S{c->p_spec.p, c->spec_seq, c->d_serr, c->p_spec_ring.p, (int)(c->spec_seq & 1), nch,
+                     reinterpret_cast<uint32_t*>(c->d_serr + 1), c->p_team.p, c->nslots};
+    c->spec_seq += 1;
+    const bool light = c->redo_light == 2 || (c->redo_light == 1 && c->redo_epoch == c->row_epoch &&
+                                              __atomic_exchange_n(c->h_serr + 1, 0, __ATOMIC_RELAXED) == 0);
+    c->redo_epoch = c->row_epoch;
+    const int redo_phase = light ? 2 : 1;
+    const int redo_grid = light ? c->team_grid_light : c->team_grid_full;
+    for (int ph = 0; ph < 2; ++ph)
+      DM_HIP(c, timed(ph == 0 ? KC_LARGE_SPEC : KC_LARGE_REDO, s_large,
+                      [&] {
+                        return launch_large_spec(ph == 0 ? 0 : redo_phase, p, c->chunks.p, nch, c->large.p, P, S,
+                                                 redo_grid, gl, gc, s_large);
+                      }),
+             "large-resource kernels");
+  }
+  for (int i = 0; i < 9 && nch > 0 && !spec; ++i) {
+    const int ph = kSeq[i];
+    if (ph >= 5 && !het) continue;
+    if (ph == 4 && !het) continue;  // the map's last-arriving chunks did fin's work
+    DM_HIP(c, timed(kCls[i], s_large,
+                    [&] { return launch_large(ph, p, c->chunks.p, nch, c->large.p, nls, P, gl, gc, s_large); }),
+           "large-resource kernels");
+  }
+  chain_live = nch > 0 && !het;
+  return DM_OK;
+}
+
+int Tick::subs() {
+  // the sub-wave bins (8x2, 16x2, 16x4, 32x4, 64x4) in one launch on bin 0's stream
+  SubBins sb{};
+  int nonempty = 0;
+  for (int k = 0; k < kSubShapes; ++k) {  // each sub-wave bin's items by shape (build_plan)
+    const int b = kSubShapeBin[k], n = (int)c->h_shape_n[k];
+    const int per = 256 / kSubShapeG[k];
+    sb.items[k] = c->bins[b].p + c->h_shape_lo[k];
+    sb.n[k] = n;
+    sb.blocks[k] = (n + per - 1) / per;
+    nonempty += n > 0;
+  }
+  if (nonempty > 0) {
+    hipStream_t s = cls_stream(0);
+    DM_HIP(c, timed(KC_SUBS, s, [&] { return launch_subs(p, sb, gl, gc, s); }), "sub-wave kernel");
+  }
+  return DM_OK;
+}
+
+int Tick::bin_part(int b, int lb, int nparts, bool split_dense, int j) {
+  const int64_t lo = c->part_lo[b][j];
+  const int n = (int)(c->part_lo[b][j + 1] - lo);
+  if (n == 0) return DM_OK;
+  WorkItem* items = c->bins[b].p + lo;
+  hipStream_t s = j == 0 ? cls_stream(b) : c->aux[c->part_stream(b, j)];
+  DevParams pj = p;
+  if (nparts > 1 && p.pub) {  // the part's own flags word (DevParams::pub_word)
+    pj.pub_word = j;
+    pj.pub_first = c->h_bins[b][(size_t)lo].seg;
+  }
+  // the tick's last kernel of this part (the dense kernel, or the rest kernel after
+  // it) completes the part's tick event when another queue waits for the tick
+  hipEvent_t done = nullptr;
+  if (one_class && c->tick_signal_wanted) {
+    done = c->tick_ev[j][c->tick_seq % dm_ctx::kTickEv];
+    c->tick_part_mask |= fork ? 1u << (j == 0 ? c->class_stream[b] : c->part_stream(b, j)) : 0u;
+  }
+  const int i = (b - 3) * dm_ctx::kParts + j;  // split slot (bins 3-6)
+  if (b >= 3 && b < 3 + dm_ctx::kSplitBins && ((c->dense_split >> (b - 3)) & 1) && split_dense) {
+    // only a writeback tick sets hints, so the split form follows one
+    const int par = c->dq_par[i];
+    const int64_t queued = __atomic_load_n(c->h_dq + i, __ATOMIC_RELAXED);
+    const bool good = 4 * queued <= n;
+    if (good) c->dq_wait[i] = 64;
+    if (good || ++c->dq_skip[i] >= c->dq_wait[i]) {
+      if (!good) c->dq_wait[i] = std::min(2 * c->dq_wait[i], 4096);
+      c->dq_skip[i] = 0;
+      // Every item verified dense in this row epoch: nothing can be queued, so the
+      // dense kernel is the part's only launch (the guard catches the impossible).
+      const uint64_t* rec = c->h_rec + 2 * i;
+      const bool verified = __atomic_load_n(rec + 1, __ATOMIC_ACQUIRE) == c->row_epoch;
+      const uint64_t counts = __atomic_load_n(rec, __ATOMIC_RELAXED);  // low half: items not dense
+      // The steady builds: every item verified dense and none with released rows or
+      // arrivals (the counts' high half), no recompute.  What the host cannot rule out
+      // is a lapse of the followers (lease lengths change on the device), so the steady
+      // kernel queues such an item and the rest kernel always follows it, with the
+      // tick's event; the guard is for launches that queue nothing.
+      // Not for a bin in stream parts: its ticks are short enough for the rest launch to
+      // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
+      // profiles/steady_ab.md).
+      const bool steady_form = c->steady_ok && nparts == 1 && verified && counts == 0 && !p.recompute;
+      const bool steady = steady_form && c->steady_ok != 2;
+      const bool skip = !steady_form && verified && (uint32_t)counts == 0;
+      if (steady) c->steady_mask |= 1u << i;
+      DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
+               return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
+                                       skip ? c->d_guard + i : nullptr, skip ? done : nullptr, steady, s);
+             }),
+             "group kernel (dense split)");
+      if (!skip) {
+        // the rest kernel strides over whatever the dense kernel queues; its grid is
+        // only sized from the last split tick's queue (a hint: correctness never
+        // depends on it): an empty queue costs 16 workgroups that read one count
+        const int rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, queued));
+        DM_HIP(c, timed(KC_REST3 + (b - 3), s, [&] {
+                 return launch_bin_rest(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, c->d_dq + i,
+                                        rest_grid, gl, gc, done, s);
+               }),
+               "group kernel (dense split)");
+        c->dq_par[i] ^= 1;
+      }
+      if (wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
+      return DM_OK;
+    }
+  }
+  if (done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
+    c->tick_flagged = false;
+    c->tick_part_mask = 0;
+  }
+  DM_HIP(c, timed(KC_BIN0 + b, s, [&] { return launch_bin(lb, pj, items, n, gl, gc, s); }), "group kernel");
+  if (b >= 3 && b < 3 + dm_ctx::kSplitBins && wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
+  return DM_OK;
+}
+
+int Tick::bins() {
   // the workgroup bins split by the dense hint after a writeback tick (hints set)
   const bool split_dense = c->hints_set;
-  // the sub-wave bins (8x2, 16x2, 16x4, 32x4, 64x4) in one launch on bin 0's stream
-  {
-    SubBins sb{};
-    int nonempty = 0;
-    for (int k = 0; k < kSubShapes; ++k) {  // each sub-wave bin's items by shape (build_plan)
-      const int b = kSubShapeBin[k], n = (int)c->h_shape_n[k];
-      const int per = 256 / kSubShapeG[k];
-      sb.items[k] = c->bins[b].p + c->h_shape_lo[k];
-      sb.n[k] = n;
-      sb.blocks[k] = (n + per - 1) / per;
-      nonempty += n > 0;
-    }
-    if (nonempty > 0) {
-      hipStream_t s = cls_stream(0);
-      DM_HIP(c, timed(KC_SUBS, s, [&] { return launch_subs(p, sb, gl, gc, s); }), "sub-wave kernel");
-    }
-  }
   c->steady_mask = 0;
   for (int b = kNumBins - 1; b >= 0; --b) {
     if (c->h_bins[b].empty()) continue;
@@ -2000,80 +2049,13 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
       c->tick_nev[c->tick_seq % dm_ctx::kTickEv] = nparts;
       c->tick_part_mask = 0;
     }
-    for (int j = 0; j < nparts; ++j) {
-      const int64_t lo = c->part_lo[b][j];
-      const int n = (int)(c->part_lo[b][j + 1] - lo);
-      if (n == 0) continue;
-      WorkItem* items = c->bins[b].p + lo;
-      hipStream_t s = j == 0 ? cls_stream(b) : c->aux[c->part_stream(b, j)];
-      DevParams pj = p;
-      if (nparts > 1 && p.pub) {  // the part's own flags word (DevParams::pub_word)
-        pj.pub_word = j;
-        pj.pub_first = c->h_bins[b][(size_t)lo].seg;
-      }
-      // the tick's last kernel of this part (the dense kernel, or the rest kernel after
-      // it) completes the part's tick event when another queue waits for the tick
-      hipEvent_t done = nullptr;
-      if (one_class && c->tick_signal_wanted) {
-        done = c->tick_ev[j][c->tick_seq % dm_ctx::kTickEv];
-        c->tick_part_mask |= fork ? 1u << (j == 0 ? c->class_stream[b] : c->part_stream(b, j)) : 0u;
-      }
-      const int i = (b - 3) * dm_ctx::kParts + j;  // split slot (bins 3-6)
-      if (b >= 3 && b < 3 + dm_ctx::kSplitBins && ((c->dense_split >> (b - 3)) & 1) && split_dense) {
-        // only a writeback tick sets hints, so the split form follows one
-        const int par = c->dq_par[i];
-        const int64_t queued = __atomic_load_n(c->h_dq + i, __ATOMIC_RELAXED);
-        const bool good = 4 * queued <= n;
-        if (good) c->dq_wait[i] = 64;
-        if (good || ++c->dq_skip[i] >= c->dq_wait[i]) {
-          if (!good) c->dq_wait[i] = std::min(2 * c->dq_wait[i], 4096);
-          c->dq_skip[i] = 0;
-          // Every item verified dense in this row epoch: nothing can be queued, so the
-          // dense kernel is the part's only launch (the guard catches the impossible).
-          const uint64_t* rec = c->h_rec + 2 * i;
-          const bool verified = __atomic_load_n(rec + 1, __ATOMIC_ACQUIRE) == c->row_epoch;
-          const uint64_t counts = __atomic_load_n(rec, __ATOMIC_RELAXED);  // low half: items not dense
-          // The steady builds: every item verified dense and none with released rows or
-          // arrivals (the counts' high half), no recompute.  What the host cannot rule out
-          // is a lapse of the followers (lease lengths change on the device), so the steady
-          // kernel queues such an item and the rest kernel always follows it, with the
-          // tick's event; the guard is for launches that queue nothing.
-          // Not for a bin in stream parts: its ticks are short enough for the rest launch to
-          // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
-          // profiles/steady_ab.md).
-          const bool steady_form = c->steady_ok && nparts == 1 && verified && counts == 0 && !p.recompute;
-          const bool steady = steady_form && c->steady_ok != 2;
-          const bool skip = !steady_form && verified && (uint32_t)counts == 0;
-          if (steady) c->steady_mask |= 1u << i;
-          DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
-                   return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
-                                           skip ? c->d_guard + i : nullptr, skip ? done : nullptr, steady, s);
-                 }),
-                 "group kernel (dense split)");
-          if (!skip) {
-            // the rest kernel strides over whatever the dense kernel queues; its grid is
-            // only sized from the last split tick's queue (a hint: correctness never
-            // depends on it): an empty queue costs 16 workgroups that read one count
-            const int rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, queued));
-            DM_HIP(c, timed(KC_REST3 + (b - 3), s, [&] {
-                     return launch_bin_rest(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, c->d_dq + i,
-                                            rest_grid, gl, gc, done, s);
-                   }),
-                   "group kernel (dense split)");
-            c->dq_par[i] ^= 1;
-          }
-          if (wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
-          continue;
-        }
-      }
-      if (done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
-        c->tick_flagged = false;
-        c->tick_part_mask = 0;
-      }
-      DM_HIP(c, timed(KC_BIN0 + b, s, [&] { return launch_bin(lb, pj, items, n, gl, gc, s); }), "group kernel");
-      if (b >= 3 && b < 3 + dm_ctx::kSplitBins && wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
-    }
+    for (int j = 0; j < nparts; ++j)
+      if (int rc = bin_part(b, lb, nparts, split_dense, j)) return rc;
   }
+  return DM_OK;
+}
+
+int Tick::finish() {
   if (!c->h_tiles.empty())
     DM_HIP(c, timed(KC_SMALL, s_small, [&] { return launch_tile_small(p, c->tiles.p, c->tile_list.p, (int)c->h_tiles.size(), s_small); }),
            "small kernel");
@@ -2095,11 +2077,29 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   if (wb) c->expl_rows = false;
   c->chain_live_ok = wb && chain_live;
   if (!(flags & DM_ASYNC)) {
-    rc = c->synced("tick");
+    const int rc = c->synced("tick");
     c->collect_profile();
     return rc;
   }
   return DM_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
+  DM_CHECK_CTX(c);
+  int rc = ready(c);
+  if (rc) return rc;
+  if (c->tpl_pipe && (rc = commit_templates(c))) return rc;
+  c->ticks_issued += 1;
+  c->tick_seq += 1;
+  c->tick_flagged = false;
+  Tick t{c, now_ns, flags};
+  if ((rc = t.outputs()) || (rc = t.streams()) || (rc = t.large_chain()) || (rc = t.subs()) ||
+      (rc = t.bins()))
+    return rc;
+  return t.finish();
 }
 
 // A round of requests, each decided by Resource.Decide in the caller's order and

@@ -1,0 +1,922 @@
+// dm_tick_group.hip — gfx950 kernels for one apportionment tick: the resource-per-group
+// kernels (workgroup bins, sub-wave groups, packed tiles).  The other work classes of a
+// tick: dm_tick_large.hip (the large-resource chain), dm_tick_general.hip (k_general).
+//
+// Every lease row is decided against the same frozen store (include/doorman_hip.h).
+// Per resource the reference's per-request loops (go/server/doorman/algorithm.go)
+// collapse to segmented reductions:
+//   Clean          store.go:169-181   pass A: expired-row sums (parity) or live sums
+//   ProportionalShare algorithm.go:213-293  pass B: extraCapacity / extraNeed, then map
+//   FairShare      algorithm.go:95-206    pass B: extra / wantExtra (round 1),
+//                                         pass C: extraExtra / wantExtraExtra at T (round 2), then map
+//   NoAlgorithm / Static / Learn  algorithm.go:66-84,297-302  map only
+// No MFMA: the arithmetic is binary64 compares, adds and a few divisions per row, and
+// the segmented reductions.  Rows are read once from HBM into VGPRs and every pass runs
+// from registers; the large-resource path re-reads from L2 / Infinity Cache.  Bytes set
+// the floor (24-48 B per lease), but the dense tick that skips unchanged stores is bound
+// by vector issue, not HBM: ~160 VALU instructions per row slot keep every SIMD's VALU
+// busy for the kernel's whole duration (profiles/steady_pmc.md), hence the steady builds
+// below, which leave out the pass whose result is known.
+//
+// Float semantics follow Go on amd64: binary64, no FMA contraction (built with
+// -ffp-contract=off), minF = `l > r ? r : l`, IEEE division by zero.
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "dm_kernel_util.h"
+#include "dm_launch.h"
+#include "dm_update_util.h"
+
+namespace dm {
+
+// --------------------------------------------------------------------------
+// Resource-per-group kernel: G threads (a wave or a 256-thread workgroup) own
+// one resource of up to G*R rows; rows live in VGPRs across all passes.
+// --------------------------------------------------------------------------
+// MODE (the 128/256/512-thread bins): kMixed = one kernel for every item (hint or
+// not), kDenseOnly = items whose hint is set (k_block_dense: no subclients column at
+// all; a stale hint queues the item for k_block_rest and returns), kRest = queued
+// items (k_block_rest: the column is read, the hint rewritten).
+enum { kMixed = 0, kDenseOnly = 1, kRest = 2 };
+// Gets stores: non-temporal for the workgroup bins and the large chain (long contiguous
+// spans: whole lines); plain for the sub-wave groups, whose spans are short and
+// unaligned, so that L2 merges the partial sectors two groups write at a resource
+// boundary (C2 112.2-112.5 -> 109.6-111.1 us, three interleaved rounds; the chain's
+// stores plain: no change; profiles/r05_ab/c2_gets_stores.txt; the chain's switch is
+// kSpecNT, dm_tick_large.hip)
+template <int G> constexpr bool kGroupNT = G >= 128;
+
+// One live row's gets in the skipping map of group_segment: the resource's algorithm on
+// the row's wants / has / subclients and the passes' sums, the same decisions as the
+// plain loop's (which keeps its inline form: every build without the skip is then the
+// code it was, register for register).
+__device__ __forceinline__ double row_gets(const Res& rs, bool ps, double C, double eq, const Clean& cl,
+                                           const AggB& b, const FsU& fu, double w, double h, int s) {
+  if (rs.learning) return h;             // Learn (algorithm.go:297-302)
+  if (rs.kind == 0) return w;            // NoAlgorithm
+  if (rs.kind == 1) return minF(C, w);   // Static
+  if (ps) {
+    const double epc = eq * (double)s;         // :233
+    const double unused = C - cl.sum_has + h;  // :239
+    return (cl.sum_wants <= C || w <= epc) ? minF(w, unused)                               // :245
+                                           : minF(epc + (w - epc) * (b.x / b.y), unused);  // :283
+  }
+  return fs_uniform_row(w, h, C, cl.sum_has, fu);
+}
+
+template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false>
+__device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
+                                              Lds<G>& lds, int32_t* general_list, int32_t* general_count,
+                                              int32_t* queue = nullptr, int32_t* qcount = nullptr,
+                                              int32_t qidx = 0, int32_t* guard = nullptr, int qcap = 0) {
+  // the dense state (below): every workgroup kernel tracks it and writes the hints;
+  // only the 128-thread mixed kernel and the dense-only kernels load by the hint
+  constexpr bool kDense = G >= 128 || (G == 64 && R >= 16);  // (64 x 16: kBin4Wave)
+  constexpr bool kHintLoad = (G == 128 && MODE == kMixed) || MODE == kDenseOnly;
+  static_assert(!STEADY || MODE == kDenseOnly, "the steady build is a dense-only build");
+  const int seg = wi.seg;
+  const int64_t lo = wi.lo;
+  const int n = kDense ? wi.n & 0xFFFF : wi.n;
+  // wave-uniform bases + 32-bit per-lane offsets: one VGPR addresses every column
+  const double* __restrict__ wb = p.wants + lo;
+  const double* __restrict__ hb = p.has + lo;
+  const int32_t* __restrict__ sb = p.sub + lo;
+  const int64_t* __restrict__ eb = p.expiry + lo;
+  // the rows stay in VGPRs for every pass: 6 registers per row
+  double w[R], h[R];
+  int s[R];   // subclients in [0, kSubMax]
+  int sr[R];  // the raw subclients words: where each row's expiry lives (dm_device.h)
+  unsigned valid = 0, live = 0;
+  unsigned relm = 0;  // rows a dense resource's mask says are released (bit k: row k*G + t)
+  unsigned relb = 0;  // rows whose subclients word marks them released
+  // Every load is issued before any is consumed: lanes past the segment end
+  // re-read row n-1 (same cache line, n >= 1 in every bin) instead of branching
+  // around the load, which made the compiler wait on each row's expiry before
+  // issuing the next row (R serial memory latencies per workgroup).
+  // A dense resource (every row a live follower with the same subclients s0, the
+  // state its last writeback tick left: dm_device.h) is not read from the
+  // subclients column: 24 B per lease instead of 28.  The work item carries the
+  // state as a hint (no dependent load before the rows); the resource's own byte,
+  // loaded with its record, confirms it, and a stale hint (an upsert or release
+  // since that tick) reads the column after all.  The 128-thread mixed kernel
+  // (257-1024 rows) loads by the hint; the 256/512-thread mixed kernels (1025-4096
+  // rows) only track the state and write the hints (the extra branch costs
+  // registers they do not have: spills at 5 waves per SIMD, C2 +3.5 %), and their
+  // dense-only kernels skip the column.
+  // A dense resource may also hold released rows (C2: loaded leases that had lapsed):
+  // its hint word carries "has released rows" (bit 8) and the tick that set it wrote
+  // which rows they are, one mask entry of R bits per lane (RelMask), read here in
+  // place of the column: 1-2 B per lane instead of 4 B per row.
+  const int hw = kDense ? wi.n >> 16 : 0;  // hint word: s0 in bits 0-7, released rows in bit 8, arrivals in bit 9
+  const int hint = (kHintLoad) ? hw & 0xFF : 0;
+  using MaskT = typename RelMask<R>::T;
+  MaskT* const mrow = reinterpret_cast<MaskT*>(p.rmask + rel_mask_offset(lo));
+  // rows upserted since the dense state was set (dm_device.h mask_pos): the high nibble
+  // of the released-row entry for R <= 4, else G entries after the released-row ones
+  constexpr unsigned kRowBits = R >= 32 ? ~0u : (1u << R) - 1u;
+  const bool arrivals = !STEADY && kDense && ((hw >> 9) & 1);
+  bool by_hint = MODE == kDenseOnly;  // the rows' states come from the hint and the masks, not the column
+  if (MODE != kDenseOnly && !hint) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = k * G + t;
+      const unsigned u = (unsigned)(i < n ? i : n - 1);
+      // plain loads: non-temporal loads measured 3-4% slower (tools/ab.py, C1 and C3)
+      w[k] = *col_at(wb, u);
+      h[k] = *col_at(hb, u);
+      sr[k] = *col_at(sb, u);
+    }
+  } else {
+    if (!STEADY && (hw >> 8 & 1)) relm = (unsigned)mrow[t] & kRowBits;
+    by_hint = true;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = k * G + t;
+      const unsigned u = (unsigned)(i < n ? i : n - 1);
+      w[k] = *col_at(wb, u);
+      h[k] = *col_at(hb, u);
+      sr[k] = hint;  // uniform: the mask's rows are taken out below (one register, not R)
+    }
+  }
+  const Res rs = load_res(p, seg);
+  // arrivals outlive the followers (at or after follow_exp): only a tick past follow_exp
+  // needs their own expiries, from the columns
+  const bool arr_lapse = arrivals && p.now > rs.follow_exp;
+  if constexpr (MODE == kDenseOnly) {
+    // STEADY (k_block_dense's steady builds, launched when the host knows of no released
+    // row, arrival or recompute in the part: dm_runtime.cpp): an item with a released-row
+    // or arrival bit after all, or whose followers have lapsed (lease lengths change on
+    // the device, so only the kernel can tell), goes to k_block_rest like a stale hint.
+    // What is left has a known Clean (below), with no row examined.
+    const bool stale = dense_subclients(rs) != hint;
+    const bool rest = STEADY ? stale || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute : stale || arr_lapse;
+    if (rest) {  // stale hint: k_block_rest reads the column
+      if (t == 0) {
+        const int q = atomicAdd(qcount, 1);
+        if (q < qcap) queue[q] = qidx;  // at most one entry per item and tick (a guarded tick's count may grow)
+        if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      return;
+    }
+  } else if (kHintLoad && hint && (dense_subclients(rs) != hint || arr_lapse)) {
+    relm = 0;  // the column says which rows are released now
+    by_hint = false;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = k * G + t;
+      sr[k] = *col_at(sb, (unsigned)(i < n ? i : n - 1));
+    }
+  }
+  // Followers expire with their resource; only a resource whose rows may carry an
+  // explicit expiry (loaded / upserted by the host, none after a writeback tick)
+  // reads the 8-B expiry column.  The test is the resource's flag, not the rows'
+  // subclients words, which would make every wave wait for its loads to decide.
+  int64_t e[R];
+  if constexpr (STEADY) {  // every row a live follower of hint subclients: no expiry, no released row
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      valid |= ((k * G + t < n) ? 1u : 0u) << k;
+      s[k] = hint;
+    }
+    live = valid;
+  } else {
+#pragma unroll
+    for (int k = 0; k < R; ++k) e[k] = rs.follow_exp;
+    if (MODE != kDenseOnly && (any_explicit(rs) || arr_lapse)) {  // a dense resource: only its lapsing arrivals
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int i = k * G + t;
+        const int64_t x = *col_at(eb, (unsigned)(i < n ? i : n - 1));
+        if (sub_explicit(sr[k])) e[k] = x;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {  // rows past the end stay out of valid/live, so every pass skips them
+      const unsigned vk = (k * G + t < n) ? 1u : 0u;
+      valid |= vk << k;
+      if (sub_released(sr[k])) e[k] = kReleased;
+      live |= (vk & (p.now > e[k] ? 0u : 1u)) << k;  // store.go:174 when.After(expiry)
+      relb |= (sub_released(sr[k]) ? 1u : 0u) << k;
+      s[k] = sub_value(sr[k]);
+    }
+    live &= ~relm;
+  }
+
+  // ---- pass A: Clean ----
+  // STEADY: Clean releases nothing (exact zeros: nothing is ever added) and every row is
+  // live with hint subclients, so the loop, its reduction and its barrier are left out.
+  // Only "any NaN wants" depends on the rows: FairShare (the one user) counts them with
+  // pass B's reduction, in bits 48 and up of AggB::i (the sum itself stays below 2^43).
+  AggA a = zeroA();
+  if constexpr (STEADY) {
+    a.smin = a.smax = hint;
+    a.nlive = n;
+  } else {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (!(valid >> k & 1)) continue;
+      const bool lv = live >> k & 1;
+      const int sk = (relm >> k & 1) ? 0 : s[k];  // a released row counts nothing (its wants and has are 0)
+      if (!lv) {
+        a.cnt += sk;
+        a.h += h[k];
+        a.w += w[k];
+      }
+      if (p.recompute) {
+        a.all.cnt += sk;
+        a.all.h += h[k];
+        a.all.w += w[k];
+      }
+      if (lv) {
+        a.smin = s[k] < a.smin ? s[k] : a.smin;
+        a.smax = s[k] > a.smax ? s[k] : a.smax;
+        a.nan |= __builtin_isnan(w[k]) ? 1 : 0;
+        a.nlive += 1;
+      }
+    }
+  }
+  if constexpr (!STEADY) {
+    const AggR all_part = a.all;
+    bool fast_a = false;
+    if constexpr (G <= 64) {
+      // Sub-wave and wave groups are VALU-bound on their reductions.  In the steady
+      // state pass A's totals are known wave-wide without one: no row of the wave is
+      // released by this Clean (rows already marked released hold zeros), its live
+      // rows share one subclient count u, no wants is NaN.  Then every group's Clean
+      // sums are exact zeros and its live range is [u, u] (empty: no live row).
+      if (!p.recompute) {
+        const uint64_t lv = __ballot(live != 0);
+        const int u = __builtin_amdgcn_readlane(a.smin, lv ? (int)__builtin_ctzll(lv) : 0);
+        const bool ok = (valid & ~live & ~relb) == 0 && a.cnt == 0 && __double_as_longlong(a.h) == 0 &&
+                        __double_as_longlong(a.w) == 0 && !a.nan && (live == 0 || (a.smin == u && a.smax == u));
+        if (__all(ok)) {
+          fast_a = true;
+          const int base = (int)(threadIdx.x & 63) & ~(G - 1);
+          uint64_t gmask = ~0ull;
+          if constexpr (G < 64) gmask = ((1ull << G) - 1) << base;
+          const bool any_live = (lv & gmask) != 0;
+          a.smin = any_live ? u : INT32_MAX;
+          a.smax = any_live ? u : INT32_MIN;
+        }
+      }
+    }
+    if (!fast_a) a = group_reduce<G, AggA, OpA, false>(a, OpA(), lds.a);
+    if (p.recompute) a.all = group_reduce<G, AggR, OpR, false>(all_part, OpR(), lds.r);
+  }
+  // (STEADY: the running sums as they are; never in recompute mode)
+  const Clean cl = STEADY ? Clean{rs.agg_count, rs.agg_has, rs.agg_wants} : clean_from(p, rs, a);
+  const double C = rs.C;
+  const double eq = C / (double)cl.count;  // algorithm.go:123,229 equalShare
+  const bool ps = !rs.learning && rs.kind == 2;
+  const bool fs = !rs.learning && rs.kind == 3;
+  const bool fs_uniform = fs && a.smin >= a.smax && !a.nan;  // no live rows counts as uniform
+  constexpr long long kNanOne = 1ll << 48;  // STEADY: a NaN wants in AggB::i
+  if (!STEADY && fs && !fs_uniform) {
+    // heterogeneous subclients (GetServerCapacity, server.go:850-879) or NaN wants:
+    // one round-2 threshold per distinct subclient count.  Rare (the hierarchy's
+    // root level), so the whole resource goes to k_general, untouched here.
+    if (t == 0) {
+      general_list[atomicAdd(general_count, 1)] = seg;
+      if (p.writeback && (wi.n >> 16)) item->n = n;  // k_general's writeback clears the byte
+    }
+    return;
+  }
+
+  // ---- pass B: ProportionalShare extraCapacity/extraNeed, FairShare round 1 ----
+  AggB b{0.0, 0.0, 0};
+  if (ps || fs) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (!(live >> k & 1)) continue;
+      if (ps) {
+        const double e = eq * (double)s[k];  // :273
+        if (w[k] < e)
+          b.x += e - w[k];  // :275
+        else
+          b.y += w[k] - e;  // :277
+      } else {
+        const double d = (double)s[k] * eq;  // :160
+        if (w[k] < d)
+          b.x += d - w[k];  // :164
+        else if (w[k] > d)
+          b.i += s[k];  // :168
+        if constexpr (STEADY) b.i += __builtin_isnan(w[k]) ? kNanOne : 0;  // (adds to neither sum above)
+      }
+    }
+    b = group_reduce<G, AggB, OpB, false>(b, OpB(), lds.b);
+    if constexpr (STEADY) {
+      if (b.i >= kNanOne) {  // FairShare with a NaN wants: k_general, as above (nothing is stored yet)
+        if (t == 0) {
+          general_list[atomicAdd(general_count, 1)] = seg;
+          if (p.writeback && (wi.n >> 16)) item->n = n;
+        }
+        return;
+      }
+    }
+  }
+
+  // ---- pass C (uniform subclients): FairShare round 2 at the resource's one threshold ----
+  AggC cu{0.0, 0};
+  FsU fu{0.0, 0.0, 0.0, 0.0, 0.0};
+  if (fs_uniform) {
+    fu = make_fsu(eq, a.smin, b.x, b.i, cu);
+    const double Tu = fu.T;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (!(live >> k & 1)) continue;
+      if (!(w[k] > (double)s[k] * eq)) continue;  // j in wantExtraClients (:165-169)
+      if (w[k] < Tu)
+        cu.ee += Tu - w[k];  // :197-198
+      else if (w[k] > Tu)
+        cu.sgt += s[k];  // :199-200
+    }
+    cu = group_reduce<G, AggC, OpC, false>(cu, OpC(), lds.c);
+    fu = make_fsu(eq, a.smin, b.x, b.i, cu);
+    if constexpr (G >= 64) fu = uniform(fu);  // one resource per wave or workgroup: SGPRs
+  }
+
+  // ---- map: decide and write every lease (store.go:153-167 Assign) ----
+  // SKIP (k_block_dense's second build, launched for a writeback tick in place: out_gets
+  // is the column h[] was loaded from) leaves out the gets store of a wave's 64-row run
+  // (512 B) when no row of the run changes: on a resource at its fixed point (no wants
+  // change, arrival, departure or capacity change since the last tick) the value is bit
+  // for bit the has just loaded, a third of the tick's bytes.  Bits, not values (-0.0,
+  // NaN payloads); a row Clean releases stores +0.0.  The ballot runs among the run's
+  // valid rows (lanes past n do not vote), so the store's branch is wave-uniform: whole
+  // runs, no partial lines.  The comparison reuses h[k] (live for delta) and leaves a
+  // scalar mask.  Every other store (subclients, wants of released rows, masks, the
+  // resource) stays.  Never on a non-writeback tick or on the alternate column, which
+  // holds the tick before last: those run the build without it, the loop as it always was.
+  SumD delta{0.0};
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    if (!(valid >> k & 1)) continue;
+    const unsigned u = (unsigned)(k * G + t);
+    if constexpr (SKIP) {
+      const bool lv = live >> k & 1;
+      const double g = lv ? row_gets(rs, ps, C, eq, cl, b, fu, w[k], h[k], s[k]) : 0.0;
+      const bool st = __ballot(__double_as_longlong(g) != __double_as_longlong(h[k])) != 0;
+      if (!lv) {  // released by Clean: no lease
+        put_released<kGroupNT<G>>(p, lo, u, (relm >> k & 1) ? (int)kSubReleased : sr[k], st);
+        continue;
+      }
+      put_live<kGroupNT<G>>(p, lo, u, g, rs, sr[k], st);
+      delta.v += g - h[k];
+      continue;
+    }
+    if (!(live >> k & 1)) {  // released by Clean: no lease
+      put_released<kGroupNT<G>>(p, lo, u, (relm >> k & 1) ? (int)kSubReleased : sr[k]);
+      continue;
+    }
+    double g;
+    if (rs.learning) {
+      g = h[k];  // Learn (algorithm.go:297-302)
+    } else if (rs.kind == 0) {
+      g = w[k];  // NoAlgorithm
+    } else if (rs.kind == 1) {
+      g = minF(C, w[k]);  // Static
+    } else if (ps) {
+      const double epc = eq * (double)s[k];         // :233
+      const double unused = C - cl.sum_has + h[k];  // :239
+      g = (cl.sum_wants <= C || w[k] <= epc) ? minF(w[k], unused)            // :245
+                                             : minF(epc + (w[k] - epc) * (b.x / b.y), unused);  // :283
+    } else {
+      g = fs_uniform_row(w[k], h[k], C, cl.sum_has, fu);
+    }
+    put_live<kGroupNT<G>>(p, lo, u, g, rs, sr[k]);
+    delta.v += g - h[k];
+  }
+  // (uniform) the live arrivals of a dense resource decided by the hint become followers:
+  // their explicit subclients words are rewritten (the arrival mask is loaded only here,
+  // so a store without arrivals carries no register for it)
+  unsigned arrm = 0;
+  if (arrivals && by_hint) {
+    arrm = R <= 4 ? ((unsigned)mrow[t] >> 4) & kRowBits : (unsigned)mrow[G + t];
+    if (p.writeback) {
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        if ((arrm & live) >> k & 1) *col_at(p.out_sub + lo, (unsigned)(k * G + t)) = hint;
+    }
+  }
+
+  // After a writeback tick every live row follows the resource and every other row
+  // is released: live rows with one subclient count s0 (1..254) make the resource
+  // dense.  Released rows among them go into its mask (written by the tick that sets
+  // the state; a dense tick leaves the state as it found it or, when the followers
+  // lapse together, ends it).
+  // A resource with no live row left (its followers lapsed together) stays dense,
+  // every row in its mask, so that a dense tick always leaves a dense resource dense
+  // (the host's skip of the rest kernel rests on it: dm_runtime.cpp).
+  const int nlive = a.nlive;
+  const int s_keep = (hw & 0xFF) ? (hw & 0xFF) : 1;
+  const int dn = !(kDense && p.writeback) ? 0
+                 : nlive == 0              ? s_keep
+                 : (a.smin == a.smax && a.smin >= 1 && a.smin <= 254) ? a.smin : 0;
+  const int hw_next = dn ? (dn | (nlive < n ? 1 << 8 : 0)) : 0;
+  delta = group_reduce<G, SumD, OpSumD, false>(delta, OpSumD(), lds.d);
+  if constexpr (STEADY) {  // the state stays as it is: dn == hint, hw_next == hw, no mask to write
+    if (t == 0) write_resource(p, seg, rs, cl, delta.v, hint);
+    return;
+  }
+  // A dense tick changes the mask only by a lapse; a writeback tick that changes the
+  // state word writes it whole (a later release ORs its row in, so it must be valid
+  // whenever the hint is set) and clears the arrivals it turned into followers.
+  if (kDense && (MODE == kDenseOnly ? nlive == 0 || (p.writeback && hw != hw_next)
+                                    : (hw_next >> 8) != 0 || (p.writeback && hw != hw_next))) {
+    // (R <= 4: a non-writeback tick keeps the arrivals' nibble)
+    mrow[t] = (MaskT)((valid & ~live) | (R <= 4 && !p.writeback ? arrm << 4 : 0u));
+    if (R > 4 && arrivals && p.writeback) mrow[G + t] = 0;
+  }
+  if (t == 0) {
+    write_resource(p, seg, rs, cl, delta.v, dn);
+    if (p.writeback && hw != hw_next) item->n = n | hw_next << 16;
+  }
+}
+
+// One G-thread workgroup per resource (G = 128..512, R = 4 or 8 rows per thread).
+// 257-1024 rows run on 128 threads (2 waves) with 8 rows each, held to 5 waves per
+// SIMD (<= 96 VGPRs): 5 x 4 SIMDs x 64 lanes x 8 rows = 10240 rows in flight per CU
+// against 7168 for 256 threads x 4 rows at 7 waves per SIMD (65 VGPRs).  The tick is
+// bound by bytes in flight: C3 560-590 -> 490-500 us, C1 61 -> 55 us
+// (tools/ab.py, one box); 6 waves per SIMD spills (80 VGPRs + scratch: 2x slower).
+// 1025-2048 / 2049-4096 rows likewise on 256 x 8 (5 waves) / 512 x 8 (106 VGPRs, 4
+// waves) instead of 512 x 4 / 1024 x 4: C2's kernel time -5%, its tick -2%.
+template <int G, int R>
+__global__ __launch_bounds__(G, (G <= 256 && R == 8) ? 5 : 1) void k_block(DevParams p, WorkItem* __restrict__ items, int nitems,
+                                             int32_t* general_list, int32_t* general_count) {
+  __shared__ Lds<G> lds;
+  if ((int)blockIdx.x >= nitems) return;
+  group_segment<G, R>(p, items[blockIdx.x], items + blockIdx.x, threadIdx.x, lds, general_list, general_count);
+}
+
+// The workgroup bins split by the dense hint (launch_bin_dense / launch_bin_rest):
+// k_block_dense decides the items whose hint is set without the subclients column
+// (128 x 8: 73 VGPRs, 6 waves per SIMD instead of 5; its steady builds 66 and 7: 14336
+// rows in flight per CU) and queues the others; k_block_rest decides the queue with the
+// mixed body, a grid striding over it (sized from the last split tick's queue; an empty queue costs
+// one small launch).  qcnt is a two-slot ring: this tick's count in qcnt[par], and
+// k_block_rest clears qcnt[par ^ 1] for the next tick (stream order); host_count
+// (host-mapped) tells the host how many items went to the queue (its choice of
+// split or mixed), written only when the count differs from the last one written
+// (qcnt[2]): a system-scope store to host memory keeps an otherwise empty launch
+// alive ~2 us longer, every tick of a dense store.
+// When the host skips k_block_rest (every item of the bin verified dense in this row
+// epoch, dm_runtime.cpp), `guard` (host-mapped) is set should the dense kernel queue
+// an item after all, which the host reports as DM_E_INTERNAL (and refuses the store)
+// instead of leaving the item undecided unnoticed.  The tick's last kernel (this one,
+// or the rest kernel) is launched with the tick's stop event when another queue waits
+// for the tick (dm_runtime.cpp tick_ev).
+// (128 x 8 held to 7 waves per SIMD: 71 VGPRs + 20 B of spill, C3 430 -> 590 us; round 5.)
+// SKIP: the build a writeback tick in place runs (group_segment: unchanged runs of gets
+// are not stored); every other tick runs the build without it.
+// STEADY: the builds for a part the host knows to hold only dense items without released
+// rows or arrivals, outside recompute mode (group_segment: Clean's result is known; an item
+// it is not known for is queued, so the rest kernel follows every steady launch).  As a
+// run-time branch in one build the two bodies need 84-87 VGPRs (5 waves per SIMD).
+template <int G, int R, bool SKIP = false, bool STEADY = false>
+__global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __restrict__ items, int nitems,
+                                                   int32_t* queue, int32_t* qcnt, int par,
+                                                   int32_t* general_list, int32_t* general_count,
+                                                   int32_t* guard) {
+  __shared__ Lds<G> lds;
+  if ((int)blockIdx.x < nitems) {
+    const WorkItem wi = items[blockIdx.x];
+    if ((wi.n >> 16) == 0) {
+      if (threadIdx.x == 0) {
+        const int q = atomicAdd(qcnt + par, 1);
+        if (q < nitems) queue[q] = (int32_t)blockIdx.x;
+        if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    } else {
+      group_segment<G, R, kDenseOnly, SKIP, STEADY>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
+                                                    general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
+                                                    nitems);
+    }
+  }
+}
+
+template <int G, int R>
+__global__ __launch_bounds__(G) void k_block_rest(DevParams p, WorkItem* __restrict__ items,
+                                                  const int32_t* __restrict__ queue, int32_t* qcnt, int par,
+                                                  int32_t* host_count, int32_t* general_list, int32_t* general_count) {
+  __shared__ Lds<G> lds;
+  const int count = qcnt[par];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    qcnt[par ^ 1] = 0;
+    if (host_count && qcnt[2] != count) {
+      __hip_atomic_store(host_count, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      qcnt[2] = count;
+    }
+  }
+  for (int q = blockIdx.x; q < count; q += gridDim.x) {
+    const int idx = queue[q];
+    group_segment<G, R, kRest>(p, items[idx], items + idx, threadIdx.x, lds, general_list, general_count);
+    __syncthreads();  // the next item reuses the single-use LDS slots
+  }
+}
+
+// One workgroup: how many items of a workgroup bin are not dense after a writeback
+// tick, published to host-mapped memory as {count, epoch} (count first, the epoch
+// with release order) -- the host's once-per-epoch check before it skips the bin's
+// k_block_rest (dm_runtime.cpp).  The count word's high half counts the dense items
+// whose hint word carries released rows or arrivals (bits 8, 9): with both halves zero
+// the host may launch the steady builds.
+__global__ __launch_bounds__(1024) void k_count_undense(const WorkItem* __restrict__ items, int n,
+                                                        unsigned long long* rec, unsigned long long epoch) {
+  __shared__ int part[16], part_f[16];
+  int c = 0, f = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int hw = items[i].n >> 16;
+    c += hw == 0 ? 1 : 0;
+    f += (hw >> 8 & 3) != 0 ? 1 : 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_down(c, o, 64);
+    f += __shfl_down(f, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6] = c;
+    part_f[threadIdx.x >> 6] = f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long tot = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w)
+      tot += (unsigned long long)(unsigned)part[w] | (unsigned long long)(unsigned)part_f[w] << 32;
+    __hip_atomic_store(rec, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(rec + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// Sub-wave groups: G = 8, 16 or 32 lanes own one resource of up to G*R rows (R rows
+// per lane), so a wave decides 64 / G resources with one set of reduction chains
+// (DPP inside each 16-lane row, plus one readlane combine for G = 32); G = 64 is one
+// wave per resource (wave reductions only, no barriers).  Small resources are
+// VALU-bound on their per-resource reductions (~28 reduced dwords per pass set, 4 DPP
+// steps each): narrow groups with several rows per lane share every DPP step among
+// 64 / G resources.
+// The sub-wave bins in one launch (k_subs): the workgroups of each bin follow one
+// another in blockIdx order, so the class stream runs them without a kernel boundary
+// (drain + ramp) between bins.  Register use is the largest bin's.
+template <int G, int R>
+__device__ __forceinline__ void sub_part(const DevParams& p, WorkItem* __restrict__ items, int nitems, int blk,
+                                         int32_t* general_list, int32_t* general_count) {
+  Lds<G> lds;  // unused by sub-wave and wave reductions
+  const int i = blk * (256 / G) + (int)(threadIdx.x / G);
+  if (i >= nitems) return;
+  group_segment<G, R>(p, items[i], items + i, threadIdx.x & (G - 1), lds, general_list, general_count);
+}
+
+template <int K>
+__device__ __forceinline__ void sub_shape(const DevParams& p, const SubBins& sb, int b, int32_t* general_list,
+                                          int32_t* general_count) {
+  if constexpr (K < kSubShapes) {
+    if (b < sb.blocks[K])
+      return sub_part<kSubShapeG[K], kSubShapeR[K]>(p, sb.items[K], sb.n[K], b, general_list, general_count);
+    sub_shape<K + 1>(p, sb, b - sb.blocks[K], general_list, general_count);
+  }
+}
+
+__global__ __launch_bounds__(256, 5) void k_subs(DevParams p, SubBins sb, int32_t* general_list,
+                                              int32_t* general_count) {
+  sub_shape<0>(p, sb, (int)blockIdx.x, general_list, general_count);
+}
+
+// --------------------------------------------------------------------------
+// Tiles of small resources (n <= kSmallMax), one 256-thread workgroup per tile
+// (dm_device.h Tile): the workgroup stages the tile's rows in LDS with lane-strided
+// (coalesced) loads while thread k loads resource k's offsets and record (consecutive
+// records: coalesced as well) -- one memory round trip, where the packed kernel waits
+// for its pack, then for the records its rows' resources name.  Thread k then decides
+// resource k literally, in row order (sums in the oracle's order: bit-exact), from LDS;
+// the gets go back to global memory row-parallel (coalesced), and each resource's
+// record from its thread (coalesced).
+// --------------------------------------------------------------------------
+struct TileLds {
+  double w[kTileRows];
+  double h[kTileRows];  // a row's has, then its gets (only the row's own resource thread reads either)
+  int32_t sr[kTileRows];
+  uint8_t lv[kTileRows];
+};
+
+__global__ __launch_bounds__(256) void k_tile_small(DevParams p, const Tile* __restrict__ tiles,
+                                                    const TileEntry* __restrict__ list) {
+  __shared__ TileLds L;
+  const Tile tl = tiles[blockIdx.x];
+  const int t = threadIdx.x;
+  const bool lst = tl.list != 0;  // (uniform)
+  const int nrows = tl.nrows, nseg = tl.nseg;
+  constexpr int K = kTileRows / 256;
+  // the records first, then the rows: every load of the tile is in flight before the
+  // first is consumed (the LDS stores below)
+  const bool own = t < nseg;
+  int seg, ldo = 0;
+  if (lst) {
+    const TileEntry e = list[tl.first_seg + (own ? t : 0)];
+    seg = e.seg;
+    ldo = e.lds;
+  } else {
+    seg = tl.first_seg + (own ? t : 0);
+  }
+  const int64_t lo64 = p.seg_off[seg], hi64 = p.seg_off[seg + 1];
+  // a row's global index is base + its LDS index (a list tile: per resource)
+  const int64_t row0 = lst ? lo64 - ldo : tl.row0;
+  const Res rs = load_res(p, seg);
+  if (lst) {  // each thread its own resource's rows (n <= kSmallMax)
+    const int n = own ? (int)(hi64 - lo64) : 0;
+    double wv[kSmallMax], hv[kSmallMax];
+    int sv[kSmallMax];
+#pragma unroll
+    for (int j = 0; j < kSmallMax; ++j)
+      if (j < n) {
+        wv[j] = p.wants[lo64 + j];
+        hv[j] = p.has[lo64 + j];
+        sv[j] = p.sub[lo64 + j];
+      }
+#pragma unroll
+    for (int j = 0; j < kSmallMax; ++j)
+      if (j < n) {
+        L.w[ldo + j] = wv[j];
+        L.h[ldo + j] = hv[j];
+        L.sr[ldo + j] = sv[j];
+      }
+  } else {
+    double wv[K], hv[K];
+    int sv[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (k * 256 < nrows) {  // uniform
+        const int i = k * 256 + t;
+        const unsigned u = (unsigned)(i < nrows ? i : nrows - 1);
+        wv[k] = *col_at(p.wants + row0, u);
+        hv[k] = *col_at(p.has + row0, u);
+        sv[k] = *col_at(p.sub + row0, u);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = k * 256 + t;
+      if (k * 256 < nrows && i < nrows) {
+        L.w[i] = wv[k];
+        L.h[i] = hv[k];
+        L.sr[i] = sv[k];
+      }
+    }
+  }
+  __syncthreads();
+  if (own) {
+    const int lo = (int)(lo64 - row0), hi = (int)(hi64 - row0);
+    // Clean (store.go:169-181): the store's running sums (or rebuilt from every row in
+    // row order, recompute mode) less the rows that expired, in row order
+    long long count;
+    double sh, sw;
+    if (p.recompute) {
+      count = 0;
+      sh = 0.0;
+      sw = 0.0;
+      for (int q = lo; q < hi; ++q) {
+        sh += L.h[q] - 0.0;
+        sw += L.w[q] - 0.0;
+        count += sub_value(L.sr[q]);
+      }
+    } else {
+      count = rs.agg_count;
+      sh = rs.agg_has;
+      sw = rs.agg_wants;
+    }
+    const bool expl_rows = any_explicit(rs);
+    unsigned live = 0;  // bit q - lo (n <= kSmallMax)
+    for (int q = lo; q < hi; ++q) {
+      const int32_t raw = L.sr[q];
+      int64_t e = rs.follow_exp;
+      if (expl_rows && sub_explicit(raw)) e = p.expiry[row0 + q];
+      if (sub_released(raw)) e = kReleased;
+      const bool lv = !(p.now > e);  // store.go:174
+      live |= (lv ? 1u : 0u) << (q - lo);
+      if (!lv && !sub_released(raw)) {  // expired: Clean releases it (a released row holds zeros)
+        sw -= L.w[q];
+        sh -= L.h[q];
+        count -= sub_value(raw);
+      }
+    }
+    const double C = rs.C;
+    const double eq = C / (double)count;
+    const bool ps = !rs.learning && rs.kind == 2, fs = !rs.learning && rs.kind == 3;
+    double x = 0.0, y = 0.0;
+    long long wi = 0;
+    if (ps || fs) {
+      for (int q = lo; q < hi; ++q) {
+        if (!(live >> (q - lo) & 1)) continue;
+        const double wj = L.w[q];
+        const int sj = sub_value(L.sr[q]);
+        if (ps) {
+          const double e2 = eq * (double)sj;  // algorithm.go:273
+          if (wj < e2)
+            x += e2 - wj;
+          else
+            y += wj - e2;
+        } else {
+          const double d = (double)sj * eq;  // algorithm.go:160
+          if (wj < d)
+            x += d - wj;
+          else if (wj > d)
+            wi += sj;
+        }
+      }
+    }
+    double osh = sh;  // Assign: sumHas += gets - has (store.go:156), row order
+    double Tc = 0.0;  // round 2 at the last threshold asked for (uniform subclients: one per resource)
+    AggC cc{0.0, 0};
+    bool have_c = false;
+    for (int q = lo; q < hi; ++q) {
+      const bool lv = live >> (q - lo) & 1;
+      L.lv[q] = lv ? 1 : 0;
+      if (!p.writeback) __builtin_nontemporal_store(lv ? (int64_t)rs.exp_out : (int64_t)kReleased,
+                                                    col_at(p.out_expiry + row0, (uint32_t)q));
+      if (!lv) {
+        L.h[q] = 0.0;
+        continue;
+      }
+      const double w = L.w[q], h = L.h[q];
+      const int s = sub_value(L.sr[q]);
+      double g;
+      if (rs.learning) {
+        g = h;  // Learn (algorithm.go:297-302)
+      } else if (rs.kind == 0) {
+        g = w;  // NoAlgorithm
+      } else if (rs.kind == 1) {
+        g = minF(C, w);  // Static
+      } else if (ps) {
+        const double epc = eq * (double)s;  // :233
+        const double unused = C - sh + h;   // :239
+        g = (sw <= C || w <= epc) ? minF(w, unused) : minF(epc + (w - epc) * (x / y), unused);
+      } else {
+        double T = 0.0;
+        if (!fs_stage01(w, h, s, C, sh, eq, x, wi, &g, &T)) {
+          if (!have_c || __double_as_longlong(T) != __double_as_longlong(Tc)) {
+            cc = AggC{0.0, 0};
+            for (int j = lo; j < hi; ++j) {  // round 2 at this row's threshold (algorithm.go:189-204)
+              if (!(live >> (j - lo) & 1)) continue;
+              const double wj = L.w[j];
+              const int sj = sub_value(L.sr[j]);
+              if (!(wj > (double)sj * eq)) continue;
+              if (wj < T)
+                cc.ee += T - wj;
+              else if (wj > T)
+                cc.sgt += sj;
+            }
+            Tc = T;
+            have_c = true;
+          }
+          g = fs_stage2(w, h, s, C, sh, eq, x, wi, T, cc);
+        }
+      }
+      L.h[q] = g;
+      osh += g - h;
+    }
+    write_resource(p, seg, rs, Clean{count, osh, sw}, 0.0);
+  }
+  if (lst) {  // a list tile: each thread its own resource's leases
+    if (own) {
+      for (int i = (int)(lo64 - row0); i < (int)(hi64 - row0); ++i) {
+        const int32_t raw = L.sr[i];
+        if (L.lv[i]) {
+          __builtin_nontemporal_store(L.h[i], col_at(p.out_gets + row0, (uint32_t)i));
+          if (p.writeback && raw < 0) *col_at(p.out_sub + row0, (uint32_t)i) = raw & 0x7FFFFFFF;
+        } else {
+          __builtin_nontemporal_store(0.0, col_at(p.out_gets + row0, (uint32_t)i));
+          if (p.writeback && !sub_released(raw)) {
+            *col_at(p.out_wants + row0, (uint32_t)i) = 0.0;
+            *col_at(p.out_sub + row0, (uint32_t)i) = (int32_t)kSubReleased;
+          }
+        }
+      }
+    }
+    return;
+  }
+  __syncthreads();
+  // the leases, row-parallel (put_live / put_released of the packed kernel)
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = k * 256 + t;
+    if (k * 256 < nrows && i < nrows) {
+      const int32_t raw = L.sr[i];
+      if (L.lv[i]) {
+        __builtin_nontemporal_store(L.h[i], col_at(p.out_gets + row0, (uint32_t)i));
+        if (p.writeback && raw < 0) *col_at(p.out_sub + row0, (uint32_t)i) = raw & 0x7FFFFFFF;
+      } else {
+        __builtin_nontemporal_store(0.0, col_at(p.out_gets + row0, (uint32_t)i));
+        if (p.writeback && !sub_released(raw)) {
+          *col_at(p.out_wants + row0, (uint32_t)i) = 0.0;
+          *col_at(p.out_sub + row0, (uint32_t)i) = (int32_t)kSubReleased;
+        }
+      }
+    }
+  }
+}
+
+// --------------------------------------------------------------------------
+// host-side launchers (called by dm_runtime.cpp)
+// --------------------------------------------------------------------------
+hipError_t launch_tile_small(const DevParams& p, const Tile* tiles, const TileEntry* list, int n, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_tile_small<<<n, 256, 0, st>>>(p, tiles, list);
+  return hipGetLastError();
+}
+
+// The workgroup bins' shapes, G threads x R rows per thread: the one list behind every
+// per-bin launcher.  Calls f(integral_constant<int, G>, integral_constant<int, R>);
+// false: no such bin.
+template <int G, int R, typename F>
+bool as_bin_shape(F& f) {
+  f(std::integral_constant<int, G>{}, std::integral_constant<int, R>{});
+  return true;
+}
+template <typename F>
+bool with_bin_shape(int bin, F&& f) {
+  switch (bin) {
+    case 3: return as_bin_shape<128, 4>(f);
+    case 4: return as_bin_shape<128, 8>(f);
+    case kBin4Wave: return as_bin_shape<64, 16>(f);
+    case 5: return as_bin_shape<256, 8>(f);
+    case 6: return as_bin_shape<256, 16>(f);
+    case kBin6Wide: return as_bin_shape<512, 8>(f);
+    default: return false;
+  }
+}
+// f(bool_constant<B>) for a runtime b
+template <typename F>
+void with_bool(bool b, F&& f) {
+  if (b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+// the workgroup bins (3-6) in their one-kernel form; the sub-wave bins run in k_subs
+hipError_t launch_bin(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* glist, int32_t* gcount,
+                      hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    k_block<G, R><<<n, G, 0, st>>>(p, segs, n, glist, gcount);
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, int32_t* gcount, hipStream_t st) {
+  unsigned blocks = 0;
+  for (int k = 0; k < kSubShapes; ++k) blocks += (unsigned)sb.blocks[k];
+  if (blocks == 0) return hipSuccess;
+  k_subs<<<blocks, 256, 0, st>>>(p, sb, glist, gcount);
+  return hipGetLastError();
+}
+
+// The 128-thread bins (3: 128 x 4, 4: 128 x 8) split by the dense hint: the dense
+// kernel over every item, then the rest kernel over what it queued (two launches,
+// timed separately).
+// done (optional): an event the launch itself completes (hipExtLaunchKernel's stop
+// event: no marker packet of its own on the queue), for another stream to wait on
+// steady: the builds that take Clean's result as known and queue every item it is not
+// known for (group_segment STEADY); the caller launches the rest kernel after them.
+hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
+                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
+                            hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)n);
+  // in place (the gets go to the column the has came from): the build that skips unchanged runs
+  const bool skip = p.writeback && p.out_gets == p.has;
+  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    with_bool(skip, [&](auto sk) {
+      with_bool(steady, [&](auto sd) {
+        hipExtLaunchKernelGGL((k_block_dense<G, R, decltype(sk)::value, decltype(sd)::value>), grid, dim3(G), 0, st,
+                              nullptr, done, 0, p, segs, n, queue, qcnt, par, glist, gcount, guard);
+      });
+    });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,
+                                hipStream_t st) {
+  k_count_undense<<<1, 1024, 0, st>>>(items, n, rec, epoch);
+  return hipGetLastError();
+}
+
+hipError_t launch_bin_rest(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
+                           int32_t* host_count, int rest_grid, int32_t* glist, int32_t* gcount, hipEvent_t done,
+                           hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const dim3 rg((unsigned)std::max(1, std::min(n, rest_grid)));
+  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    hipExtLaunchKernelGGL((k_block_rest<G, R>), rg, dim3(G), 0, st, nullptr, done, 0, p, segs, queue, qcnt, par,
+                          host_count, glist, gcount);
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+}  // namespace dm

@@ -1,0 +1,429 @@
+// dm_update.hip — the store-update kernels: validation, upsert, release, wants updates
+// (by row list and by mask), and the lease read-back gathers.
+#include <hip/hip_runtime.h>
+
+#include "dm_kernel_util.h"
+#include "dm_launch.h"
+#include "dm_update_util.h"
+
+namespace dm {
+
+// --------------------------------------------------------------------------
+// store maintenance
+// --------------------------------------------------------------------------
+// Assign on existing rows (store.go:153-167): running sums += new - old.
+// Rows of one call may hit the same resource, so the deltas reach the sums
+// through atomics — one per run of a resource within a wave (wave_seg_add,
+// dm_update_util.h, with seg_of_row and the dense-state helpers).
+
+// Validation of one store-update call on the device (no O(n) host pass): rows in
+// range and unique within the call (a row bitmap, all-zero between calls), and
+// the value flags the planner needs.  The apply kernels run only if no error bit
+// is set, so a rejected call leaves the store untouched.
+__global__ void k_check_rows(int64_t n, const int64_t* __restrict__ rows, int64_t N, uint32_t* bitmap,
+                             const double* __restrict__ wants, const int64_t* __restrict__ sub,
+                             const int32_t* __restrict__ sub32, uint32_t* flags) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t f = 0;
+  if (i < n) {
+    const int64_t r = rows[i];
+    if (r < 0 || r >= N) {
+      f |= kUpdRange;
+    } else {
+      const uint32_t bit = 1u << (r & 31);
+      if (atomicOr(&bitmap[r >> 5], bit) & bit) f |= kUpdDup;
+    }
+    if (wants && __builtin_isnan(wants[i])) f |= kUpdNaN;
+    if (sub || sub32) {
+      const int64_t v = sub32 ? (int64_t)sub32[i] : sub[i];
+      if (v < 0 || v > kSubMax) f |= kUpdSub;
+      if (v != 1) f |= kUpdNotOne;
+    }
+  }
+  // one atomic per wave and flag value
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(f);
+  if (__all(f == lo)) {
+    if ((threadIdx.x & 63) == 0 && lo) atomicOr(flags, lo);
+  } else if (f) {
+    atomicOr(flags, f);
+  }
+}
+
+// Return the bitmap words of this call's rows to zero.
+__global__ void k_clear_rows(int64_t n, const int64_t* __restrict__ rows, int64_t N, uint32_t* bitmap) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rows[i];
+  if (r >= 0 && r < N) bitmap[r >> 5] = 0u;
+}
+
+// Narrow arrivals (dm_store_batch): has == nullptr -> 0; sub32 instead of sub;
+// expiry == nullptr -> the resource's now + lease length (the Assign's expiry,
+// store.go:161).
+__global__ void k_upsert(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ has,
+                         const double* __restrict__ wants, const int64_t* __restrict__ sub,
+                         const int32_t* __restrict__ sub32, const int64_t* __restrict__ expiry,
+                         const ResCfg* __restrict__ cfg, int64_t now, RowIndex ix, double* s_has, double* s_wants,
+                         int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
+                         DenseUpd du) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (*flags & kUpdReject) return;  // uniform over the grid
+  const bool active = i < n;
+  int seg = 0;
+  double dh = 0.0, dw = 0.0;
+  long long ds = 0;
+  if (active) {
+    const int64_t r = rows[i];
+    seg = seg_of_row(ix, r);
+    const double hv = has ? has[i] : 0.0;
+    const int64_t sv = sub32 ? (int64_t)sub32[i] : sub[i];
+    dh = hv - s_has[r];
+    dw = wants[i] - s_wants[r];
+    ds = sv - sub_value(s_sub[r]);
+    s_has[r] = hv;
+    s_wants[r] = wants[i];
+    s_sub[r] = (int32_t)((uint32_t)sv | kSubExplicit);  // in [0, kSubMax] (k_check_rows); expiry explicit
+    const int64_t ex = expiry ? expiry[i] : now + (int64_t)cfg[seg].lease_len_s * kNs;
+    s_exp[r] = ex;
+    // an arrival with the dense resource's count and the Assign's expiry, not before the
+    // followers': the resource stays dense, the row goes into its arrival mask
+    MaskPos mp;
+    WorkItem* it;
+    const uint8_t st = expl[seg];
+    if (!expiry && dense_row(du, ix, seg, r, st, &mp, &it) && sv == (int64_t)st - 1 && ex >= agg[seg].follow_exp) {
+      mask_bit(du.rmask + rel_mask_offset(ix.seg_off[seg]), mp.roff, mp.rbit, false);
+      mask_bit(du.rmask + rel_mask_offset(ix.seg_off[seg]), mp.aoff, mp.abit, true);
+      atomicOr(&it->n, 1 << 25);
+    } else {
+      expl[seg] = 1;  // the tick reads this resource's expiry column again
+    }
+  }
+  wave_seg_add(agg, active, seg, dh, dw, ds, true, true);
+}
+
+__global__ void k_release(int64_t n, const int64_t* __restrict__ rows, RowIndex ix, double* s_has, double* s_wants,
+                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
+                          DenseUpd du) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (*flags & kUpdReject) return;  // uniform over the grid
+  const bool active = i < n;
+  int seg = 0;
+  double dh = 0.0, dw = 0.0;
+  long long ds = 0;
+  if (active) {
+    const int64_t r = rows[i];
+    seg = seg_of_row(ix, r);
+    (void)s_exp;
+    release_row(ix, seg, r, s_has, s_wants, s_sub, expl, du, &dh, &dw, &ds);
+  }
+  wave_seg_add(agg, active, seg, dh, dw, ds, true, true);
+}
+
+// Narrow Assign for a refresh that only changes wants (store.go:157):
+// sumWants += new - old.  Rows are unique within one call.
+// A released row is a free slot, not a client: a refresh of it changes nothing (a
+// returning client is an arrival, dm_store_upsert).  Written into it, the wants would
+// be subtracted from the resource's running sum by every later tick's Clean.
+__global__ void k_update_wants(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ wants,
+                               RowIndex ix, const int32_t* __restrict__ s_sub, double* s_wants, ResAgg* agg,
+                               const uint32_t* flags) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (*flags & kUpdReject) return;  // uniform over the grid
+  const bool active = i < n;
+  int seg = 0;
+  double d = 0.0;
+  if (active) {
+    const int64_t r = rows[i];
+    seg = seg_of_row(ix, r);
+    if (!sub_released(s_sub[r])) {
+      d = wants[i] - s_wants[r];
+      s_wants[r] = wants[i];
+    }
+  }
+  wave_seg_add(agg, active, seg, 0.0, d, 0, false, false);
+}
+
+// ---- wants updates as a row mask + packed values (dm_store_update_wants_mask) ----
+// Bit j of word w is row first_row + 64 w + j; the set rows take the packed values
+// in ascending row order.  At 10% of the rows updated this moves 1.25 B of mask
+// per update over PCIe instead of an 8-B row index (C4: 116 instead of 200 MB).
+struct OpAddI64 {
+  __device__ long long operator()(long long a, long long b) const { return a + b; }
+};
+// Pass 1: popcount per 256-word block (+ rows past the store's end), and every
+// word's exclusive offset within its block.
+__global__ __launch_bounds__(256) void k_mask_count(int64_t nwords, const uint64_t* __restrict__ mask,
+                                                    int64_t first_row, int64_t N, int64_t* block_sums,
+                                                    int32_t* word_pre, uint32_t* flags) {
+  __shared__ int part[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t m = w < nwords ? mask[w] : 0ull;
+  const int64_t row0 = first_row + 64 * w;
+  if (m && row0 + 63 >= N) {  // bits of rows >= N
+    const int64_t keep = N - row0;  // < 64
+    const uint64_t ok = keep <= 0 ? 0ull : ((1ull << keep) - 1ull);
+    if (m & ~ok) atomicOr(flags, kUpdRange);
+  }
+  const int c = __popcll(m);
+  int incl = c;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) part[wave] = incl;
+  __syncthreads();
+  int pre = incl - c;
+  for (int i = 0; i < wave; ++i) pre += part[i];
+  if (w < nwords) word_pre[w] = pre;
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = (int64_t)part[0] + part[1] + part[2] + part[3];
+}
+
+// Pass 2 (one workgroup): exclusive scan of the block sums in place; the total
+// must equal the number of packed values.
+__global__ __launch_bounds__(1024) void k_mask_scan(int64_t nblocks, int64_t* block_sums, int64_t n_values,
+                                                    uint32_t* flags) {
+  __shared__ int64_t tot[1024];
+  const int t = threadIdx.x;
+  const int64_t per = (nblocks + 1023) / 1024;
+  const int64_t b0 = t * per < nblocks ? t * per : nblocks;
+  const int64_t b1 = b0 + per < nblocks ? b0 + per : nblocks;
+  int64_t s = 0;
+  for (int64_t b = b0; b < b1; ++b) s += block_sums[b];
+  tot[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {  // inclusive Hillis-Steele scan of the 1024 partials
+    const int64_t v = t >= o ? tot[t - o] : 0;
+    __syncthreads();
+    tot[t] += v;
+    __syncthreads();
+  }
+  int64_t run = tot[t] - s;
+  for (int64_t b = b0; b < b1; ++b) {
+    const int64_t v = block_sums[b];
+    block_sums[b] = run;
+    run += v;
+  }
+  if (t == 1023 && tot[1023] != n_values) atomicOr(flags, kUpdCount);
+}
+
+// Pass 3: one lane per row; a wave takes kMaskWords consecutive mask words (64
+// rows each).  Lane q first fetches word q, its first value's offset and the
+// resource of its first row (all words in parallel); then every row's loads of
+// every word are issued before any is consumed (coalesced: per word the wave reads
+// its packed values and 512 B of the wants column).  A resource's deltas stay in
+// per-lane registers while consecutive words lie inside it and leave with one
+// reduction + atomic when the resource changes; a word that spans resources adds
+// its runs directly (wave_seg_add).
+constexpr int kMaskWords = 16;
+__global__ __launch_bounds__(256) void k_mask_apply(int64_t nwords, const uint64_t* __restrict__ mask,
+                                                    int64_t first_row, const int64_t* __restrict__ block_offs,
+                                                    const int32_t* __restrict__ word_pre,
+                                                    const double* __restrict__ wants, RowIndex ix,
+                                                    const int32_t* __restrict__ s_sub, double* s_wants, ResAgg* agg,
+                                                    uint32_t* flags, int64_t vlo, int64_t vhi) {
+  if (*flags & kUpdReject) return;  // uniform over the grid
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kMaskWords;
+  if (w0 >= nwords) return;  // whole waves
+  const int nw = nwords - w0 < kMaskWords ? (int)(nwords - w0) : kMaskWords;
+  uint64_t my_m = 0ull;
+  int64_t my_off = 0, my_end = 0;
+  if (lane < nw) {
+    const int64_t w = w0 + lane;
+    my_m = mask[w];
+    my_off = block_offs[w >> 8] + word_pre[w];
+  }
+  // only the values [vlo, vhi) have landed (dm_store_apply copies them in chunks): a
+  // wave whose words' values all lie outside is done
+  {
+    const int64_t first = readlane_any(my_off, 0);
+    const int64_t last = readlane_any(my_off, nw - 1) + __popcll(readlane_any(my_m, nw - 1));  // one past
+    if (last <= vlo || first >= vhi) return;
+  }
+  int my_seg = 0;
+  if (lane < nw) {
+    my_seg = seg_of_row(ix, first_row + 64 * (w0 + lane));
+    my_end = ix.seg_off[my_seg + 1];  // the word lies in one resource iff its last row < my_end
+  }
+  const uint64_t below = (1ull << lane) - 1ull;
+  uint32_t inr = 0;  // bit q: this lane's row of word q is set and its value in [vlo, vhi)
+  double v[kMaskWords], old[kMaskWords];
+  uint32_t freed = 0;  // bit q: this lane's row of word q is released (k_update_wants: left alone)
+#pragma unroll
+  for (int q = 0; q < kMaskWords; ++q) {  // every load in flight before the first use
+    v[q] = 0.0;
+    old[q] = 0.0;
+    if (q < nw) {
+      const uint64_t m = readlane_any(my_m, q);
+      const int64_t vi = readlane_any(my_off, q) + __popcll(m & below);
+      if (((m >> lane) & 1ull) && vi >= vlo && vi < vhi) {
+        inr |= 1u << q;
+        v[q] = wants[vi];
+        old[q] = s_wants[first_row + 64 * (w0 + q) + lane];
+        freed |= (sub_released(s_sub[first_row + 64 * (w0 + q) + lane]) ? 1u : 0u) << q;
+      }
+    }
+  }
+  int cur = -1;      // resource whose deltas `acc` holds (uniform)
+  double acc = 0.0;  // this lane's share of them
+  bool nan = false;
+#pragma unroll
+  for (int q = 0; q < kMaskWords; ++q) {
+    const uint64_t m = q < nw ? readlane_any(my_m, q) : 0ull;
+    if (m != 0ull) {  // uniform
+      const int64_t row0 = first_row + 64 * (w0 + q);
+      const bool act = (inr >> q & 1u) && !(freed >> q & 1u);
+      const int s0 = __builtin_amdgcn_readlane(my_seg, q);
+      const bool single = readlane_any(my_end, q) > row0 + 63 - __builtin_clzll(m);
+      double d = 0.0;
+      int seg = s0;
+      if (act) {
+        const int64_t r = row0 + lane;
+        nan |= __builtin_isnan(v[q]);
+        if (!single)
+          while (ix.seg_off[seg + 1] <= r) ++seg;
+        d = v[q] - old[q];
+        s_wants[r] = v[q];
+      }
+      if (single && s0 == cur) {
+        acc += d;
+      } else {
+        if (cur >= 0) {  // flush the previous resource
+          const double t = wave_reduce(acc, [](double a, double b) { return a + b; });
+          if (lane == 0) atomicAdd(&agg[cur].sum_wants, t);
+        }
+        if (single) {
+          cur = s0;
+          acc = d;
+        } else {
+          cur = -1;
+          acc = 0.0;
+          wave_seg_add(agg, act, seg, 0.0, d, 0, false, false);
+        }
+      }
+    }
+  }
+  if (cur >= 0) {
+    const double t = wave_reduce(acc, [](double a, double b) { return a + b; });
+    if (lane == 0) atomicAdd(&agg[cur].sum_wants, t);
+  }
+  if (__ballot(nan) && lane == 0) atomicOr(flags, kUpdNaN);
+}
+
+// dm_store_apply: a part is applied only if no earlier part was rejected.
+__global__ void k_carry_reject(const uint32_t* __restrict__ from, uint32_t* to) { *to |= *from & kUpdReject; }
+
+// gets / expiry of scattered rows (dm_read_leases_rows)
+// Rows as the store holds them (dm_device.h encoding), for the host: the expiry of
+// row r (a follower's is its resource's follow_exp) and its subclients value.
+// rows == nullptr: rows off .. off+n-1.
+__global__ void k_resolve_rows(int64_t n, const int64_t* __restrict__ rows, int64_t off, const int32_t* __restrict__ sub,
+                               const int64_t* __restrict__ expiry, RowIndex ix, const ResAgg* __restrict__ agg,
+                               int64_t* out_exp, int64_t* out_sub) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rows ? rows[i] : off + i;
+  const int32_t raw = sub[r];
+  int64_t e;
+  if (sub_released(raw))
+    e = kReleased;
+  else if (raw < 0)
+    e = expiry[r];
+  else
+    e = agg[seg_of_row(ix, r)].follow_exp;
+  if (out_exp) out_exp[i] = e;
+  if (out_sub) out_sub[i] = sub_value(raw);
+}
+
+__global__ void k_gather_leases(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ gets,
+                                const int64_t* __restrict__ expiry, double* out_gets, int64_t* out_exp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rows[i];
+  out_gets[i] = gets[r];
+  if (expiry) out_exp[i] = expiry[r];  // else resolved by k_resolve_rows
+}
+
+// --------------------------------------------------------------------------
+// host-side launchers (called by dm_runtime.cpp)
+// --------------------------------------------------------------------------
+hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
+                         const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
+                         const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
+                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_upsert<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, cfg, now, ix, s_has,
+                                                        s_wants, s_sub, s_exp, agg, expl, flags, du);
+  return hipGetLastError();
+}
+
+hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
+                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
+                          const DenseUpd& du, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_release<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, ix, s_has, s_wants, s_sub, s_exp, agg, expl, flags,
+                                                         du);
+  return hipGetLastError();
+}
+
+hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
+                               const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
+                               hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_update_wants<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, wants, ix, s_sub, s_wants, agg, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_resolve_rows(int64_t n, const int64_t* rows, int64_t off, const int32_t* sub, const int64_t* expiry,
+                               const RowIndex& ix, const ResAgg* agg, int64_t* out_exp, int64_t* out_sub,
+                               hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_resolve_rows<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, off, sub, expiry, ix, agg, out_exp, out_sub);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_leases(int64_t n, const int64_t* rows, const double* gets, const int64_t* expiry,
+                               double* out_gets, int64_t* out_exp, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_gather_leases<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, gets, expiry, out_gets, out_exp);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, const double* wants,
+                             const int64_t* sub, const int32_t* sub32, uint32_t* flags, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_check_rows<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, N, bitmap, wants, sub, sub32, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  k_clear_rows<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, N, bitmap);
+  return hipGetLastError();
+}
+
+hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
+                                    int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
+                                    const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
+                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi) {
+  if (nwords <= 0) return hipSuccess;
+  const int64_t nb = (nwords + 255) / 256;
+  if (phase != 1) {  // the mask's counts and value offsets (the mask alone)
+    k_mask_count<<<(unsigned)nb, 256, 0, st>>>(nwords, mask, first_row, N, block_sums, word_pre, flags);
+    k_mask_scan<<<1, 1024, 0, st>>>(nb, block_sums, n_values, flags);
+  }
+  if (phase != 0) {  // the rows whose values [vlo, vhi) have landed
+    const int64_t waves = (nwords + kMaskWords - 1) / kMaskWords;
+    k_mask_apply<<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, ix,
+                                                              s_sub, s_wants, agg, flags, vlo, vhi);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_carry_reject(const uint32_t* from, uint32_t* to, hipStream_t st) {
+  k_carry_reject<<<1, 1, 0, st>>>(from, to);
+  return hipGetLastError();
+}
+
+}  // namespace dm

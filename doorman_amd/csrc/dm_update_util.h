@@ -1,5 +1,5 @@
 // Device helpers shared by the kernels that change stored rows outside a tick: the store
-// updates (dm_kernels.hip), the re-layout (dm_relayout.hip) and Clean (dm_clean.hip).
+// updates (dm_update.hip), the re-layout (dm_relayout.hip) and Clean (dm_clean.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

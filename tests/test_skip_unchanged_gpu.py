@@ -1,4 +1,4 @@
-"""The dense kernels' skip of unchanged gets stores (dm_kernels.hip group_segment) and the
+"""The dense kernels' skip of unchanged gets stores (dm_tick_group.hip group_segment) and the
 column rule that lets it engage (dm_apportion: in place unless the caller asks for the
 alternate column, the speculative chain may run, or -- on a store beyond the Infinity
 Cache -- a call wrote rows since the last writeback tick).

@@ -1,4 +1,4 @@
-"""The steady builds of the dense tick kernel (dm_kernels.hip group_segment STEADY,
+"""The steady builds of the dense tick kernel (dm_tick_group.hip group_segment STEADY,
 dm_runtime.cpp's launch policy).
 
 A bin part whose items are all dense, none with a released row or an arrival, runs outside
