@@ -1,0 +1,772 @@
+// dm_ctx.h — what the host units of the runtime share: the context (one per GPU: the
+// device-resident columnar lease store, its dispatch plan, streams and policy state), the
+// types that own its device memory, pinned host memory and events, the entry macros of
+// the C-ABI calls, and the functions that cross a unit boundary.  The only definition of
+// dm_ctx; the units around it are dm_runtime.cpp (context life, streams, profiling),
+// dm_plan.cpp, dm_tick.cpp, dm_decide.cpp, dm_store.cpp, dm_store_update.cpp and
+// dm_hier_host.cpp.  See DESIGN.md §3-§5.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>  // types only: librccl is loaded when the first communicator is made
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/doorman_hip.h"
+#include "dm_device.h"
+#include "dm_launch.h"
+
+namespace dm {
+
+// the thread's last error, for calls that have no context to keep it in (dm_last_error(NULL))
+void set_last_error(const std::string& msg);
+
+// kernel classes for profiling
+enum KClass {
+  KC_SMALL = 0,
+  KC_BIN0,  // wave64 .. 256x16
+  KC_LARGE_A = KC_BIN0 + kNumBins,
+  KC_LARGE_B,
+  KC_LARGE_C,
+  KC_LARGE_MAP,
+  KC_LARGE_FIN,
+  KC_GENERAL,
+  KC_UPSERT,
+  KC_RELEASE,
+  KC_SUBS,
+  KC_DENSE3,  // the workgroup bins' split form (bins 3-6): dense kernel, then the rest kernel
+  KC_DENSE4,
+  KC_DENSE5,
+  KC_DENSE6,
+  KC_REST3,
+  KC_REST4,
+  KC_REST5,
+  KC_REST6,
+  KC_PUBLISH,   // dm_publish_totals
+  KC_HIER_ROOT, // dm_hier_root_tick
+  KC_LARGE_T,   // heterogeneous FairShare on the chain: thresholds,
+  KC_LARGE_CH,  // bucket partials,
+  KC_LARGE_E,   // bucket totals,
+  KC_LARGE_MH,  // the map
+  KC_DECIDE,    // dm_decide: the round's device work (fast path + k_decide)
+  KC_LARGE_SPEC, // the speculative chain: k_large_spec,
+  KC_LARGE_REDO, // k_large_redo
+  KC_HIER_GATHER, // dm_hier_step's gather of the servers' blocks (ncclAllGather, or a rehearsal's copy)
+  KC_COUNT
+};
+// bin 6 (2049-4096 rows) runs on 256 x 16 or 512 x 8 workgroups (kBin6Wide):
+// "block2k4k" names the bin, dm_plan_info says which shape ran
+inline const char* const kClassNames[KC_COUNT] = {
+                                     "small_tiles",  "sub16x4",    "sub32x4",    "wave64x4",   "block128x4",
+                                     "block128x8",   "block256x8", "block2k4k",  "sub8x2",    "sub16x2",
+                                     "large_a",      "large_b",
+                                     "large_c",      "large_map",  "large_fin",  "general",    "store_upsert",
+                                     "store_release", "subs_merged", "block128x4_dense",
+                                     "block128x8_dense", "block256x8_dense", "block2k4k_dense",
+                                     "block128x4_rest", "block128x8_rest", "block256x8_rest", "block2k4k_rest",
+                                     "hier_publish",
+                                     "hier_root", "large_t", "large_c_het", "large_e", "large_map_het", "decide",
+                                     "large_spec", "large_redo", "hier_gather"};
+
+// The owners below free what they hold when their holder goes: a context's members with
+// the `delete c` that ends dm_destroy (after every stream has been drained), a local with
+// its scope.  None can be copied (the static_asserts after each).
+
+// Device memory.  Move-only: std::swap exchanges two buffers (the ping-pong columns, the
+// template slots, a re-layout's fresh table).
+template <typename T>
+struct DBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  DBuf(DBuf&& o) noexcept : p(o.p), n(o.n) {
+    o.p = nullptr;
+    o.n = 0;
+  }
+  DBuf& operator=(DBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      n = o.n;
+      o.p = nullptr;
+      o.n = 0;
+    }
+    return *this;
+  }
+  ~DBuf() { release(); }
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+    if (count == 0) return hipSuccess;
+    hipError_t e = hipMalloc(&p, count * sizeof(T));
+    if (e == hipSuccess) n = count;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+};
+static_assert(!std::is_copy_constructible<DBuf<int>>::value && !std::is_copy_assignable<DBuf<int>>::value &&
+                  std::is_nothrow_move_constructible<DBuf<int>>::value &&
+                  std::is_nothrow_move_assignable<DBuf<int>>::value,
+              "a device buffer has one owner: moved (std::swap), never copied");
+
+// Host memory from hipHostMalloc: p is the plain host pointer every call site reads
+// through, d the device's pointer to the same words when the allocation is mapped
+// (hipHostMallocMapped), else nullptr.
+template <typename T>
+struct HBuf {
+  T* p = nullptr;
+  T* d = nullptr;
+  HBuf() = default;
+  HBuf(const HBuf&) = delete;
+  HBuf& operator=(const HBuf&) = delete;
+  ~HBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  hipError_t alloc(size_t count, unsigned flags) {
+    hipError_t e = hipHostMalloc((void**)&p, count * sizeof(T), flags);
+    if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer((void**)&d, p, 0);
+    return e;
+  }
+};
+static_assert(!std::is_copy_constructible<HBuf<int>>::value && !std::is_copy_assignable<HBuf<int>>::value,
+              "a host allocation has one owner");
+
+// An event a context keeps for its whole life (created in dm_create); reads as the
+// hipEvent_t it holds.  The profiling pool's and the queue calibration's events come and
+// go with their use and are not of this kind.
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&ev, flags); }
+  operator hipEvent_t() const { return ev; }
+};
+static_assert(!std::is_copy_constructible<Event>::value && !std::is_copy_assignable<Event>::value,
+              "an event has one owner");
+
+struct ProfEvent {
+  int cls;
+  hipEvent_t a, b;
+};
+
+}  // namespace dm
+
+using namespace dm;
+
+struct dm_ctx {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  // auxiliary streams: independent size bins of one tick run concurrently
+  static constexpr int kAux = 4;
+  // auxiliary stream of each work class: bins 0..kNumBins-1, small tiles, large chain
+  // (round 4 moved every bin to each other stream in A/Bs: this split won every one)
+  // (round 5, with the small tiles: bin 3 on stream 3 112.8-117.3 us, on stream 1
+  // 112.8-114.2, bin 6 on stream 3 127-129, against 111.0-112.4 us; profiles/r05_c2_classes.md)
+  static constexpr int kClassStream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};  // C2: 200 -> 189 us (small class alone)
+  // this store's assignment (plan_streams): kClassStream, except that on a store that
+  // leaves some auxiliary stream without work, classes that would share a stream move
+  // onto the idle ones (a shard of a Zipf population holds only some classes)
+  int class_stream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};
+  int64_t h_shape_lo[kSubShapes] = {}, h_shape_n[kSubShapes] = {};  // sub-wave shapes' items within their bins
+  hipStream_t aux[kAux] = {};
+  bool aux_own_queue = false;  // each auxiliary stream has a hardware queue of its own (CU mask)
+  uint64_t aux_seq = 0;        // the stream set's creation order in the process (take_aux)
+  hipStream_t cpy = nullptr;  // store-update column copies (overlap a running tick)
+  Event ev_stage[2];  // staged update copies -> per-chunk validation
+  // Cross-stream order between the context's streams (fork / join of a tick's work
+  // classes, the pipelined hierarchy's template slots, dm_stream_wait): an event
+  // recorded on the producing stream and waited on by the consuming one.  An event wait
+  // idles the consuming queue ~12-20 us on the box (tools/xs_probe.py); stream-memory
+  // tokens (hipStreamWriteValue64 / WaitValue64, which this ROCm runs as blit kernels
+  // of 3-5 us each plus a dispatch gap) measured no cheaper per step (round 4: 75.0 vs
+  // 72.2 us per N = 8 shard step) and were retired in round 5, as was the tick-done
+  // word (the tick's last kernels' stop events replaced it: tick_ev below).  A wait on
+  // a token signalled on the waiting stream itself is skipped (stream order).
+  static constexpr int kTplSlots = 4;  // staged templates: in use + pending (lag 2) + the one being written
+  enum : int {
+    XS_FORK = 0,
+    XS_JOIN0 = 1,                       // + aux stream
+    XS_READY0 = XS_JOIN0 + kAux,        // + template slot: the root round wrote it
+    XS_FREE0 = XS_READY0 + kTplSlots,   // + template slot: the ticks that read it are done
+    XS_LEAF = XS_FREE0 + kTplSlots,     // leaf stream -> the root round's stream
+    XS_ROOT,                            // root stream -> the leaf (unpipelined, separate streams)
+    XS_EXT,                             // dm_stream_wait
+    XS_N
+  };
+  struct XsTok {
+    int w = 0;
+    hipStream_t s = nullptr;  // the stream it was signalled on
+    bool rec = false;         // recorded (else the wait records on s first: lazy signal)
+  };
+  // A pipelined leaf's staged templates from another stream: the host waits for the
+  // exchange that made them and the leaf's stream gets no barrier (a queue waiting on
+  // another queue here costs ~12-16 us even when the signal is long set -- the step of
+  // an N = 8 shard idled that long every tick, tools/step_trace.py); the host stays at
+  // most ~one step ahead, the device never waits.
+  Event xs_ev[XS_N];
+  hipError_t xs_signal(int w, hipStream_t s, XsTok* tok) {
+    tok->w = w;
+    tok->s = s;
+    tok->rec = true;
+    return hipEventRecord(xs_ev[w], s);
+  }
+  // A signal recorded only if a wait on another stream needs it, then at that wait:
+  // it orders after everything the signalling stream holds by then (never less than
+  // at signal time), and a same-stream consumer costs nothing.
+  void xs_signal_lazy(int w, hipStream_t s, XsTok* tok) {
+    tok->w = w;
+    tok->s = s;
+    tok->rec = false;
+  }
+  hipError_t xs_wait(const XsTok& tok, hipStream_t s) {
+    if (tok.s == s || tok.s == nullptr) return hipSuccess;  // same stream, or known complete
+    if (!tok.rec) return xs_order(tok.w, tok.s, s);
+    return hipStreamWaitEvent(s, xs_ev[tok.w], 0);
+  }
+  hipError_t xs_order(int w, hipStream_t from, hipStream_t to) {
+    if (from == to) return hipSuccess;
+    XsTok t;
+    hipError_t e = xs_signal(w, from, &t);
+    return e == hipSuccess ? xs_wait(t, to) : e;
+  }
+  std::string err;
+
+  int64_t R = 0, N = 0;
+  bool store_loaded = false, cfg_loaded = false;
+  // A device-side invariant failed (a redo workgroup gave up waiting, a dense kernel
+  // queued an item on a tick that skipped its rest kernel: the host-mapped words
+  // below).  The tick that tripped it may have written wrong leases and sums into the
+  // store, so every call that reads, updates or ticks the store refuses it from then
+  // on (DM_E_INTERNAL) until dm_store_load replaces it.
+  bool store_lost = false;
+  std::string lost_msg;
+  // the store may hold explicit-expiry rows: set by every call that can write one
+  // (load, upserts, decide, the root's tick), cleared by a writeback tick (which
+  // turns every live explicit row into a follower).  Without them pass A's
+  // speculative round 1 is exact and pass B runs one workgroup per large resource.
+  bool expl_rows = true;
+  // the last call that changed the store was a writeback tick through the chain
+  // (Partials::s_live): cleared at the start of every tick and by every call that
+  // writes a subclients word or releases a row
+  bool chain_live_ok = false;
+  // Row epoch: bumped by every call that writes rows (loads, plans, upserts, releases,
+  // wants refreshes, decide, the root's tick) -- never by a tick.  Within one epoch a
+  // writeback tick leaves every dense workgroup-bin resource dense (dm_tick_group.hip),
+  // so a bin verified all-dense once in the epoch (k_count_undense) can skip its
+  // k_block_rest: nothing can be queued.
+  uint64_t row_epoch = 1;
+  void rows_changed() {
+    chain_live_ok = false;
+    row_epoch += 1;
+  }
+  std::vector<int64_t> h_seg_off;
+  std::vector<int64_t> h_refresh_s;
+
+  // lease table
+  DBuf<int64_t> seg_off;
+  DBuf<int32_t> blk_seg;  // RowIndex coarse index
+  RowIndex row_index() const { return RowIndex{seg_off.p, blk_seg.p, R}; }
+  DBuf<double> wants, has;
+  DBuf<int32_t> sub;  // subclients, 4 B per lease on the device (the ABI carries int64)
+  DBuf<int64_t> expiry;
+  // running sums + the followers' expiry, AoS (32 B)
+  DBuf<ResAgg> agg;
+  DBuf<uint8_t> expl;  // per resource: rows may carry explicit expiries (DevParams::expl)
+  DBuf<uint8_t> rmask;  // released-row masks of dense workgroup-bin resources (DevParams::rmask)
+  DBuf<int32_t> item_of;  // [R]: bin << 24 | item index for bins 3-6, else -1 (DenseUpd)
+  // config, AoS: what every tick reads (32 B), and the rest (safe capacity, refresh)
+  DBuf<ResCfg> cfg;
+  DBuf<ResCold> cold;
+  // outputs of a non-writeback tick
+  DBuf<double> out_gets;
+  DBuf<int64_t> out_expiry;
+  DBuf<ResAgg> res;
+  bool last_writeback = false, have_result = false;
+  int wb_inplace = -1;  // the store's last writeback tick wrote the has column (1) or the alternate one (0)
+  uint64_t wb_epoch = 0;  // row_epoch at the last writeback tick (0: none yet)
+  // the workgroup bins' items carry dense hints: set by a writeback tick, kept by the
+  // store updates (which keep a dense resource's state or end it: DenseUpd), cleared by
+  // a new store
+  bool hints_set = false;
+  int64_t seg_uniform = 0;  // rows per resource when every resource has the same count, else 0
+  // A forked tick's work classes run on the auxiliary streams.  Normally they are
+  // joined back into the context stream at the end of the tick; with DM_DEFER_JOIN
+  // the join waits for the next library call that needs it (each cross-queue hop
+  // costs ~20 us on the GPU, so back-to-back ticks keep every class streaming).
+  // aux_pending: class work not yet joined into the context stream.
+  // main_dirty: the context stream holds work the auxiliary streams have not
+  // waited for (the next fork must record an event).
+  bool aux_pending = false, main_dirty = true;
+  hipError_t join_aux() {
+    if (!aux_pending) return hipSuccess;
+    aux_pending = false;
+    aux_unjoined = 0;
+    for (int i = 0; i < kAux; ++i) {
+      hipError_t e = xs_order(XS_JOIN0 + i, aux[i], stream);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  // the store-update kernels' view of the dense state (dm_device.h DenseUpd)
+  DenseUpd dense_upd() const {
+    DenseUpd d{};
+    d.item_of = item_of.p;
+    for (int b = 3; b <= 6; ++b) d.bins[b - 3] = bins[b].p;
+    d.bin4_wave = bin4_wave ? 1 : 0;
+    d.bin6_wide = bin6_wide ? 1 : 0;
+    d.rmask = rmask.p;
+    return d;
+  }
+  // Queue calibration (calib_step): which of the four auxiliary streams -- four hardware
+  // queues -- carries which work class moved configs[2]'s tick from 111 to 157 us over
+  // the 24 assignments (profiles/r05_queues.txt), and a queue's place in the process's
+  // creation order, which a host that made streams of its own first shifts, decides
+  // which assignment is best.  So the context times every assignment on its first
+  // forked writeback ticks (windows of kCalibWin ticks, each between joins of every
+  // class stream, HIP events on the context stream), times the best kCalibFinal again
+  // over longer windows, and keeps the fastest: aux[i] = aux_phys[perm[i]].
+  // (the skip: a context's first ticks run slow -- first-touch, and the GPU reaches its
+  // sustained-load operating point only after ~0.1-0.3 s of back-to-back work,
+  // profiles/r06_c4_variants.md -- which biases the candidates timed first; round 2
+  // therefore also interleaves its candidates, kCalibRep2 short windows each, and sums
+  // them, so that a drift of the clocks falls on every candidate alike)
+  static constexpr int kCalibSkip = 1024, kCalibWin = 6, kCalibFinal = 3, kCalibWin2 = 4, kCalibRep2 = 4;
+  int calib = 0;  // 0 pending, 1 round 1, 2 round 2, 3 waiting for the events, 4 done / off
+  int calib_skip = 0, calib_k = 0, calib_t = 0, calib_round = 0;
+  int perm[kAux] = {0, 1, 2, 3};
+  hipStream_t aux_phys[kAux] = {};
+  std::vector<std::array<int, kAux>> calib_cand;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> calib_ev;
+  std::vector<int> calib_of_ev;  // candidate timed by each window
+  std::vector<float> calib_ms;
+  bool calib_log = false;
+  int64_t calib_best = -1;  // the chosen permutation (perm[0] + 4 perm[1] + 16 perm[2] + 64 perm[3])
+  // plan
+  std::vector<Tile> h_tiles;  // small resources (n <= kSmallMax) in tiles (k_tile_small)
+  std::vector<TileEntry> h_tile_list;  // the list tiles' resources
+  DBuf<TileEntry> tile_list;
+  std::vector<WorkItem> h_bins[kNumBins];
+  std::vector<Chunk> h_chunks;
+  std::vector<LargeSeg> h_large;
+  DBuf<Tile> tiles;
+  DBuf<WorkItem> bins[kNumBins];
+  DBuf<Chunk> chunks;
+  DBuf<LargeSeg> large;
+  // the sub-wave bins run in one launch (k_subs): C2 tick 144-145 -> 138 us against
+  // one launch per bin (tools/ab.py, both orders, one box; the per-bin form was
+  // retired in round 5)
+  // The 128-thread bins (3, 4) split by the dense hint (k_block_dense + k_block_rest)
+  // on a tick that follows a writeback tick (only those set hints), unless the last
+  // split tick the host has heard of queued more than a quarter of the bin's items
+  // for k_block_rest (then it tries again after 64 ticks, doubling the wait after every
+  // try that still queued too many, up to 4096: C2's bins, whose resources keep
+  // released rows, run 21 % slower split, and a try's k_block_rest strides over
+  // thousands of items).  DM_DENSE_SPLIT=0: never split.
+  int dense_split = 0xF;  // bit i: bin 3+i runs in the split form (DM_DENSE_SPLIT: 0 off, 1 all, else the mask)
+  static constexpr int kSplitBins = 4;  // bins 3..6
+  // A split part whose items are all verified dense, none with released rows or arrivals
+  // (k_count_undense's two counts), runs the steady builds of k_block_dense outside
+  // recompute mode: Clean's result is known, so its pass is left out (dm_tick_group.hip
+  // group_segment STEADY).  DM_STEADY=0: never; 2 (A/B only): the steady ticks' launches,
+  // dense then rest, with the plain builds: what the trailing rest launch costs.
+  int steady_ok = 1;
+  unsigned steady_mask = 0;  // bit i: split slot i's last tick ran a steady build (dm_plan_info slot 20)
+  // Stream parts: a workgroup bin that is the store's only work class, and small enough
+  // that a launch's ramp and drain are a visible share of it, runs as kParts launches
+  // over contiguous halves of its items on two auxiliary streams, never joined from
+  // tick to tick (DM_DEFER_JOIN): each part's next tick starts while the other part
+  // drains, so the GPU never idles between ticks (an N = 8 shard of configs[3], 12.5M
+  // leases: 57.3 -> 48.8 us per tick, tools/shard_split.py; the whole configs[3], 100M
+  // leases: 430 -> 425 us, not worth its cross-queue waits in the exchange).  Every
+  // split-bin state below is per part: slot (b - 3) * kParts + part.
+  static constexpr int kParts = 2;
+  static constexpr int kSplitSlots = kSplitBins * kParts;
+  int bin_parts[kNumBins] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
+  // off for a leaf whose ticks an exchange on another stream waits for (dm_hier_attach):
+  // there the exchange's two waits and the parts' CU share cost more than the parts
+  // gain (the N = 8 rehearsal step 58.7 -> 66 us; one wait: 60-62 us; round 5)
+  bool parts_ok = true;
+  int64_t part_lo[kNumBins][kParts + 1] = {};  // item bounds of each part
+  DBuf<int32_t> dq_list[kSplitSlots], dq_cnt[kSplitSlots];
+  int dq_par[kSplitSlots] = {};
+  int dq_skip[kSplitSlots] = {};   // ticks in the one-kernel form since the split was last tried
+  int dq_wait[kSplitSlots] = {64, 64, 64, 64, 64, 64, 64, 64};  // ticks before the next try
+  bool bin6_wide = false;  // bin 6 on 512 x 8 workgroups (kBin6Wide): it holds most of the rows
+  bool bin4_wave = false;  // bin 4 on one wave per resource (kBin4Wave): most of its resources FairShare
+  std::vector<int32_t> h_kind;  // the loaded configuration's kinds (bin 4's shape)
+  HBuf<int32_t> h_dq;  // host-mapped: items the last split tick queued, per bin
+  // host-mapped, per split bin: {undense count, epoch} of the epoch's check
+  // (k_count_undense), and the guard a dense kernel sets should it queue an item on a
+  // tick whose rest kernel was skipped
+  HBuf<uint64_t> h_rec;
+  HBuf<int32_t> h_guard;
+  uint64_t dq_ver_epoch[kSplitSlots] = {};  // the epoch each slot's check was enqueued in
+  // large-path partials
+  DBuf<int64_t> pa_cnt, pa_cnt_all, pa_smin, pa_smax, pb_w, pc_sgt;
+  DBuf<double> pa_has, pa_wants, pa_has_all, pa_wants_all, pb_x, pb_y, pc_ee, pd_delta;
+  DBuf<int32_t> pa_nan;
+  DBuf<uint32_t> pa_live;
+  DBuf<uint8_t> p_tot;
+  // the speculative chain (k_large_spec + k_large_redo; DM_SPEC_CHAIN=0: the chain):
+  // per large resource its SpecTot, the redo's launch count, the host-mapped give-up flag
+  bool spec_chain = true;
+  DBuf<SpecTot> p_spec;
+  DBuf<uint32_t> p_spec_ring;  // SpecArgs::ring
+  // 3/4 of the redo workgroups (full build) the GPU holds at once: the full build's
+  // grid when the store has that many team slots
+  int64_t redo_cap = 0;
+  // the redo by teams (k_large_redo_team): team slots and the two builds' grids.  (The
+  // per-chunk redo of round 4, bounded by redo_cap chunks per resource, was retired in
+  // round 5: the teams need only kTeamMax co-resident workgroups for any resource.)
+  DBuf<int32_t> p_team;
+  int nslots = 0, team_grid_full = 1, team_grid_light = 1;
+  uint64_t spec_seq = 0;
+  HBuf<int32_t> h_serr;  // [0] the give-up flag, [1] SpecArgs::seen
+  // k_large_redo's light build (dm_tick_large.hip) while the last redo the host saw found
+  // nothing marked and no row changed since (DM_REDO_LIGHT: 0 never, 1 so, 2 always)
+  int redo_light = 1;
+  uint64_t redo_epoch = 0;  // row_epoch at the last speculative tick
+  DBuf<int32_t> p_uni;
+  // heterogeneous FairShare on the chain (allocated on the first tick that may need it)
+  DBuf<uint32_t> ph_set;  // per large resource: distinct subclient counts (all ones between ticks)
+  DBuf<int32_t> ph_n, ph_bkc;
+  size_t ph_set_ready = 0;  // large resources whose set slots are initialised
+  DBuf<uint8_t> ph_het;
+  DBuf<double> ph_bkw;
+  DBuf<int64_t> ph_bks;
+  // worklist of resources for k_general (heterogeneous-subclient FairShare)
+  DBuf<int32_t> glist, gcount;
+  // Some non-small resource may need k_general.  A store update can make a store "maybe
+  // general" (a NaN wants, subclients other than one) after its plan chose stream parts,
+  // which plan_parts leaves out for a store that is general when planned.  The parts stay
+  // (ADVICE r5 asked which): a tick that may run k_general joins every class stream before
+  // it (dm_apportion: no deferred join), so k_general sees both parts' worklist appends,
+  // and the parts' own kernels leave a heterogeneous resource untouched for it
+  // (tests/test_parts_gpu.py::test_parts_store_turning_general_keeps_its_parts).
+  bool maybe_general = false;
+  bool all_sub_one = true;  // every loaded row had subclients == 1
+  int64_t n_nonsmall = 0;
+  // staging for upsert / release
+  DBuf<int64_t> st_rows, st_sub, st_exp;
+  DBuf<double> st_has, st_wants;
+  DBuf<uint64_t> st_mask;  // dm_store_update_wants_mask
+  DBuf<int64_t> st_blk;
+  DBuf<int32_t> st_wpre;
+  static constexpr int kWChunks = 4;  // dm_store_apply: the refresh values' copy chunks
+  // One round's staging (dm_store_apply): set 0 for the synchronous call, sets 1..
+  // kAsyncSets for dm_store_apply_async, whose batch k uses set 1 + k % kAsyncSets and is
+  // retired (its flags read) before batch k + kAsyncSets reuses the set.
+  struct ApplySet {
+    DBuf<uint64_t> mask;
+    DBuf<double> mwants;  // the refresh part's values
+    DBuf<int64_t> blk;
+    DBuf<int32_t> wpre;
+    DBuf<int64_t> rel;  // the departures' rows
+    DBuf<int64_t> rows, sub, exp;
+    DBuf<double> has, wants;
+    DBuf<uint32_t> flags;  // one flags word per part
+    HBuf<uint32_t> h_flags;  // its pinned host mirror
+    Event ev_bat[3];
+    Event ev_wchunk[kWChunks];
+    Event ev_done;  // (asynchronous sets) the batch's last kernel and flags copy
+    bool pending = false;      // enqueued, not yet retired
+    bool may_general = false;  // its refresh or arrivals may bring NaN wants / other subclient counts
+    int64_t nu = 0;
+  };
+  static constexpr int kAsyncSets = 2;
+  ApplySet aset[1 + kAsyncSets];
+  int64_t async_seq = 0;  // asynchronous batches enqueued
+  // a tick enqueued while an asynchronous batch that may make the store general is in flight
+  bool async_may_general() const {
+    for (int i = 1; i <= kAsyncSets; ++i)
+      if (aset[i].pending && aset[i].may_general) return true;
+    return false;
+  }
+  // dm_store_relayout: the rejection flags and the first rejected resource, compact mode's
+  // block counts / prefix and per-resource bases, the row map's device staging
+  DBuf<uint32_t> rl_flags;
+  DBuf<unsigned long long> rl_bad;
+  DBuf<int64_t> rl_blk_pre, rl_map;
+  DBuf<int32_t> rl_seg_local;
+  // dm_store_clean: the scan blocks' counts / prefix and minima, and the last clean's list
+  // of released rows (sized from its count, never from N), kept for dm_read_cleaned until
+  // the next clean, load or re-layout
+  DBuf<int64_t> cl_blk_pre, cl_blk_min, cl_list;
+  bool cl_valid = false;
+  int64_t cl_n = 0;
+  DBuf<uint32_t> row_bits;    // device row bitmap for the uniqueness check, all-zero between calls
+  DBuf<uint32_t> upd_flags;    // k_check_rows result (device)
+  // dm_decide: a round's requests (grouped by resource), per-resource work items, results
+  DBuf<int64_t> rq_rows, rq_sub, rq_exp;
+  DBuf<double> rq_has, rq_wants, rq_gets;
+  DBuf<ReqItem> rq_items;
+  DBuf<double> rq_sc_has, rq_sc_wants;  // the round's working copy of the requested resources' rows
+  DBuf<int32_t> rq_sc_sub;
+  // dm_decide's fast path (dm_decide_fast.hip); DM_DECIDE_FAST=0 turns it off
+  bool decide_fast = true;
+  DBuf<FastItem> fd_items;
+  DBuf<FastRes> fd_res;
+  DBuf<int64_t> fd_prev, fd_bounds;
+  DBuf<double> fd_pw, fd_v, fd_keys, fd_keys_s, fd_ev_in, fd_ev;
+  DBuf<FdScan> fd_sc, fd_ps, fd_part;
+  DBuf<int32_t> fd_evs_in, fd_evs, fd_ecnt, fd_bdc;
+  DBuf<double2> fd_esum, fd_bds;
+  DBuf<FdClean> fd_pc;
+  DBuf<FdScan> fd_pt;
+  DBuf<FdLind> fd_ld;
+  DBuf<uint8_t> fd_tmp;
+  // dm_publish_totals: the workgroups' validation flags and their arrival counter
+  // (k_publish; both return to zero after each launch)
+  DBuf<uint32_t> pub_sync;
+  // dm_publish_ring: writeback tick k publishes into pub_ring[k % n]
+  std::vector<double2*> pub_ring;
+  int64_t pub_k = 0;
+  // root side of the hierarchy: the exchange's layout (dm_hier_layout) and the
+  // last round's per-server flags
+  int hier_G = 0;                    // 0: not configured (replicated, G from each call)
+  bool hier_sharded = false;
+  std::vector<int64_t> h_hier_lo;    // [G + 1] sharded bounds
+  DBuf<int64_t> hier_lo;
+  int64_t hier_stride = 0;
+  DBuf<uint32_t> hier_status;
+  int hier_servers = 0;
+  // dm_hier_attach / dm_hier_step (root side): the leaf it serves, its ring and gathered
+  // buffer, its server index; the exchange's RCCL communicator (dm_hier_comm_init)
+  dm_ctx* hs_leaf = nullptr;
+  int hs_server = 0;
+  std::vector<void*> hs_ring;
+  void* hs_gathered = nullptr;
+  ncclComm_t nccl_comm = nullptr;
+  bool hs_ordered = false;  // dm_hier_step already ordered the exchange stream after the tick
+  // leaf side: pipelined templates (dm_hier_pipeline).  An exchange stages this
+  // leaf's new templates in a free slot; the leaf's ticks take the staged templates
+  // of the exchanges enqueued before the previous tick (one tick of lag).
+  bool tpl_pipe = false;
+  int tpl_lag = 1;  // ticks between an exchange and the first tick that takes its templates, minus one
+  DBuf<ResCfg> tpl_cfg[kTplSlots];
+  DBuf<ResCold> tpl_cold[kTplSlots];
+  XsTok tpl_ready[kTplSlots];        // root stream: the slot's templates are written
+  XsTok tpl_free[kTplSlots];         // leaf stream: the ticks that read the slot are done
+  bool tpl_free_rec[kTplSlots] = {};  // tpl_free holds a signal
+  struct Staged {
+    int slot;
+    int64_t tag;  // leaf ticks issued before the exchange was enqueued
+  };
+  std::vector<Staged> tpl_pending;          // oldest first
+  std::vector<int> tpl_free_slots;
+  int64_t ticks_issued = 0;
+  // The tick-done signal: ticks numbered by tick_seq (never reset).  The last kernel of
+  // a one-class split tick (C1, C3: the dense kernel, or the rest kernel after it) is
+  // launched with a stop event (hipExtLaunchKernel: the kernel's own completion signal,
+  // no marker packet of its own on the leaf's queue -- each marker cost a ~10-us bubble
+  // per N = 8 shard step), one event per tick in a ring; another queue waits on it.
+  // Round 4 stored a word from a one-wave k_tick_done after the dense kernel (5 us of
+  // the leaf's queue): the N = 8 rehearsal step 60.2-60.7 -> 58.7-58.8 us (round 5,
+  // gpurun_out/r5b2shard, three alternations).
+  // The event covers the tick's leases and sums, not every launch of it: once per row
+  // epoch a writeback tick enqueues k_count_undense after the event-carrying kernel on
+  // the same stream (check_dense).  That kernel only reads the work items' hints and
+  // writes a host-mapped count, which no consumer of the event (the exchange, a template
+  // slot's reuse) touches; a consumer that needed it would have to join the stream.
+  uint64_t tick_seq = 0;          // the last tick's number
+  bool tick_flagged = false;      // ... and whether its last kernels complete tick_ev[*][tick_seq % kTickEv]
+  static constexpr int kTickEv = 16;
+  Event tick_ev[kParts][kTickEv];  // per stream part (one part: [0])
+  int tick_nev[kTickEv] = {};                // the parts that completed each flagged tick's events
+  unsigned tick_part_mask = 0;               // auxiliary streams of the last flagged tick's parts
+  // auxiliary streams with work not yet joined into the context stream
+  unsigned aux_unjoined = 0;
+  // the last tick's events cover every auxiliary stream's unjoined work, so a consumer
+  // may wait on them instead of joining (which would make the next tick's parts wait
+  // for each other: 49 -> 74 us per tick on the N = 8 shard, tools/shard_split.py)
+  bool tick_covers() const { return tick_flagged && tick_part_mask != 0 && (aux_unjoined & ~tick_part_mask) == 0; }
+  // a stream part's auxiliary stream (part 0: the bin's class stream).  Part 1 beside
+  // bins 4-6's stream 1: stream 2 or 0 run C1 at 40.6-40.8 us per tick, stream 3 at
+  // 61.6-64.2 us (which hardware queues pair well: take_aux; profiles/r05_parts_ab.txt)
+  int part_stream(int b, int j) const {
+    if (j == 0) return class_stream[b];
+    return class_stream[b] != 2 ? 2 : 0;
+  }
+  // set by the first consumer on another stream (the exchange's order, a template
+  // slot's reuse): before it, no tick carries the event
+  bool tick_signal_wanted = false;
+  uint64_t tpl_free_seq[kTplSlots] = {};  // a slot is free once this tick's event completed (0: use tpl_free)
+  HBuf<uint32_t> h_flags;  // pinned host mirror of upd_flags
+  // profiling
+  bool profiling = false;
+  std::vector<ProfEvent> pending;
+  std::vector<hipEvent_t> event_pool;
+  int64_t prof_launches[KC_COUNT] = {};
+  double prof_ms[KC_COUNT] = {};
+
+  int fail(int code, const std::string& msg) {
+    err = msg;
+    set_last_error(msg);
+    return code;
+  }
+  int hip_fail(hipError_t e, const char* what) {
+    return fail(DM_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  // The device's failure words (host-mapped, written by kernels of earlier ticks):
+  // once one is set the store is lost (store_lost).  Called at the entry of every call
+  // that touches the store and after every host wait that may have completed a tick.
+  int check_device() {
+    if (!store_lost) {
+      for (int i = 0; h_guard.p && i < kSplitSlots; ++i)
+        if (__atomic_load_n(h_guard.p + i, __ATOMIC_RELAXED)) {
+          store_lost = true;
+          lost_msg = "a dense kernel queued an item on a tick that skipped its rest kernel";
+        }
+      if (!store_lost && h_serr.p && __atomic_load_n(h_serr.p, __ATOMIC_RELAXED)) {
+        store_lost = true;
+        lost_msg = "a redo workgroup of the speculative chain gave up waiting for its resource";
+      }
+    }
+    if (!store_lost || reading) return DM_OK;  // (a reader of a lost store: dm_store_lost says so)
+    return fail(DM_E_INTERNAL, "internal failure on the device: " + lost_msg +
+                                   "; the store's leases and sums may be wrong, reload it (dm_store_load)");
+  }
+  bool reading = false;  // a read call in progress (DM_STORE_READABLE): a lost store may be read
+  // wait for the context stream, then report a device failure the wait completed
+  int synced(const char* what) {
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return check_device();
+  }
+  hipEvent_t take_event() {
+    if (!event_pool.empty()) {
+      hipEvent_t e = event_pool.back();
+      event_pool.pop_back();
+      return e;
+    }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+  }
+  // HIP events around one launch on its stream while profiling is on (dm_kernel_times)
+  template <typename F>
+  hipError_t timed(int cls, hipStream_t s, F&& fn) {
+    if (!profiling) return fn();
+    ProfEvent pe{cls, take_event(), take_event()};
+    (void)hipEventRecord(pe.a, s);
+    hipError_t e = fn();
+    (void)hipEventRecord(pe.b, s);
+    pending.push_back(pe);
+    return e;
+  }
+  void collect_profile() {
+    for (auto& pe : pending) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, pe.a, pe.b) == hipSuccess) {
+        prof_ms[pe.cls] += ms;
+        prof_launches[pe.cls] += 1;
+      }
+      event_pool.push_back(pe.a);
+      event_pool.push_back(pe.b);
+    }
+    pending.clear();
+  }
+};
+
+#define DM_HIP(ctx, expr, what)                  \
+  do {                                           \
+    hipError_t _e = (expr);                      \
+    if (_e != hipSuccess) return (ctx)->hip_fail(_e, what); \
+  } while (0)
+
+#define DM_CHECK_CTX(ctx)                                   \
+  do {                                                      \
+    if (!(ctx)) {                                           \
+      dm::set_last_error("null context");                   \
+      return DM_E_INVAL;                                    \
+    }                                                       \
+    DM_HIP(ctx, hipSetDevice((ctx)->device), "hipSetDevice"); \
+  } while (0)
+
+// Entry of every call that puts work on the context stream: join the auxiliary
+// streams' deferred tick work first (DM_DEFER_JOIN), and remember that the
+// context stream now holds work the next fork must order.
+#define DM_ENTER(ctx)                                         \
+  do {                                                        \
+    DM_CHECK_CTX(ctx);                                        \
+    DM_HIP(ctx, (ctx)->join_aux(), "join auxiliary streams"); \
+    (ctx)->main_dirty = true;                                 \
+  } while (0)
+
+// Entry of every call that reads or updates the store: refuse a lost store
+// (dm_ctx::store_lost) with the device's message.
+#define DM_STORE_OK(ctx)                             \
+  do {                                               \
+    if (int _rc = (ctx)->check_device()) return _rc; \
+  } while (0)
+// The read calls work on a lost store too (for diagnosis): the failure is
+// still recorded, and dm_store_lost reports it.  Ticks and updates keep refusing it.
+struct ReadScope {
+  dm_ctx* c;
+  explicit ReadScope(dm_ctx* x) : c(x) { c->reading = true; }
+  ~ReadScope() { c->reading = false; }
+};
+#define DM_STORE_READABLE(ctx)  \
+  ReadScope _read_scope(ctx); \
+  (void)(ctx)->check_device()
+
+template <typename T>
+static hipError_t upload(DBuf<T>& b, const T* src, size_t n, hipStream_t st) {
+  hipError_t e = b.ensure(n);
+  if (e != hipSuccess || n == 0) return e;
+  return hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+}
+
+template <typename T>
+static hipError_t download(T* dst, const T* src, int64_t off, int64_t n, hipStream_t st) {
+  if (!dst || n == 0) return hipSuccess;
+  return hipMemcpyAsync(dst, src + off, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st);
+}
+
+static inline int check_range(dm_ctx* c, int64_t off, int64_t n, int64_t total) {
+  if (off < 0 || n < 0 || off + n > total) return c->fail(DM_E_RANGE, "range out of bounds");
+  return DM_OK;
+}
+
+static_assert(!std::is_copy_constructible<dm_ctx>::value, "a context owns its buffers and events: never copied");
+
+// What one host unit defines and another calls.  Like the launchers (dm_launch.h) these
+// live in namespace dm and never get a dm_-prefixed C name.
+namespace dm {
+// dm_plan.cpp
+int64_t uniform_rows(const int64_t* seg_off, int64_t R);  // rows per resource when all have the same count, else 0
+void build_plan(dm_ctx* c);
+int upload_plan(dm_ctx* c);
+int update_bin4_shape(dm_ctx* c, hipStream_t st);
+int set_parts_ok(dm_ctx* c, bool ok);
+// dm_tick.cpp
+int ready(dm_ctx* c);
+void calib_free(dm_ctx* c);
+// dm_store_update.cpp
+void async_drain(dm_ctx* c);
+int async_retire_all(dm_ctx* c);
+// dm_hier_host.cpp
+struct RcclApi;
+const RcclApi* rccl_api();
+void rccl_destroy(const RcclApi* r, ncclComm_t comm);
+}  // namespace dm

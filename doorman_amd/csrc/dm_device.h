@@ -348,7 +348,7 @@ struct DevParams {
   // dm_publish_ring: a writeback tick also writes what dm_publish_totals would (record
   // 1 + r = {SumWants, Count} as each resource's sums are stored, the validation flags
   // OR-ed into record 0) and clears its flags word in record 0 of the ring's next
-  // buffer; nullptr: off.  A bin split into stream parts (dm_runtime.cpp) runs its parts
+  // buffer; nullptr: off.  A bin split into stream parts (dm_plan.cpp) runs its parts
   // unjoined from tick to tick, so each part owns a 32-bit flags word of record 0
   // (pub_word: 0 or 1; the first 8 bytes read as one int64 hold their OR in either
   // half) and clears only that word, from its first resource (pub_first), in the next

@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void k_hier_tick(DevParams p, HierArgs ha) {
 }
 
 // --------------------------------------------------------------------------
-// host-side launchers (called by dm_runtime.cpp)
+// host-side launchers (called by dm_hier_host.cpp)
 // --------------------------------------------------------------------------
 hipError_t launch_publish(int64_t R, const ResAgg* agg, void* dst, uint32_t* sync, hipStream_t st) {
   const int nb = (int)std::min<int64_t>(64, std::max<int64_t>(1, (R + 255) / 256));

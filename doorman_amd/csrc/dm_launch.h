@@ -1,4 +1,5 @@
-// dm_launch.h — the host-side launchers the kernel units define and dm_runtime.cpp calls.
+// dm_launch.h — the host-side launchers the kernel units define and the runtime's host units
+// (dm_ctx.h and the .cpp files around it) call.
 // Every unit that defines one includes this header, so a definition that drifts from its
 // declaration fails to compile instead of failing to link.
 #pragma once

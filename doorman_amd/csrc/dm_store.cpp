@@ -1,0 +1,309 @@
+// dm_store.cpp — a store and its configuration onto the device (dm_store_load,
+// dm_config_load) and the calls that read them back (dm_read_*).
+#include "dm_ctx.h"
+
+// Could some non-small resource need k_general (heterogeneous subclients or NaN
+// wants among its rows)?  Conservative: expiry is ignored.
+// Could any FairShare resource need k_general (live subclients not all equal, or NaN
+// wants)?  Released rows (DM_RELEASED) are never live, so they do not count.
+static bool scan_maybe_general(const int64_t* off, int64_t R, const int64_t* sub, const double* wants,
+                               const int64_t* exp) {
+  for (int64_t r = 0; r < R; ++r) {
+    if (off[r + 1] - off[r] <= kSmallMax) continue;
+    int64_t s0 = -1;
+    for (int64_t i = off[r]; i < off[r + 1]; ++i) {
+      if (exp[i] == DM_RELEASED) continue;
+      if (std::isnan(wants[i])) return true;
+      if (s0 < 0) s0 = sub[i];
+      if (sub[i] != s0) return true;
+    }
+  }
+  return false;
+}
+
+int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
+  DM_ENTER(c);
+  async_drain(c);
+  if (!s || s->n_resources < 0 || s->n_leases < 0 || !s->seg_off) return c->fail(DM_E_INVAL, "bad snapshot");
+  const int64_t R = s->n_resources, N = s->n_leases;
+  if (R > INT32_MAX - 1) return c->fail(DM_E_INVAL, "too many resources for one context (max 2^31-2)");
+  if (N > 0 && (!s->wants || !s->has || !s->subclients || !s->expiry_ns))
+    return c->fail(DM_E_INVAL, "snapshot columns missing");
+  if (s->seg_off[0] != 0 || s->seg_off[R] != N) return c->fail(DM_E_INVAL, "seg_off must run from 0 to n_leases");
+  for (int64_t r = 0; r < R; ++r)
+    if (s->seg_off[r + 1] < s->seg_off[r]) return c->fail(DM_E_INVAL, "seg_off must be non-decreasing");
+  for (int64_t i = 0; i < N; ++i)
+    if (s->subclients[i] < 0 || s->subclients[i] > kSubMax)
+      return c->fail(DM_E_INVAL, "subclients must be in [0, 2^31-2]");
+  const bool have_agg = s->agg_count && s->agg_sum_has && s->agg_sum_wants;
+  if ((s->agg_count || s->agg_sum_has || s->agg_sum_wants) && !have_agg)
+    return c->fail(DM_E_INVAL, "give all three running sums or none");
+  DM_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  c->R = R;
+  c->N = N;
+  c->h_seg_off.assign(s->seg_off, s->seg_off + R + 1);
+  c->seg_uniform = uniform_rows(s->seg_off, R);  // every resource the same number of rows (a hierarchy root store: G)
+  hipStream_t st = c->stream;
+  DM_HIP(c, upload(c->seg_off, s->seg_off, (size_t)R + 1, st), "upload seg_off");
+  {  // RowIndex: resource of the first row of every 2^kRowBlkShift-row block
+    const int64_t nb = (N >> kRowBlkShift) + 2;
+    std::vector<int32_t> blk((size_t)nb, 0);
+    int64_t sg = 0;
+    for (int64_t b = 0; b < nb && R > 0; ++b) {
+      const int64_t row = std::min<int64_t>(b << kRowBlkShift, std::max<int64_t>(N - 1, 0));
+      while (sg + 1 < R && s->seg_off[sg + 1] <= row) ++sg;
+      blk[(size_t)b] = (int32_t)sg;
+    }
+    DM_HIP(c, upload(c->blk_seg, blk.data(), blk.size(), st), "upload row index");
+    DM_HIP(c, hipStreamSynchronize(st), "upload row index");  // blk leaves scope
+  }
+  DM_HIP(c, upload(c->wants, s->wants, (size_t)N, st), "upload wants");
+  DM_HIP(c, upload(c->has, s->has, (size_t)N, st), "upload has");
+  {
+    std::vector<int32_t> sub32((size_t)N);
+    // every loaded row keeps its own expiry (explicit, dm_device.h); a writeback tick
+    // turns the live ones into followers of their resource's expiry
+    for (int64_t i = 0; i < N; ++i) sub32[i] = (int32_t)((uint32_t)s->subclients[i] | kSubExplicit);
+    DM_HIP(c, upload(c->sub, sub32.data(), (size_t)N, st), "upload subclients");
+    DM_HIP(c, hipStreamSynchronize(st), "upload subclients");  // sub32 leaves scope
+  }
+  DM_HIP(c, upload(c->expiry, s->expiry_ns, (size_t)N, st), "upload expiry");
+  std::vector<int64_t> cnt;
+  std::vector<double> sh, sw;
+  const int64_t* ac = s->agg_count;
+  const double* ah = s->agg_sum_has;
+  const double* aw = s->agg_sum_wants;
+  if (!have_agg) {  // one Assign per row, in row order (store.go:156-158)
+    cnt.assign(R, 0);
+    sh.assign(R, 0.0);
+    sw.assign(R, 0.0);
+    for (int64_t r = 0; r < R; ++r)
+      for (int64_t i = s->seg_off[r]; i < s->seg_off[r + 1]; ++i) {
+        sh[r] += s->has[i] - 0.0;
+        sw[r] += s->wants[i] - 0.0;
+        cnt[r] += s->subclients[i];
+      }
+    ac = cnt.data();
+    ah = sh.data();
+    aw = sw.data();
+  }
+  std::vector<ResAgg> agg(R);
+  for (int64_t r = 0; r < R; ++r) agg[r] = ResAgg{ac[r], ah[r], aw[r], 0};
+  DM_HIP(c, upload(c->agg, agg.data(), (size_t)R, st), "upload running sums");
+  const std::vector<uint8_t> expl((size_t)std::max<int64_t>(R, 1), 1);  // loaded rows carry explicit expiries
+  DM_HIP(c, upload(c->expl, expl.data(), expl.size(), st), "upload explicit flags");
+  build_plan(c);
+  int rc = upload_plan(c);
+  if (rc) return rc;
+  c->maybe_general = scan_maybe_general(s->seg_off, R, s->subclients, s->wants, s->expiry_ns);
+  // released rows never take part in a tick, so they do not count against this
+  c->all_sub_one = true;
+  for (int64_t i = 0; i < N && c->all_sub_one; ++i)
+    c->all_sub_one = s->subclients[i] == 1 || s->expiry_ns[i] == DM_RELEASED;
+  DM_HIP(c, hipStreamSynchronize(st), "store load");
+  c->store_loaded = true;
+  c->cl_valid = false;  // the last clean's list named rows of the store this one replaced
+  c->store_lost = false;  // upload_plan cleared the device's failure words
+  c->expl_rows = true;
+  c->rows_changed();
+  c->have_result = false;
+  c->wb_inplace = -1;
+  c->hints_set = false;
+  if (c->cfg_loaded && (int64_t)c->h_refresh_s.size() != R) c->cfg_loaded = false;
+  return DM_OK;
+}
+
+int dm_config_load(dm_ctx* c, int64_t R, const dm_resource_cfg* cfg) {
+  DM_ENTER(c);
+  // In-flight batches finish first (their arrivals take the lease lengths they were sent
+  // under).  The store stays, so their outcome counts: every set is retired through
+  // apply_check, which keeps maybe_general / all_sub_one true to the rows (a drained NaN
+  // wants or other subclient count would otherwise leave later ticks on the non-general
+  // path: tests/test_general_transitions_gpu.py), and a rejected batch's error is
+  // returned instead of loading the configuration -- the caller calls again.
+  if (int ra = async_retire_all(c)) return ra;
+  c->rows_changed();
+  if (!cfg || R < 0 || !cfg->kind || !cfg->capacity || !cfg->lease_length_s || !cfg->refresh_interval_s ||
+      !cfg->learning_end_ns || !cfg->parent_expiry_ns || !cfg->safe_capacity)
+    return c->fail(DM_E_INVAL, "bad config");
+  for (int64_t r = 0; r < R; ++r) {
+    if (cfg->lease_length_s[r] < 0 || cfg->refresh_interval_s[r] < 0)
+      return c->fail(DM_E_INVAL, "lease_length and refresh_interval must be >= 0 (server.go:384-434)");
+    if (cfg->refresh_interval_s[r] > INT32_MAX || cfg->lease_length_s[r] > INT32_MAX)
+      return c->fail(DM_E_INVAL, "refresh_interval and lease_length must be < 2^31 s");
+  }
+  for (int64_t r = 0; r < R; ++r)
+    if (cfg->kind[r] < DM_NO_ALGORITHM || cfg->kind[r] > DM_FAIR_SHARE) {
+      char buf[96];
+      snprintf(buf, sizeof buf, "unknown algorithm kind %d for resource %lld", cfg->kind[r], (long long)r);
+      return c->fail(DM_E_KIND, buf);
+    }
+  DM_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  hipStream_t st = c->stream;
+  std::vector<ResCfg> rc(R);
+  std::vector<ResCold> rcold(R);
+  for (int64_t r = 0; r < R; ++r) {
+    rc[r] = ResCfg{cfg->capacity[r], cfg->learning_end_ns[r], cfg->parent_expiry_ns[r],
+                   (int32_t)cfg->lease_length_s[r], cfg->kind[r]};
+    rcold[r] = ResCold{cfg->safe_capacity[r], (int32_t)cfg->refresh_interval_s[r], 0};
+  }
+  c->tpl_pending.clear();  // staged exchanges were computed for the old configuration
+  DM_HIP(c, upload(c->cfg, rc.data(), (size_t)R, st), "upload config");
+  DM_HIP(c, upload(c->cold, rcold.data(), (size_t)R, st), "upload config");
+  c->h_refresh_s.assign(cfg->refresh_interval_s, cfg->refresh_interval_s + R);
+  c->h_kind.assign(cfg->kind, cfg->kind + R);
+  if (c->store_loaded && R == c->R) {  // bin 4's shape by the new kinds
+    if (int rc2 = update_bin4_shape(c, st)) return rc2;
+  }
+  DM_HIP(c, hipStreamSynchronize(st), "config load");
+  c->cfg_loaded = true;
+  return DM_OK;
+}
+
+int dm_read_leases(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
+  int rc = check_range(c, off, n, c->N);
+  if (rc) return rc;
+  DM_HIP(c, download(gets, c->last_writeback ? c->has.p : c->out_gets.p, off, n, c->stream), "read gets");
+  if (expiry_ns && c->last_writeback) {  // the store's encoding, resolved on the device
+    DM_HIP(c, c->st_exp.ensure((size_t)std::max<int64_t>(n, 1)), "stage expiry");
+    DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, c->st_exp.p,
+                                  nullptr, c->stream),
+           "resolve expiry");
+    DM_HIP(c, download(expiry_ns, (const int64_t*)c->st_exp.p, 0, n, c->stream), "read expiry");
+  } else {
+    DM_HIP(c, download(expiry_ns, (const int64_t*)c->out_expiry.p, off, n, c->stream), "read expiry");
+  }
+  return c->synced("read leases");
+}
+
+int dm_read_leases_rows(dm_ctx* c, int64_t n, const int64_t* rows, double* gets, int64_t* expiry_ns) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
+  if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad rows");
+  if (n == 0) return DM_OK;
+  for (int64_t i = 0; i < n; ++i)
+    if (rows[i] < 0 || rows[i] >= c->N) return c->fail(DM_E_RANGE, "row out of range");
+  const double* g = c->last_writeback ? c->has.p : c->out_gets.p;
+  const int64_t* e = c->last_writeback ? nullptr : c->out_expiry.p;  // the store's encoding: resolved below
+  DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
+  DM_HIP(c, c->st_has.ensure((size_t)n), "stage gets");
+  DM_HIP(c, c->st_exp.ensure((size_t)n), "stage expiry");
+  DM_HIP(c, hipMemcpyAsync(c->st_rows.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, c->stream), "stage rows");
+  DM_HIP(c, launch_gather_leases(n, c->st_rows.p, g, e, c->st_has.p, c->st_exp.p, c->stream), "gather leases");
+  if (!e)
+    DM_HIP(c, launch_resolve_rows(n, c->st_rows.p, 0, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, c->st_exp.p,
+                                  nullptr, c->stream),
+           "resolve expiry");
+  DM_HIP(c, download(gets, (const double*)c->st_has.p, 0, n, c->stream), "read gets");
+  DM_HIP(c, download(expiry_ns, (const int64_t*)c->st_exp.p, 0, n, c->stream), "read expiry");
+  return c->synced("read leases");
+}
+
+int dm_read_leases_proto(dm_ctx* c, int64_t off, int64_t n, double* capacity, int64_t* expiry_time_s,
+                         int64_t* refresh_interval_s) {
+  std::vector<int64_t> e(n > 0 ? n : 0);
+  int rc = dm_read_leases(c, off, n, capacity, e.data());
+  if (rc) return rc;
+  if (expiry_time_s)
+    for (int64_t i = 0; i < n; ++i) {
+      // time.Time.Unix(): floor division by 1e9 (server.go:789)
+      int64_t v = e[i];
+      if (v == DM_RELEASED) {
+        expiry_time_s[i] = DM_RELEASED;
+        continue;
+      }
+      int64_t q = v / kNs;
+      if (v % kNs != 0 && v < 0) --q;
+      expiry_time_s[i] = q;
+    }
+  if (refresh_interval_s && n > 0) {
+    // the device config: a hierarchy exchange rewrites a leaf's algorithm (dm_hier_root_tick)
+    const auto& so = c->h_seg_off;
+    const int64_t r0 = std::upper_bound(so.begin(), so.end(), off) - so.begin() - 1;
+    const int64_t r1 = std::upper_bound(so.begin(), so.end(), off + n - 1) - so.begin() - 1;
+    std::vector<ResCold> cf((size_t)(r1 - r0 + 1));
+    DM_HIP(c, download(cf.data(), (const ResCold*)c->cold.p, r0, r1 - r0 + 1, c->stream), "read config");
+    DM_HIP(c, hipStreamSynchronize(c->stream), "read config");
+    int64_t r = r0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t row = off + i;
+      while (r + 1 < (int64_t)so.size() && so[r + 1] <= row) ++r;
+      refresh_interval_s[i] = e[i] == DM_RELEASED ? 0 : cf[(size_t)(r - r0)].refresh_s;
+    }
+  }
+  return DM_OK;
+}
+
+int dm_read_resources(dm_ctx* c, int64_t r0, int64_t n, int64_t* count, double* sum_has, double* sum_wants,
+                      double* safe) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  int rc = check_range(c, r0, n, c->R);
+  if (rc) return rc;
+  if (safe && !c->have_result) return c->fail(DM_E_STATE, "safe capacity needs a dm_apportion result");
+  const bool wb = !c->have_result || c->last_writeback;
+  std::vector<ResAgg> v(n > 0 ? n : 0);
+  std::vector<ResCfg> cf(safe && n > 0 ? n : 0);
+  std::vector<ResCold> cc(safe && n > 0 ? n : 0);
+  DM_HIP(c, download(v.data(), (const ResAgg*)(wb ? c->agg.p : c->res.p), r0, n, c->stream), "read resources");
+  // the device config: a hierarchy exchange rewrites a leaf's templates (dm_hier_root_tick)
+  if (safe) DM_HIP(c, download(cf.data(), (const ResCfg*)c->cfg.p, r0, n, c->stream), "read config");
+  if (safe) DM_HIP(c, download(cc.data(), (const ResCold*)c->cold.p, r0, n, c->stream), "read config");
+  if (int rs = c->synced("read resources")) return rs;
+  for (int64_t i = 0; i < n; ++i) {
+    if (count) count[i] = v[i].count;
+    if (sum_has) sum_has[i] = v[i].sum_has;
+    if (sum_wants) sum_wants[i] = v[i].sum_wants;
+    // SetSafeCapacity (resource.go:81-96) after the tick's Clean: configured, or capacity / Count
+    if (safe) safe[i] = std::isnan(cc[i].safe_capacity) ? cf[i].capacity / (double)v[i].count : cc[i].safe_capacity;
+  }
+  return DM_OK;
+}
+
+int dm_read_config(dm_ctx* c, int64_t r0, int64_t n, int32_t* kind, double* capacity, int64_t* lease_length_s,
+                   int64_t* refresh_interval_s, int64_t* learning_end_ns, int64_t* parent_expiry_ns,
+                   double* safe_capacity) {
+  DM_ENTER(c);
+  if (!c->cfg_loaded) return c->fail(DM_E_STATE, "no configuration loaded");
+  int rc = check_range(c, r0, n, c->R);
+  if (rc) return rc;
+  std::vector<ResCfg> v(n > 0 ? (size_t)n : 0);
+  std::vector<ResCold> vc(n > 0 ? (size_t)n : 0);
+  DM_HIP(c, download(v.data(), (const ResCfg*)c->cfg.p, r0, n, c->stream), "read config");
+  DM_HIP(c, download(vc.data(), (const ResCold*)c->cold.p, r0, n, c->stream), "read config");
+  DM_HIP(c, hipStreamSynchronize(c->stream), "read config");
+  for (int64_t i = 0; i < n; ++i) {
+    if (kind) kind[i] = v[i].kind;
+    if (capacity) capacity[i] = v[i].capacity;
+    if (lease_length_s) lease_length_s[i] = v[i].lease_len_s;
+    if (refresh_interval_s) refresh_interval_s[i] = vc[i].refresh_s;
+    if (learning_end_ns) learning_end_ns[i] = v[i].learning_end_ns;
+    if (parent_expiry_ns) parent_expiry_ns[i] = v[i].parent_expiry_ns;
+    if (safe_capacity) safe_capacity[i] = vc[i].safe_capacity;
+  }
+  return DM_OK;
+}
+
+int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  int rc = check_range(c, off, n, c->N);
+  if (rc) return rc;
+  DM_HIP(c, download(has, (const double*)c->has.p, off, n, c->stream), "read has");
+  DM_HIP(c, download(wants, (const double*)c->wants.p, off, n, c->stream), "read wants");
+  if ((sub || exp) && n > 0) {  // subclients and expiry from the column encoding (dm_device.h)
+    DM_HIP(c, c->st_exp.ensure((size_t)n), "stage expiry");
+    DM_HIP(c, c->st_sub.ensure((size_t)n), "stage subclients");
+    DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p,
+                                  exp ? c->st_exp.p : nullptr, sub ? c->st_sub.p : nullptr, c->stream),
+           "resolve rows");
+    DM_HIP(c, download(exp, (const int64_t*)c->st_exp.p, 0, n, c->stream), "read expiry");
+    DM_HIP(c, download(sub, (const int64_t*)c->st_sub.p, 0, n, c->stream), "read subclients");
+  }
+  return c->synced("read store");
+}

@@ -1,0 +1,596 @@
+// dm_tick.cpp — dm_apportion: one tick's launches over the plan's work classes and their
+// streams (struct Tick), and what a tick does first: the readiness check, a pipelined
+// leaf's staged templates, the queue calibration's windows.
+#include <ctime>
+
+#include "dm_ctx.h"
+
+int dm::ready(dm_ctx* c) {
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  if (int rc = c->check_device()) return rc;
+  if (!c->cfg_loaded || (int64_t)c->h_refresh_s.size() != c->R)
+    return c->fail(DM_E_STATE, "no configuration loaded for the store's resources");
+  return DM_OK;
+}
+
+// Pipelined hierarchy (dm_hier_pipeline): before a leaf tick, take the templates of
+// the exchanges enqueued before the previous tick (stream-ordered after their root
+// kernels); the slot they replace becomes free once the ticks that read it are done.
+static int commit_templates(dm_ctx* c) {
+  int take = -1;
+  size_t n = 0;
+  while (n < c->tpl_pending.size() && c->tpl_pending[n].tag + (c->tpl_lag - 1) < c->ticks_issued)
+    take = c->tpl_pending[n++].slot;
+  for (size_t i = 0; i + 1 < n; ++i) c->tpl_free_slots.push_back(c->tpl_pending[i].slot);  // superseded
+  c->tpl_pending.erase(c->tpl_pending.begin(), c->tpl_pending.begin() + (ptrdiff_t)n);
+  if (take < 0) return DM_OK;
+  const dm_ctx::XsTok& rt = c->tpl_ready[take];
+  const bool host_wait = rt.rec && rt.s && rt.s != c->stream;
+  // deferred class work also read the old templates: joined, unless the last tick's
+  // events cover it (the slot's reuse then waits on them, below)
+  const bool keep = host_wait && c->tick_covers();
+  if (!keep) DM_HIP(c, c->join_aux(), "join");
+  if (host_wait) {
+    // poll: the wake-up of a blocking wait comes too late for the next launch to be
+    // queued in time.  Bounded by time (the exchange may wait on a slower rank's
+    // all-gather): after 50 us of polling, a blocking wait frees the core.
+    hipError_t q = hipEventQuery(c->xs_ev[rt.w]);
+    if (q == hipErrorNotReady) {
+      timespec t0{}, t1{};
+      clock_gettime(CLOCK_MONOTONIC, &t0);
+      do {
+        q = hipEventQuery(c->xs_ev[rt.w]);
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+      } while (q == hipErrorNotReady &&
+               (t1.tv_sec - t0.tv_sec) * 1000000000LL + (t1.tv_nsec - t0.tv_nsec) < 50000);
+    }
+    if (q == hipErrorNotReady) q = hipEventSynchronize(c->xs_ev[rt.w]);
+    if (q != hipSuccess) return c->hip_fail(q, "staged templates");
+  } else {
+    DM_HIP(c, c->xs_wait(rt, c->stream), "staged templates");
+  }
+  if (!keep) c->main_dirty = true;  // the class streams fork after the wait
+  std::swap(c->cfg, c->tpl_cfg[take]);
+  std::swap(c->cold, c->tpl_cold[take]);
+  // the old templates (now in slot `take`) are free after the ticks already enqueued
+  // the next exchange into it waits for the ticks enqueued so far: on the last tick's
+  // events (tick_ev, every stream part's) when its last kernels complete them, else on
+  // a (lazy) event
+  c->tpl_free_seq[take] = c->tick_flagged ? c->tick_seq : 0;
+  c->xs_signal_lazy(dm_ctx::XS_FREE0 + take, c->stream, &c->tpl_free[take]);
+  c->tpl_free_rec[take] = true;
+  c->tpl_free_slots.push_back(take);
+  return DM_OK;
+}
+
+// One forked writeback tick's part in the queue calibration (dm_ctx::calib), called
+// before the tick forks.  Window boundaries join every class stream into the context
+// stream (so the next window's assignment starts after the last one's work: a class's
+// consecutive ticks on two streams are then still ordered) and record an event there.
+static hipError_t calib_apply(dm_ctx* c, const std::array<int, dm_ctx::kAux>& pm) {
+  hipError_t e = c->join_aux();
+  if (e != hipSuccess) return e;
+  for (int i = 0; i < dm_ctx::kAux; ++i) {
+    c->perm[i] = pm[(size_t)i];
+    c->aux[i] = c->aux_phys[pm[(size_t)i]];
+  }
+  c->main_dirty = true;  // the next tick forks: every class stream waits for the context stream
+  return hipSuccess;
+}
+
+static hipError_t calib_mark(dm_ctx* c, bool end) {
+  if (end) {
+    hipEvent_t ev;
+    hipError_t e = c->join_aux();
+    if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
+    if (e != hipSuccess) return e;
+    c->calib_ev.back().second = ev;
+    c->main_dirty = true;
+    return hipSuccess;
+  }
+  hipEvent_t ev;
+  hipError_t e = hipEventCreate(&ev);
+  if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
+  if (e != hipSuccess) return e;
+  c->calib_ev.push_back({ev, nullptr});
+  c->calib_of_ev.push_back(c->calib_k);
+  return hipSuccess;
+}
+
+void dm::calib_free(dm_ctx* c) {
+  for (auto& pr : c->calib_ev) {
+    if (pr.first) (void)hipEventDestroy(pr.first);
+    if (pr.second) (void)hipEventDestroy(pr.second);
+  }
+  c->calib_ev.clear();
+  c->calib_of_ev.clear();
+}
+
+static hipError_t calib_step(dm_ctx* c) {
+  if (c->calib == 4) return hipSuccess;
+  if (c->calib == 0) {
+    if (!c->aux_own_queue) {  // shared queues: the assignment does not choose hardware queues
+      c->calib = 4;
+      return hipSuccess;
+    }
+    if (++c->calib_skip < dm_ctx::kCalibSkip) return hipSuccess;
+    for (int i = 0; i < dm_ctx::kAux; ++i) c->aux_phys[i] = c->aux[i];
+    std::array<int, dm_ctx::kAux> pm{0, 1, 2, 3};
+    c->calib_cand.clear();
+    do c->calib_cand.push_back(pm);
+    while (std::next_permutation(pm.begin(), pm.end()));
+    c->calib = 1;
+    c->calib_round = 1;
+    c->calib_k = 0;
+    c->calib_t = 1;  // this tick is the window's first
+    hipError_t e = calib_apply(c, c->calib_cand[0]);
+    return e == hipSuccess ? calib_mark(c, false) : e;
+  }
+  if (c->calib == 1 || c->calib == 2) {
+    const int win = c->calib == 1 ? dm_ctx::kCalibWin : dm_ctx::kCalibWin2;
+    if (++c->calib_t <= win) return hipSuccess;
+    hipError_t e = calib_mark(c, true);
+    if (e != hipSuccess) return e;
+    c->calib_t = 1;
+    const int ncand = (int)c->calib_cand.size();
+    if (++c->calib_k < ncand) {
+      e = calib_apply(c, c->calib_cand[(size_t)c->calib_k]);
+      return e == hipSuccess ? calib_mark(c, false) : e;
+    }
+    c->calib = 3;  // wait for the windows' events (polled by later ticks)
+    return hipSuccess;
+  }
+  // calib == 3: the last window's end event done?  then pick
+  const hipError_t q = hipEventQuery(c->calib_ev.back().second);
+  if (q == hipErrorNotReady) return hipSuccess;
+  if (q != hipSuccess) return q;
+  std::vector<std::pair<float, size_t>> t;
+  for (size_t w = 0; w < c->calib_ev.size(); ++w) {
+    float ms = 0.0f;
+    hipError_t e = hipEventElapsedTime(&ms, c->calib_ev[w].first, c->calib_ev[w].second);
+    if (e != hipSuccess) return e;
+    t.push_back({ms, w});
+  }
+  if (c->calib_log) {  // test hook (DM_QUEUE_CALIB=2): every window's assignment and time per tick
+    const int win = c->calib_round == 1 ? dm_ctx::kCalibWin : dm_ctx::kCalibWin2;
+    for (const auto& pr : t) {
+      const auto& pm = c->calib_cand[(size_t)c->calib_of_ev[pr.second]];
+      fprintf(stderr, "[dm queue calibration] round %d perm %d%d%d%d %.2f us/tick\n", win == dm_ctx::kCalibWin ? 1 : 2,
+              pm[0], pm[1], pm[2], pm[3], 1000.0 * pr.first / win);
+    }
+  }
+  std::sort(t.begin(), t.end());
+  if (c->calib == 3 && c->calib_round == 1) {  // round 2: the best of round 1 over longer windows
+    // the best kCalibFinal of round 1, and the creation-order assignment (the measured
+    // default) so that the choice is never worse than not calibrating
+    std::vector<std::array<int, dm_ctx::kAux>> fin;
+    const std::array<int, dm_ctx::kAux> ident{0, 1, 2, 3};
+    for (int i = 0; i < dm_ctx::kCalibFinal; ++i) fin.push_back(c->calib_cand[(size_t)c->calib_of_ev[t[(size_t)i].second]]);
+    if (std::find(fin.begin(), fin.end(), ident) == fin.end()) fin.push_back(ident);
+    calib_free(c);
+    c->calib_cand.clear();
+    for (int r = 0; r < dm_ctx::kCalibRep2; ++r)  // interleaved: fin[0], fin[1], ..., fin[0], ...
+      c->calib_cand.insert(c->calib_cand.end(), fin.begin(), fin.end());
+    c->calib = 2;
+    c->calib_round = 2;
+    c->calib_k = 0;
+    c->calib_t = 1;
+    hipError_t e = calib_apply(c, c->calib_cand[0]);
+    return e == hipSuccess ? calib_mark(c, false) : e;
+  }
+  // round 2: each candidate's windows summed
+  std::vector<std::pair<std::array<int, dm_ctx::kAux>, float>> sum;
+  for (const auto& pr : t) {
+    const auto& pm = c->calib_cand[(size_t)c->calib_of_ev[pr.second]];
+    auto it = std::find_if(sum.begin(), sum.end(), [&](const auto& x) { return x.first == pm; });
+    if (it == sum.end()) sum.push_back({pm, pr.first});
+    else it->second += pr.first;
+  }
+  const auto best = std::min_element(sum.begin(), sum.end(), [](const auto& a, const auto& b) {
+                      return a.second < b.second;
+                    })->first;
+  calib_free(c);
+  c->calib = 4;
+  c->calib_best = best[0] + 4 * best[1] + 16 * best[2] + 64 * best[3];
+  return calib_apply(c, best);
+}
+
+// Once per row epoch, after a writeback tick of workgroup bin b's part j (split slot
+// i): count its items left without a dense hint (k_count_undense -> h_rec).  A count
+// of 0 lets the following ticks of the epoch skip the part's k_block_rest.
+static hipError_t check_dense(dm_ctx* c, int i, int b, int j, hipStream_t s) {
+  const int64_t lo = c->part_lo[b][j], n = c->part_lo[b][j + 1] - lo;
+  if (c->dq_ver_epoch[i] == c->row_epoch || n <= 0) return hipSuccess;
+  c->dq_ver_epoch[i] = c->row_epoch;
+  return launch_count_undense(c->bins[b].p + lo, (int)n, (unsigned long long*)(c->h_rec.d + 2 * i),
+                              (unsigned long long)c->row_epoch, s);
+}
+
+namespace {
+// One dm_apportion call: what its steps share, and the steps in the order they run.  Each
+// step returns DM_OK or the failure dm_apportion returns (DM_HIP returns from the step).
+struct Tick {
+  dm_ctx* c;
+  int64_t now_ns;
+  uint32_t flags;
+  bool wb = false, pingpong = false;
+  DevParams p{};
+  Partials P{};
+  hipStream_t st = nullptr, s_large = nullptr, s_small = nullptr;
+  int nch = 0;
+  int32_t *gl = nullptr, *gc = nullptr;  // k_general's worklist and its count
+  bool general = false, fork = false, one_class = false;
+  bool live_ok = false;
+  bool chain_live = false;  // this tick ran the (non-heterogeneous) chain
+
+  template <typename F>
+  hipError_t timed(int cls, hipStream_t s, F&& fn) {
+    return c->timed(cls, s, fn);
+  }
+  hipStream_t cls_stream(int cls) const { return fork ? c->aux[c->class_stream[cls]] : st; }
+
+  int outputs();      // the output columns and DevParams
+  int streams();      // the worklist, the streams in use and the fork
+  int large_chain();  // the large-resource chain
+  int subs();         // the sub-wave launch
+  int bins();         // the workgroup bins ...
+  int bin_part(int b, int lb, int nparts, bool split_dense, int j);  // ... and one stream part of one
+  int finish();       // the join, the general kernel and the state updates
+};
+
+int Tick::outputs() {
+  wb = flags & DM_WRITEBACK;
+  p.seg_off = c->seg_off.p;
+  p.wants = c->wants.p;
+  p.has = c->has.p;
+  p.sub = c->sub.p;
+  p.expiry = c->expiry.p;
+  p.cfg = c->cfg.p;
+  p.agg = c->agg.p;
+  p.expl = c->expl.p;
+  p.rmask = c->rmask.p;
+  // Every tick decides every row's lease (released rows included).  A writeback tick
+  // writes its gets in place, into the has column, where the dense kernels skip the
+  // gets store of every 64-row run the tick leaves unchanged (dm_tick_group.hip
+  // group_segment: a third of a quiescent resource's bytes).  It writes the alternate
+  // column, which becomes the store's has after the tick, when the caller asks for it,
+  // when it may take the speculative large chain (below), and on a store beyond the
+  // Infinity Cache whose rows a call has written since the last writeback tick (the row
+  // epoch): such a tick has little to skip, and separate columns stream ~2 % faster than
+  // reading and writing the same lines (C3 without the skip 427 against 435 us, C4's
+  // kernel 616 against 630 us).  A cache-resident store (C1)
+  // always preferred in place.  A store's ticks switch modes freely: after either kind
+  // c->has is complete.
+  if ((flags & DM_WB_INPLACE) && (flags & DM_WB_ALTERNATE))
+    return c->fail(DM_E_INVAL, "DM_WB_INPLACE and DM_WB_ALTERNATE are exclusive");
+  // The speculative large chain (below) writes its gets before they are verified, so a
+  // tick that may take it writes the alternate column whatever the store's size.
+  const bool spec_eligible = c->spec_chain && wb && !(flags & DM_AGG_RECOMPUTE) && !c->expl_rows &&
+                             !((c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0) &&
+                             !c->h_chunks.empty();
+  const bool stream_written = c->N * 48 > kStreamBytes && c->wb_epoch != c->row_epoch;
+  pingpong = wb && !(flags & DM_WB_INPLACE) &&
+             ((flags & DM_WB_ALTERNATE) || spec_eligible || stream_written);
+  if (wb) {
+    c->wb_inplace = pingpong ? 0 : 1;  // dm_plan_info slot 19
+    c->wb_epoch = c->row_epoch;
+  }
+  // A writeback tick writes no per-lease expiry: the leases it grants follow their
+  // resource's expiry (dm_device.h), so only gets (and rare subclients words) move.
+  if (!wb) {
+    DM_HIP(c, c->out_gets.ensure((size_t)std::max<int64_t>(c->N, 1)), "alloc out_gets");
+    DM_HIP(c, c->out_expiry.ensure((size_t)std::max<int64_t>(c->N, 1)), "alloc out_expiry");
+    p.out_gets = c->out_gets.p;
+    p.out_expiry = c->out_expiry.p;
+  } else if (pingpong) {
+    DM_HIP(c, c->out_gets.ensure((size_t)std::max<int64_t>(c->N, 1)), "alloc out_gets");
+    p.out_gets = c->out_gets.p;
+    p.out_expiry = nullptr;
+  } else {
+    p.out_gets = c->has.p;
+    p.out_expiry = nullptr;
+  }
+  p.writeback = wb ? 1 : 0;
+  if (wb) {
+    p.out_wants = c->wants.p;
+    p.out_sub = c->sub.p;
+    p.res = c->agg.p;
+  } else {
+    DM_HIP(c, c->res.ensure((size_t)std::max<int64_t>(c->R, 1)), "alloc res");
+    p.out_wants = nullptr;
+    p.out_sub = nullptr;
+    p.res = c->res.p;
+  }
+  p.now = now_ns;
+  p.recompute = (flags & DM_AGG_RECOMPUTE) ? 1 : 0;
+  live_ok = c->chain_live_ok;
+  c->chain_live_ok = false;
+  if (wb && !c->pub_ring.empty()) {
+    const int64_t n = (int64_t)c->pub_ring.size();
+    p.pub = c->pub_ring[(size_t)(c->pub_k % n)];
+    p.pub_clear = c->pub_ring[(size_t)((c->pub_k + 1) % n)];
+    p.pub_word = -1;  // (a split bin's parts set their own)
+    p.pub_first = 0;
+    c->pub_k += 1;
+  }
+  return DM_OK;
+}
+
+int Tick::streams() {
+  P = Partials{c->pa_cnt.p, c->pa_has.p, c->pa_wants.p, c->pa_cnt_all.p, c->pa_has_all.p, c->pa_wants_all.p,
+               c->pa_smin.p, c->pa_smax.p, c->pa_nan.p,
+               c->pb_x.p,   c->pb_y.p,   c->pb_w.p,     c->pc_ee.p,   c->pc_sgt.p,  c->pd_delta.p,
+               c->pa_live.p, c->p_tot.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  st = c->stream;
+  nch = (int)c->h_chunks.size();
+  gl = c->glist.p;
+  gc = c->gcount.p;
+  // (an asynchronous store batch still in flight may bring NaN wants or other subclient
+  // counts: the tick is ready for k_general until the batch is retired)
+  general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
+  if (general) {  // only non-small resources are ever appended to the worklist
+    DM_HIP(c, hipMemsetAsync(gc, 0, sizeof(int32_t), st), "worklist reset");
+    c->main_dirty = true;
+  }
+  // Independent work classes: large resources (a 5-kernel chain), big groups,
+  // small groups + packed.  With more than one class present they run on the
+  // auxiliary streams concurrently, forked from and joined back to the main stream.
+  unsigned used = 0;  // auxiliary streams with work this tick
+  for (int b = 0; b < kNumBins; ++b)
+    if (!c->h_bins[b].empty()) {
+      used |= 1u << c->class_stream[b];
+      if (c->bin_parts[b] > 1) used |= 1u << c->part_stream(b, 1);
+    }
+  if (!c->h_tiles.empty()) used |= 1u << c->class_stream[kNumBins];
+  if (nch > 0) used |= 1u << c->class_stream[kNumBins + 1];
+  fork = __builtin_popcount(used) > 1;
+  int nonempty_bins = 0;
+  for (int b = 0; b < kNumBins; ++b) nonempty_bins += c->h_bins[b].empty() ? 0 : 1;
+  // one work class (on the context stream, or in stream parts): its split bin's last
+  // kernel completes the tick's event (only check_dense's hint count may follow it)
+  bool parts_only = false;
+  for (int b = 0; b < kNumBins; ++b) parts_only |= !c->h_bins[b].empty() && c->bin_parts[b] > 1;
+  one_class = (!fork || parts_only) && nch == 0 && c->h_tiles.empty() && !general && nonempty_bins == 1;
+  if (fork && wb && c->tick_signal_wanted == false) DM_HIP(c, calib_step(c), "queue calibration");
+  s_large = cls_stream(kNumBins + 1);
+  s_small = cls_stream(kNumBins);
+  if (!fork) {  // everything on the context stream, after any deferred class work
+    DM_HIP(c, c->join_aux(), "join");
+    c->main_dirty = true;
+  } else if (c->main_dirty) {  // class streams wait for what the context stream holds
+    dm_ctx::XsTok fk;
+    DM_HIP(c, c->xs_signal(dm_ctx::XS_FORK, st, &fk), "fork");
+    for (int i = 0; i < dm_ctx::kAux; ++i) DM_HIP(c, c->xs_wait(fk, c->aux[i]), "fork");
+    c->main_dirty = false;
+  }
+  if (fork) c->aux_unjoined |= used;
+  return DM_OK;
+}
+
+int Tick::large_chain() {
+  const int nls = (int)c->h_large.size();
+  // heterogeneous-subclient FairShare is decided on the chain when the store may
+  // hold it (k_large_t, k_large_c_het, k_large_e, k_large_map_het)
+  const bool het = general && nch > 0;
+  if (het) {
+    const size_t nc = (size_t)nch, nl = (size_t)std::max(nls, 1);
+    if (c->ph_set_ready < nl || c->ph_set.n < nl * 2 * kHetMaxS) {
+      DM_HIP(c, c->ph_set.ensure(nl * 2 * kHetMaxS), "heterogeneous partials");
+      DM_HIP(c, c->ph_n.ensure(nl), "heterogeneous partials");
+      DM_HIP(c, hipMemsetAsync(c->ph_set.p, 0xFF, nl * 2 * kHetMaxS * sizeof(uint32_t), s_large), "heterogeneous sets");
+      DM_HIP(c, hipMemsetAsync(c->ph_n.p, 0, nl * sizeof(int32_t), s_large), "heterogeneous sets");
+      c->ph_set_ready = nl;
+    }
+    DM_HIP(c, c->ph_het.ensure(nl * sizeof(HetRes)), "heterogeneous partials");
+    DM_HIP(c, c->ph_bkw.ensure(nc * kHetBuckets), "heterogeneous partials");
+    DM_HIP(c, c->ph_bks.ensure(nc * kHetBuckets), "heterogeneous partials");
+    DM_HIP(c, c->ph_bkc.ensure(nc * kHetBuckets), "heterogeneous partials");
+    P.s_set = c->ph_set.p;
+    P.s_n = c->ph_n.p;
+    P.het = c->ph_het.p;
+    P.bk_w = c->ph_bkw.p;
+    P.bk_s = c->ph_bks.p;
+    P.bk_c = c->ph_bkc.p;
+  }
+  P.b_first = (!het && !p.recompute && !c->expl_rows) ? 1 : 0;
+  P.s_live = (!het && live_ok && !c->expl_rows) ? 1 : 0;
+  P.uni = c->p_uni.p;
+  // A, B, [T], C, [C_het, E], map, [map_het], fin
+  static constexpr int kSeq[9] = {0, 1, 5, 2, 6, 7, 3, 8, 4};
+  static constexpr int kCls[9] = {KC_LARGE_A, KC_LARGE_B,   KC_LARGE_T,  KC_LARGE_C,  KC_LARGE_CH,
+                                  KC_LARGE_E, KC_LARGE_MAP, KC_LARGE_MH, KC_LARGE_FIN};
+  // the steady state: one speculative launch, verified per resource, and a redo launch
+  // that only the resources whose totals moved use (the store's rows must not be
+  // overwritten by the speculative gets: alternate output columns)
+  const bool spec = c->spec_chain && !het && P.b_first && wb && p.out_gets != p.has && nch > 0;
+  if (spec) {
+    const SpecArgs S{c->p_spec.p, c->spec_seq, c->h_serr.d, c->p_spec_ring.p, (int)(c->spec_seq & 1), nch,
+                     reinterpret_cast<uint32_t*>(c->h_serr.d + 1), c->p_team.p, c->nslots};
+    c->spec_seq += 1;
+    const bool light = c->redo_light == 2 || (c->redo_light == 1 && c->redo_epoch == c->row_epoch &&
+                                              __atomic_exchange_n(c->h_serr.p + 1, 0, __ATOMIC_RELAXED) == 0);
+    c->redo_epoch = c->row_epoch;
+    const int redo_phase = light ? 2 : 1;
+    const int redo_grid = light ? c->team_grid_light : c->team_grid_full;
+    for (int ph = 0; ph < 2; ++ph)
+      DM_HIP(c, timed(ph == 0 ? KC_LARGE_SPEC : KC_LARGE_REDO, s_large,
+                      [&] {
+                        return launch_large_spec(ph == 0 ? 0 : redo_phase, p, c->chunks.p, nch, c->large.p, P, S,
+                                                 redo_grid, gl, gc, s_large);
+                      }),
+             "large-resource kernels");
+  }
+  for (int i = 0; i < 9 && nch > 0 && !spec; ++i) {
+    const int ph = kSeq[i];
+    if (ph >= 5 && !het) continue;
+    if (ph == 4 && !het) continue;  // the map's last-arriving chunks did fin's work
+    DM_HIP(c, timed(kCls[i], s_large,
+                    [&] { return launch_large(ph, p, c->chunks.p, nch, c->large.p, nls, P, gl, gc, s_large); }),
+           "large-resource kernels");
+  }
+  chain_live = nch > 0 && !het;
+  return DM_OK;
+}
+
+int Tick::subs() {
+  // the sub-wave bins (8x2, 16x2, 16x4, 32x4, 64x4) in one launch on bin 0's stream
+  SubBins sb{};
+  int nonempty = 0;
+  for (int k = 0; k < kSubShapes; ++k) {  // each sub-wave bin's items by shape (build_plan)
+    const int b = kSubShapeBin[k], n = (int)c->h_shape_n[k];
+    const int per = 256 / kSubShapeG[k];
+    sb.items[k] = c->bins[b].p + c->h_shape_lo[k];
+    sb.n[k] = n;
+    sb.blocks[k] = (n + per - 1) / per;
+    nonempty += n > 0;
+  }
+  if (nonempty > 0) {
+    hipStream_t s = cls_stream(0);
+    DM_HIP(c, timed(KC_SUBS, s, [&] { return launch_subs(p, sb, gl, gc, s); }), "sub-wave kernel");
+  }
+  return DM_OK;
+}
+
+int Tick::bin_part(int b, int lb, int nparts, bool split_dense, int j) {
+  const int64_t lo = c->part_lo[b][j];
+  const int n = (int)(c->part_lo[b][j + 1] - lo);
+  if (n == 0) return DM_OK;
+  WorkItem* items = c->bins[b].p + lo;
+  hipStream_t s = j == 0 ? cls_stream(b) : c->aux[c->part_stream(b, j)];
+  DevParams pj = p;
+  if (nparts > 1 && p.pub) {  // the part's own flags word (DevParams::pub_word)
+    pj.pub_word = j;
+    pj.pub_first = c->h_bins[b][(size_t)lo].seg;
+  }
+  // the tick's last kernel of this part (the dense kernel, or the rest kernel after
+  // it) completes the part's tick event when another queue waits for the tick
+  hipEvent_t done = nullptr;
+  if (one_class && c->tick_signal_wanted) {
+    done = c->tick_ev[j][c->tick_seq % dm_ctx::kTickEv];
+    c->tick_part_mask |= fork ? 1u << (j == 0 ? c->class_stream[b] : c->part_stream(b, j)) : 0u;
+  }
+  const int i = (b - 3) * dm_ctx::kParts + j;  // split slot (bins 3-6)
+  if (b >= 3 && b < 3 + dm_ctx::kSplitBins && ((c->dense_split >> (b - 3)) & 1) && split_dense) {
+    // only a writeback tick sets hints, so the split form follows one
+    const int par = c->dq_par[i];
+    const int64_t queued = __atomic_load_n(c->h_dq.p + i, __ATOMIC_RELAXED);
+    const bool good = 4 * queued <= n;
+    if (good) c->dq_wait[i] = 64;
+    if (good || ++c->dq_skip[i] >= c->dq_wait[i]) {
+      if (!good) c->dq_wait[i] = std::min(2 * c->dq_wait[i], 4096);
+      c->dq_skip[i] = 0;
+      // Every item verified dense in this row epoch: nothing can be queued, so the
+      // dense kernel is the part's only launch (the guard catches the impossible).
+      const uint64_t* rec = c->h_rec.p + 2 * i;
+      const bool verified = __atomic_load_n(rec + 1, __ATOMIC_ACQUIRE) == c->row_epoch;
+      const uint64_t counts = __atomic_load_n(rec, __ATOMIC_RELAXED);  // low half: items not dense
+      // The steady builds: every item verified dense and none with released rows or
+      // arrivals (the counts' high half), no recompute.  What the host cannot rule out
+      // is a lapse of the followers (lease lengths change on the device), so the steady
+      // kernel queues such an item and the rest kernel always follows it, with the
+      // tick's event; the guard is for launches that queue nothing.
+      // Not for a bin in stream parts: its ticks are short enough for the rest launch to
+      // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
+      // profiles/steady_ab.md).
+      const bool steady_form = c->steady_ok && nparts == 1 && verified && counts == 0 && !p.recompute;
+      const bool steady = steady_form && c->steady_ok != 2;
+      const bool skip = !steady_form && verified && (uint32_t)counts == 0;
+      if (steady) c->steady_mask |= 1u << i;
+      DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
+               return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
+                                       skip ? c->h_guard.d + i : nullptr, skip ? done : nullptr, steady, s);
+             }),
+             "group kernel (dense split)");
+      if (!skip) {
+        // the rest kernel strides over whatever the dense kernel queues; its grid is
+        // only sized from the last split tick's queue (a hint: correctness never
+        // depends on it): an empty queue costs 16 workgroups that read one count
+        const int rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, queued));
+        DM_HIP(c, timed(KC_REST3 + (b - 3), s, [&] {
+                 return launch_bin_rest(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, c->h_dq.d + i,
+                                        rest_grid, gl, gc, done, s);
+               }),
+               "group kernel (dense split)");
+        c->dq_par[i] ^= 1;
+      }
+      if (wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
+      return DM_OK;
+    }
+  }
+  if (done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
+    c->tick_flagged = false;
+    c->tick_part_mask = 0;
+  }
+  DM_HIP(c, timed(KC_BIN0 + b, s, [&] { return launch_bin(lb, pj, items, n, gl, gc, s); }), "group kernel");
+  if (b >= 3 && b < 3 + dm_ctx::kSplitBins && wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
+  return DM_OK;
+}
+
+int Tick::bins() {
+  // the workgroup bins split by the dense hint after a writeback tick (hints set)
+  const bool split_dense = c->hints_set;
+  c->steady_mask = 0;
+  for (int b = kNumBins - 1; b >= 0; --b) {
+    if (c->h_bins[b].empty()) continue;
+    if (b == 7 || b == 8 || b <= 2) continue;  // k_subs
+    const int lb = (b == 6 && c->bin6_wide)   ? kBin6Wide
+                   : (b == 4 && c->bin4_wave) ? kBin4Wave
+                                              : b;  // the launchers' bin (shape)
+    const int nparts = c->bin_parts[b];
+    if (one_class && c->tick_signal_wanted) {
+      c->tick_flagged = true;
+      c->tick_nev[c->tick_seq % dm_ctx::kTickEv] = nparts;
+      c->tick_part_mask = 0;
+    }
+    for (int j = 0; j < nparts; ++j)
+      if (int rc = bin_part(b, lb, nparts, split_dense, j)) return rc;
+  }
+  return DM_OK;
+}
+
+int Tick::finish() {
+  if (!c->h_tiles.empty())
+    DM_HIP(c, timed(KC_SMALL, s_small, [&] { return launch_tile_small(p, c->tiles.p, c->tile_list.p, (int)c->h_tiles.size(), s_small); }),
+           "small kernel");
+  if (fork) {
+    c->aux_pending = true;
+    // k_general consumes every class's worklist appends on the context stream
+    const bool defer = (flags & DM_ASYNC) && (flags & DM_DEFER_JOIN) && !general;
+    if (!defer) DM_HIP(c, c->join_aux(), "join");
+  }
+  if (general) {
+    const int blocks = (int)std::min<int64_t>(c->n_nonsmall, 1024);
+    DM_HIP(c, timed(KC_GENERAL, st, [&] { return launch_general(p, gl, gc, blocks, st); }), "general kernel");
+    c->main_dirty = true;
+  }
+  if (pingpong) std::swap(c->has, c->out_gets);  // the written column becomes the store's (stream order)
+  c->last_writeback = wb;
+  c->have_result = true;
+  if (wb) c->hints_set = true;
+  if (wb) c->expl_rows = false;
+  c->chain_live_ok = wb && chain_live;
+  if (!(flags & DM_ASYNC)) {
+    const int rc = c->synced("tick");
+    c->collect_profile();
+    return rc;
+  }
+  return DM_OK;
+}
+
+}  // namespace
+
+int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
+  DM_CHECK_CTX(c);
+  int rc = ready(c);
+  if (rc) return rc;
+  if (c->tpl_pipe && (rc = commit_templates(c))) return rc;
+  c->ticks_issued += 1;
+  c->tick_seq += 1;
+  c->tick_flagged = false;
+  Tick t{c, now_ns, flags};
+  if ((rc = t.outputs()) || (rc = t.streams()) || (rc = t.large_chain()) || (rc = t.subs()) ||
+      (rc = t.bins()))
+    return rc;
+  return t.finish();
+}

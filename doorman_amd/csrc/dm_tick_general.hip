@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void k_general(DevParams p, const int32_t* __r
 }
 
 // --------------------------------------------------------------------------
-// host-side launchers (called by dm_runtime.cpp)
+// host-side launchers (called by dm_tick.cpp)
 // --------------------------------------------------------------------------
 hipError_t launch_general(const DevParams& p, const int32_t* glist, const int32_t* gcount, int blocks,
                           hipStream_t st) {

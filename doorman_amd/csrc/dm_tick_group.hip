@@ -146,7 +146,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   const bool arr_lapse = arrivals && p.now > rs.follow_exp;
   if constexpr (MODE == kDenseOnly) {
     // STEADY (k_block_dense's steady builds, launched when the host knows of no released
-    // row, arrival or recompute in the part: dm_runtime.cpp): an item with a released-row
+    // row, arrival or recompute in the part: dm_tick.cpp): an item with a released-row
     // or arrival bit after all, or whose followers have lapsed (lease lengths change on
     // the device, so only the kernel can tell), goes to k_block_rest like a stale hint.
     // What is left has a known Clean (below), with no row examined.
@@ -408,7 +408,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // lapse together, ends it).
   // A resource with no live row left (its followers lapsed together) stays dense,
   // every row in its mask, so that a dense tick always leaves a dense resource dense
-  // (the host's skip of the rest kernel rests on it: dm_runtime.cpp).
+  // (the host's skip of the rest kernel rests on it: dm_tick.cpp).
   const int nlive = a.nlive;
   const int s_keep = (hw & 0xFF) ? (hw & 0xFF) : 1;
   const int dn = !(kDense && p.writeback) ? 0
@@ -463,11 +463,11 @@ __global__ __launch_bounds__(G, (G <= 256 && R == 8) ? 5 : 1) void k_block(DevPa
 // (qcnt[2]): a system-scope store to host memory keeps an otherwise empty launch
 // alive ~2 us longer, every tick of a dense store.
 // When the host skips k_block_rest (every item of the bin verified dense in this row
-// epoch, dm_runtime.cpp), `guard` (host-mapped) is set should the dense kernel queue
+// epoch, dm_tick.cpp), `guard` (host-mapped) is set should the dense kernel queue
 // an item after all, which the host reports as DM_E_INTERNAL (and refuses the store)
 // instead of leaving the item undecided unnoticed.  The tick's last kernel (this one,
 // or the rest kernel) is launched with the tick's stop event when another queue waits
-// for the tick (dm_runtime.cpp tick_ev).
+// for the tick (dm_ctx.h tick_ev).
 // (128 x 8 held to 7 waves per SIMD: 71 VGPRs + 20 B of spill, C3 430 -> 590 us; round 5.)
 // SKIP: the build a writeback tick in place runs (group_segment: unchanged runs of gets
 // are not stored); every other tick runs the build without it.
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(G) void k_block_rest(DevParams p, WorkItem* __restr
 // One workgroup: how many items of a workgroup bin are not dense after a writeback
 // tick, published to host-mapped memory as {count, epoch} (count first, the epoch
 // with release order) -- the host's once-per-epoch check before it skips the bin's
-// k_block_rest (dm_runtime.cpp).  The count word's high half counts the dense items
+// k_block_rest (dm_tick.cpp).  The count word's high half counts the dense items
 // whose hint word carries released rows or arrivals (bits 8, 9): with both halves zero
 // the host may launch the steady builds.
 __global__ __launch_bounds__(1024) void k_count_undense(const WorkItem* __restrict__ items, int n,
@@ -818,7 +818,7 @@ __global__ __launch_bounds__(256) void k_tile_small(DevParams p, const Tile* __r
 }
 
 // --------------------------------------------------------------------------
-// host-side launchers (called by dm_runtime.cpp)
+// host-side launchers (called by dm_tick.cpp)
 // --------------------------------------------------------------------------
 hipError_t launch_tile_small(const DevParams& p, const Tile* tiles, const TileEntry* list, int n, hipStream_t st) {
   if (n <= 0) return hipSuccess;

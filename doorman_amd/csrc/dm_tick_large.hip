@@ -884,7 +884,7 @@ __device__ __forceinline__ void spec_wait(const SpecArgs& S, const uint64_t* fla
 // other classes' waves much sooner (C2: 20 -> 10 us of event time, the tick -3.6 us),
 // while a redo of every large resource takes it about 2x as long.  The host launches
 // the light build while the last redo it saw found nothing marked and no row changed
-// since (dm_runtime.cpp); both leave the same bits.
+// since (dm_tick.cpp); both leave the same bits.
 __device__ __forceinline__ void redo_team(const DevParams& p, const Chunk* __restrict__ chunks,
                                           const LargeSeg* __restrict__ ls, const Partials& P, const SpecArgs& S,
                                           int32_t* glist, int32_t* gcount, int l, int m, Lds<256>& lds,
@@ -1315,7 +1315,7 @@ __global__ __launch_bounds__(256) void k_large_map_het(DevParams p, const Chunk*
 }
 
 // --------------------------------------------------------------------------
-// host-side launchers (called by dm_runtime.cpp)
+// host-side launchers (called by dm_tick.cpp)
 // --------------------------------------------------------------------------
 hipError_t launch_large(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls, int nls,
                         const Partials& P, int32_t* glist, int32_t* gcount, hipStream_t st) {
@@ -1349,7 +1349,7 @@ hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks,
 }
 
 // Workgroups of the redo's full build that one CU holds at once (the full build's grid:
-// up to 3/4 of what the GPU holds, dm_runtime.cpp).
+// up to 3/4 of what the GPU holds, dm_create in dm_runtime.cpp).
 int redo_blocks_per_cu() {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_large_redo_team<false>, 256, 0) != hipSuccess) return 1;

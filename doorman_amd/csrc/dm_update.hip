@@ -346,7 +346,7 @@ __global__ void k_gather_leases(int64_t n, const int64_t* __restrict__ rows, con
 }
 
 // --------------------------------------------------------------------------
-// host-side launchers (called by dm_runtime.cpp)
+// host-side launchers (called by dm_store.cpp and dm_store_update.cpp)
 // --------------------------------------------------------------------------
 hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
                          const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,

@@ -1,5 +1,5 @@
 """Store updates that turn a store general, through every call that maintains the host's
-routing state (dm_runtime.cpp: maybe_general, all_sub_one, and the window in which an
+routing state (dm_ctx.h: maybe_general, all_sub_one, and the window in which an
 asynchronous batch is pending).
 
 A FairShare resource whose live rows carry different subclient counts, or a NaN wants,

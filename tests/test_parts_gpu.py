@@ -1,4 +1,4 @@
-"""Stream parts (dm_runtime.cpp plan_parts): a store whose only work class is one
+"""Stream parts (dm_plan.cpp plan_parts): a store whose only work class is one
 workgroup bin of >= 4096 resources and <= 1 GiB of rows runs that bin as two launches
 over its halves, on two auxiliary streams, never joined from tick to tick under
 DM_DEFER_JOIN -- so part 0 of tick k + 1 may run beside part 1 of tick k.  The ticks

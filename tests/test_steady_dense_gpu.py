@@ -1,5 +1,5 @@
 """The steady builds of the dense tick kernel (dm_tick_group.hip group_segment STEADY,
-dm_runtime.cpp's launch policy).
+dm_tick.cpp's launch policy).
 
 A bin part whose items are all dense, none with a released row or an arrival, runs outside
 recompute mode a build of k_block_dense that takes Clean's result as known (nothing

@@ -2,7 +2,7 @@
 """Compare the gfx950 device code of two source trees, kernel for kernel.
 
 For a change that only moves kernels between translation units: every kernel unit of both
-trees (the Makefile's list in doorman_amd/csrc, and dm_runtime.cpp) is compiled to device assembly with the
+trees (the Makefile's lists in doorman_amd/csrc: the kernel units and the runtime's host units) is compiled to device assembly with the
 product's flags, the output is cut per function symbol, compiler-numbered local labels
 are renumbered per function (so a function's index in its unit does not matter), and
 the instruction text, the .amdhsa_* descriptor, the resource symbols and comment block
@@ -27,11 +27,16 @@ LABEL = re.compile(r"\.L([A-Za-z_]+?)(\d+)(_\d+)?\b")
 
 
 def units(tree):
-    """The tree's kernel units: what its Makefile lists, or every .hip file (a tree from before the list)."""
+    """The tree's kernel units: what its Makefile lists, or every .hip file (a tree from before the list);
+    then the runtime's host units: the Makefile's list, or dm_runtime.cpp alone (a tree from before that list)."""
     d = os.path.join(tree, "doorman_amd", "csrc")
-    r = subprocess.run(["make", "-s", "--no-print-directory", "print-units"], cwd=d, capture_output=True, text=True)
-    fs = r.stdout.split() if r.returncode == 0 else sorted(f for f in os.listdir(d) if f.endswith(".hip"))
-    return d, fs + ["dm_runtime.cpp"]
+
+    def listed(target):
+        r = subprocess.run(["make", "-s", "--no-print-directory", target], cwd=d, capture_output=True, text=True)
+        return r.stdout.split() if r.returncode == 0 else None
+
+    fs = listed("print-units") or sorted(f for f in os.listdir(d) if f.endswith(".hip"))
+    return d, fs + (listed("print-host-units") or ["dm_runtime.cpp"])
 
 
 def compile_unit(d, f, out):
@@ -140,7 +145,7 @@ def main():
         nf, nu = build(a.new, os.path.join(tmp, "new"), a.jobs)
     lines = ["# Device code, parent against new: kernel for kernel", "",
              "Every kernel unit compiled with `hipcc " + " ".join(FLAGS) + "`",
-             "(`dm_runtime.cpp` with `-x hip`), cut per function symbol, comments and `.file`/`.loc`/`.ident`",
+             "(the runtime's `.cpp` units with `-x hip`), cut per function symbol, comments and `.file`/`.loc`/`.ident`",
              "dropped, local labels renumbered per function (`tools/isa_diff.py PARENT NEW`).", "",
              "| tree | unit | kernels |", "|---|---|---|"]
     for name, u in (("parent", pu), ("new", nu)):
