@@ -278,6 +278,7 @@ struct dm_ctx {
   void rows_changed() {
     chain_live_ok = false;
     row_epoch += 1;
+    for (uint64_t& e : fix_live) e = 0;  // no fixed-point key is trusted across a write (below)
   }
   std::vector<int64_t> h_seg_off;
   std::vector<int64_t> h_refresh_s;
@@ -401,6 +402,22 @@ struct dm_ctx {
   // split-bin state below is per part: slot (b - 3) * kParts + part.
   static constexpr int kParts = 2;
   static constexpr int kSplitSlots = kSplitBins * kParts;
+  // Fixed points (dm_device.h FixKey, dm_tick_group.hip group_segment FIXED): a part that
+  // runs a steady build on a writeback tick in place runs the FIXED build, which keeps a
+  // key per item (fix_keys[b - 3], parallel to bins[b]) and loads no row of an item whose
+  // valid key matches its capacity and kind.  A valid key says that nothing but FIXED
+  // builds has touched the item's rows, running sums or state since it was set; the
+  // device cannot know that, so the host does: fix_live[slot] is the row epoch in which
+  // the part's last tick launched the FIXED build (0: it did not).  Keys are in use for a
+  // launch only while that is the current epoch; every other launch of the part (the
+  // mixed kernel, a plain or non-skipping dense build, an alternate-column, non-writeback
+  // or recompute tick, DM_STEADY=2) and every rows_changed() clears it, and the first
+  // FIXED launch after that ignores and rewrites every key.  DM_FIXED=0: never.
+  int fixed_ok = 1;
+  DBuf<FixKey> fix_keys[kSplitBins];
+  uint64_t fix_live[kSplitSlots] = {};
+  unsigned fixed_mask = 0;  // bit i: split slot i's last tick ran with keys in use (dm_plan_info slot 21)
+  DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
   int bin_parts[kNumBins] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
   // off for a leaf whose ticks an exchange on another stream waits for (dm_hier_attach):
   // there the exchange's two waits and the parts' CU share cost more than the parts

@@ -85,6 +85,22 @@ struct WorkItem {  // one resource of a size bin: no dependent load before its r
   int64_t lo;
 };
 
+// The fixed-point key of a work item of the workgroup bins (3-6), in an array parallel to
+// the bin's items and indexed like them (loaded beside the item: no dependent load).
+// valid: the item's last tick, a FIXED build of k_block_dense (dm_tick_group.hip), stored
+// no gets, reduced a delta of +0.0 and wrote back the record it read, outside learning
+// mode, computing with this capacity (Res::C as bits, the parent-expiry test applied) and
+// kind.  While nothing but such builds touches the item's rows, running sums or state
+// (the host's fix_live, dm_ctx.h), a tick that finds the same capacity and kind would
+// recompute the same sums, thresholds and gets, and loads no row.  Only those builds
+// read or write keys; the item's hint word is not involved.
+struct FixKey {
+  uint64_t cbits;
+  int32_t kind;
+  int32_t valid;
+};
+static_assert(sizeof(FixKey) == 16, "one 16-B scalar load per item");
+
 // The sub-wave bins of one tick for k_subs, in launch order, each bin in several
 // shapes G x R (G lanes per resource, R rows per lane; a bin's items ordered by shape,
 // build_plan): bin 7 (5-16 rows) 2x3 (5-6), 2x4 (7-8), 4x3 (9-12), 4x4 (13-16); bin 8 (17-32) 8x3 /

@@ -193,6 +193,8 @@ static void plan_parts(dm_ctx* c) {
 // kBin4Wave (dm_device.h): bin 4 in stream parts and most of its resources FairShare
 // by the loaded kinds.  (Without parts the shape did not pay: configs[3]'s N = 8 shard
 // and the whole configs[3] unchanged, its N = 4 shard +3 %, profiles/r05_ab/b4_one_wave.txt.)
+static int reset_keys(dm_ctx* c, int b, hipStream_t st);
+
 static bool bin4_prefers_wave(const dm_ctx* c) {
   const std::vector<WorkItem>& items = c->h_bins[4];
   if (items.empty() || c->bin_parts[4] < 2 || (int64_t)c->h_kind.size() != c->R) return false;
@@ -209,6 +211,16 @@ int dm::update_bin4_shape(dm_ctx* c, hipStream_t st) {
   if (wave == c->bin4_wave) return DM_OK;
   c->bin4_wave = wave;
   DM_HIP(c, upload(c->bins[4], c->h_bins[4].data(), c->h_bins[4].size(), st), "plan bins");
+  return reset_keys(c, 4, st);
+}
+
+// Wherever a workgroup bin's items are uploaded, its fixed-point keys start invalid, and
+// no part of it has keys in use (dm_ctx::fix_live).
+static int reset_keys(dm_ctx* c, int b, hipStream_t st) {
+  DBuf<FixKey>& k = c->fix_keys[b - 3];
+  DM_HIP(c, k.ensure(std::max<size_t>(c->h_bins[b].size(), 1)), "fixed-point keys");
+  DM_HIP(c, hipMemsetAsync(k.p, 0, k.n * sizeof(FixKey), st), "fixed-point keys");
+  for (int j = 0; j < dm_ctx::kParts; ++j) c->fix_live[(b - 3) * dm_ctx::kParts + j] = 0;
   return DM_OK;
 }
 
@@ -220,6 +232,7 @@ static int init_split_slots(dm_ctx* c, hipStream_t st) {
     __atomic_store_n(c->h_rec.p + 2 * i + 1, (uint64_t)0, __ATOMIC_RELAXED);
     __atomic_store_n(c->h_guard.p + i, 0, __ATOMIC_RELAXED);
     c->dq_ver_epoch[i] = 0;
+    c->fix_live[i] = 0;
     __atomic_store_n(c->h_dq.p + i, 0, __ATOMIC_RELAXED);
     c->dq_skip[i] = 0;
     c->dq_wait[i] = 64;
@@ -330,5 +343,9 @@ int dm::upload_plan(dm_ctx* c) {
     if (c->h_seg_off[r + 1] - c->h_seg_off[r] > kSmallMax) ++c->n_nonsmall;
   DM_HIP(c, c->glist.ensure((size_t)std::max<int64_t>(c->n_nonsmall, 1)), "worklist");
   DM_HIP(c, c->gcount.ensure(1), "worklist");
+  // (last: the allocations above keep their order)
+  for (int b = 3; b < 3 + dm_ctx::kSplitBins; ++b)
+    if (int rc = reset_keys(c, b, st)) return rc;
+  DM_HIP(c, c->fix_count.ensure(1), "fixed-point keys");
   return DM_OK;
 }

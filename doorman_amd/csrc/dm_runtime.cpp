@@ -170,6 +170,7 @@ int dm_create(int device, dm_ctx** out) {
     c->dense_split = v == 1 ? 0xF : (v & 0xF);
   }
   if (const char* sd = getenv("DM_STEADY")) c->steady_ok = atoi(sd);
+  if (const char* fx = getenv("DM_FIXED")) c->fixed_ok = atoi(fx) != 0;
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
   // hardware queue.  Plain streams share the process's GPU_MAX_HW_QUEUES (4) queues
@@ -319,7 +320,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[12 + kNumBins];
+  int64_t v[13 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -339,7 +340,8 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   // column, -1 before any writeback tick
   v[10 + kNumBins] = c->wb_inplace;
   v[11 + kNumBins] = __builtin_popcount(c->steady_mask);  // bin parts whose last tick ran a steady build
-  const int n = 12 + kNumBins;
+  v[12 + kNumBins] = __builtin_popcount(c->fixed_mask);   // ... and ran it with the fixed-point keys in use
+  const int n = 13 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }
@@ -360,7 +362,7 @@ int dm_store_stats(dm_ctx* c, int64_t* out, int max) {
   std::vector<uint8_t> ex((size_t)c->R);
   DM_HIP(c, download(ex.data(), (const uint8_t*)c->expl.p, 0, c->R, c->stream), "read row states");
   DM_HIP(c, hipStreamSynchronize(c->stream), "read row states");
-  int64_t v[4] = {0, 0, 0, 0};
+  int64_t v[5] = {0, 0, 0, 0, 0};
   for (int64_t r = 0; r < c->R; ++r) {
     if (ex[(size_t)r] >= 2) {
       v[0] += 1;
@@ -370,6 +372,18 @@ int dm_store_stats(dm_ctx* c, int64_t* out, int max) {
     }
   }
   v[3] = c->R;
-  for (int i = 0; i < 4 && i < max; ++i) out[i] = v[i];
-  return 4;
+  // the valid fixed-point keys of the parts whose keys are in use (dm_ctx::fix_live),
+  // counted here on demand, never by the tick
+  for (int i = 0; i < dm_ctx::kSplitSlots && max > 4; ++i) {
+    const int b = 3 + i / dm_ctx::kParts, j = i % dm_ctx::kParts;
+    const int64_t lo = c->part_lo[b][j], n = c->part_lo[b][j + 1] - lo;
+    if (n <= 0 || c->fix_live[i] != c->row_epoch || !c->fix_keys[b - 3].p) continue;
+    int32_t cnt = 0;
+    DM_HIP(c, launch_count_keys(c->fix_keys[b - 3].p + lo, (int)n, c->fix_count.p, c->stream), "count keys");
+    DM_HIP(c, download(&cnt, (const int32_t*)c->fix_count.p, 0, 1, c->stream), "count keys");
+    DM_HIP(c, hipStreamSynchronize(c->stream), "count keys");
+    v[4] += cnt;
+  }
+  for (int i = 0; i < 5 && i < max; ++i) out[i] = v[i];
+  return 5;
 }

@@ -497,9 +497,18 @@ int Tick::bin_part(int b, int lb, int nparts, bool split_dense, int j) {
       const bool steady = steady_form && c->steady_ok != 2;
       const bool skip = !steady_form && verified && (uint32_t)counts == 0;
       if (steady) c->steady_mask |= 1u << i;
+      // The FIXED build: a steady build on a writeback tick in place.  It may trust the
+      // items' keys when the part's last tick was one too, in this row epoch (fix_live,
+      // dm_ctx.h); otherwise it rewrites every key and the next one may.
+      const bool fixed = steady && c->fixed_ok && wb && pj.out_gets == pj.has;
+      const bool use_keys = fixed && c->fix_live[i] == c->row_epoch;
+      c->fix_live[i] = fixed ? c->row_epoch : 0;
+      if (use_keys) c->fixed_mask |= 1u << i;
+      FixKey* keys = fixed ? c->fix_keys[b - 3].p + lo : nullptr;
       DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
                return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
-                                       skip ? c->h_guard.d + i : nullptr, skip ? done : nullptr, steady, s);
+                                       skip ? c->h_guard.d + i : nullptr, skip ? done : nullptr, steady, keys,
+                                       use_keys, s);
              }),
              "group kernel (dense split)");
       if (!skip) {
@@ -518,6 +527,7 @@ int Tick::bin_part(int b, int lb, int nparts, bool split_dense, int j) {
       return DM_OK;
     }
   }
+  if (b >= 3 && b < 3 + dm_ctx::kSplitBins) c->fix_live[i] = 0;  // the mixed kernel keeps no key
   if (done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
     c->tick_flagged = false;
     c->tick_part_mask = 0;
@@ -531,6 +541,7 @@ int Tick::bins() {
   // the workgroup bins split by the dense hint after a writeback tick (hints set)
   const bool split_dense = c->hints_set;
   c->steady_mask = 0;
+  c->fixed_mask = 0;
   for (int b = kNumBins - 1; b >= 0; --b) {
     if (c->h_bins[b].empty()) continue;
     if (b == 7 || b == 8 || b <= 2) continue;  // k_subs

@@ -66,16 +66,27 @@ __device__ __forceinline__ double row_gets(const Res& rs, bool ps, double C, dou
   return fs_uniform_row(w, h, C, cl.sum_has, fu);
 }
 
-template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false>
+// Thread 0: the item's fixed-point key (dm_device.h FixKey) after this tick.  Stored only
+// when it differs from the one loaded, unless the launch does not use the keys: then
+// whatever the array holds is overwritten.
+__device__ __forceinline__ void put_key(FixKey* key, const FixKey& fk, int use_keys, bool fix, double C, int kind) {
+  const FixKey nk{fix ? (uint64_t)__double_as_longlong(C) : 0ull, fix ? kind : 0, fix ? 1 : 0};
+  if (!use_keys || nk.cbits != fk.cbits || nk.kind != fk.kind || nk.valid != fk.valid) *key = nk;
+}
+
+template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false, bool FIXED = false>
 __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
                                               Lds<G>& lds, int32_t* general_list, int32_t* general_count,
                                               int32_t* queue = nullptr, int32_t* qcount = nullptr,
-                                              int32_t qidx = 0, int32_t* guard = nullptr, int qcap = 0) {
+                                              int32_t qidx = 0, int32_t* guard = nullptr, int qcap = 0,
+                                              FixKey* key = nullptr, const FixKey fk = FixKey{0, 0, 0},
+                                              int use_keys = 0) {
   // the dense state (below): every workgroup kernel tracks it and writes the hints;
   // only the 128-thread mixed kernel and the dense-only kernels load by the hint
   constexpr bool kDense = G >= 128 || (G == 64 && R >= 16);  // (64 x 16: kBin4Wave)
   constexpr bool kHintLoad = (G == 128 && MODE == kMixed) || MODE == kDenseOnly;
   static_assert(!STEADY || MODE == kDenseOnly, "the steady build is a dense-only build");
+  static_assert(!FIXED || (SKIP && STEADY), "the fixed-point build is a steady build that skips unchanged stores");
   const int seg = wi.seg;
   const int64_t lo = wi.lo;
   const int n = kDense ? wi.n & 0xFFFF : wi.n;
@@ -118,7 +129,13 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   constexpr unsigned kRowBits = R >= 32 ? ~0u : (1u << R) - 1u;
   const bool arrivals = !STEADY && kDense && ((hw >> 9) & 1);
   bool by_hint = MODE == kDenseOnly;  // the rows' states come from the hint and the masks, not the column
-  if (MODE != kDenseOnly && !hint) {
+  // FIXED (k_block_dense's build for a steady part ticking in place, dm_tick.cpp): an item
+  // whose key is valid, in a launch that uses the keys, issues no row load before its
+  // record has confirmed or refuted the key (below); every other item loads first, as ever.
+  const bool keyed = FIXED && use_keys && fk.valid;
+  if (FIXED && keyed) {
+    // (the loads follow the record on a mismatch)
+  } else if (MODE != kDenseOnly && !hint) {
 #pragma unroll
     for (int k = 0; k < R; ++k) {
       const int i = k * G + t;
@@ -154,11 +171,33 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
     const bool rest = STEADY ? stale || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute : stale || arr_lapse;
     if (rest) {  // stale hint: k_block_rest reads the column
       if (t == 0) {
+        if constexpr (FIXED) put_key(key, fk, use_keys, false, 0.0, 0);  // before the hand-off
         const int q = atomicAdd(qcount, 1);
         if (q < qcap) queue[q] = qidx;  // at most one entry per item and tick (a guarded tick's count may grow)
         if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
       return;
+    }
+    if constexpr (FIXED) {
+      if (keyed) {
+        // The key's tick computed with this capacity and kind, outside learning mode, from
+        // the rows, running sums and state that are still there (FixKey): this tick would
+        // store no gets, reduce a delta of +0.0 and write the sums it read.  It writes the
+        // record as the full path would (follow_exp moves, the exchange's block is
+        // published, the state byte stays) and is done.
+        if (fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
+          if (t == 0) write_resource(p, seg, rs, Clean{rs.agg_count, rs.agg_has, rs.agg_wants}, 0.0, hint);
+          return;
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {  // refuted (the capacity or kind moved): one memory latency later than usual
+          const int i = k * G + t;
+          const unsigned u = (unsigned)(i < n ? i : n - 1);
+          w[k] = *col_at(wb, u);
+          h[k] = *col_at(hb, u);
+          sr[k] = hint;
+        }
+      }
     }
   } else if (kHintLoad && hint && (dense_subclients(rs) != hint || arr_lapse)) {
     relm = 0;  // the column says which rows are released now
@@ -309,6 +348,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
     if constexpr (STEADY) {
       if (b.i >= kNanOne) {  // FairShare with a NaN wants: k_general, as above (nothing is stored yet)
         if (t == 0) {
+          if constexpr (FIXED) put_key(key, fk, use_keys, false, 0.0, 0);  // before the hand-off
           general_list[atomicAdd(general_count, 1)] = seg;
           if (p.writeback && (wi.n >> 16)) item->n = n;
         }
@@ -350,6 +390,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // resource) stays.  Never on a non-writeback tick or on the alternate column, which
   // holds the tick before last: those run the build without it, the loop as it always was.
   SumD delta{0.0};
+  bool stored = false;  // FIXED: some run of this wave's gets is stored (wave-uniform)
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     if (!(valid >> k & 1)) continue;
@@ -358,6 +399,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
       const bool lv = live >> k & 1;
       const double g = lv ? row_gets(rs, ps, C, eq, cl, b, fu, w[k], h[k], s[k]) : 0.0;
       const bool st = __ballot(__double_as_longlong(g) != __double_as_longlong(h[k])) != 0;
+      if constexpr (FIXED) stored |= st;
       if (!lv) {  // released by Clean: no lease
         put_released<kGroupNT<G>>(p, lo, u, (relm >> k & 1) ? (int)kSubReleased : sr[k], st);
         continue;
@@ -415,6 +457,33 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
                  : nlive == 0              ? s_keep
                  : (a.smin == a.smax && a.smin >= 1 && a.smin <= 254) ? a.smin : 0;
   const int hw_next = dn ? (dn | (nlive < n ? 1 << 8 : 0)) : 0;
+  if constexpr (FIXED) {
+    // the delta's reduction in group_reduce's order, each wave's "stored a run" beside its
+    // partial behind the same barrier; then the key: the item is at its fixed point when
+    // no wave stored a run, the delta is +0.0 as bits and the sums written are the sums
+    // read (count and sum_wants are, in a steady build), outside learning mode
+    delta = wave_reduce_g<(G < 64 ? G : 64)>(delta, OpSumD());
+    int any = stored ? 1 : 0;
+    if constexpr (G > 64) {
+      if ((t & 63) == 0) lds.dn[t >> 6] = SumDN{delta.v, any, 0};
+      __syncthreads();
+      SumDN r = lds.dn[0];
+#pragma unroll 3
+      for (int i = 1; i < G / 64; ++i) {
+        const SumDN x = lds.dn[i];
+        r = SumDN{r.v + x.v, r.n | x.n, 0};
+      }
+      delta.v = r.v;
+      any = r.n;
+    }
+    if (t == 0) {
+      write_resource(p, seg, rs, cl, delta.v, hint);
+      const bool fix = !any && __double_as_longlong(delta.v) == 0 &&
+                       __double_as_longlong(cl.sum_has + delta.v) == __double_as_longlong(rs.agg_has) && !rs.learning;
+      put_key(key, fk, use_keys, fix, C, rs.kind);
+    }
+    return;
+  }
   delta = group_reduce<G, SumD, OpSumD, false>(delta, OpSumD(), lds.d);
   if constexpr (STEADY) {  // the state stays as it is: dn == hint, hw_next == hw, no mask to write
     if (t == 0) write_resource(p, seg, rs, cl, delta.v, hint);
@@ -493,6 +562,37 @@ __global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __rest
       group_segment<G, R, kDenseOnly, SKIP, STEADY>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
                                                     general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
                                                     nitems);
+    }
+  }
+}
+
+// FIXED: k_block_dense<G, R, true, true> for a part ticking in place, as a kernel of its own
+// name and arguments, so that the builds above stay the code they were.  Each item has a
+// key (dm_device.h FixKey; `keys` runs parallel to `items`) that the build sets when the
+// item's tick changed nothing, and clears when it did or hands the item to other code;
+// with use_keys (the part's last tick was this build too and no call has written rows
+// since: dm_ctx.h fix_live) an item whose key still matches its capacity and kind loads
+// no row at all.
+template <int G, int R>
+__global__ __launch_bounds__(G) void k_block_dense_fixed(DevParams p, WorkItem* __restrict__ items, int nitems,
+                                                         int32_t* queue, int32_t* qcnt, int par,
+                                                         int32_t* general_list, int32_t* general_count,
+                                                         int32_t* guard, FixKey* __restrict__ keys, int use_keys) {
+  __shared__ Lds<G> lds;
+  if ((int)blockIdx.x < nitems) {
+    const WorkItem wi = items[blockIdx.x];
+    const FixKey fk = keys[blockIdx.x];
+    if ((wi.n >> 16) == 0) {
+      if (threadIdx.x == 0) {
+        put_key(keys + blockIdx.x, fk, use_keys, false, 0.0, 0);  // before the hand-off
+        const int q = atomicAdd(qcnt + par, 1);
+        if (q < nitems) queue[q] = (int32_t)blockIdx.x;
+        if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    } else {
+      group_segment<G, R, kDenseOnly, true, true, true>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
+                                                        general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
+                                                        nitems, keys + blockIdx.x, fk, use_keys);
     }
   }
 }
@@ -881,15 +981,23 @@ hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, in
 // event: no marker packet of its own on the queue), for another stream to wait on
 // steady: the builds that take Clean's result as known and queue every item it is not
 // known for (group_segment STEADY); the caller launches the rest kernel after them.
+// keys (optional; only with steady, on a writeback tick in place): the FIXED build, over the
+// keys of these items; use_keys: valid keys may be trusted (else every key is rewritten).
 hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
                             int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
-                            hipStream_t st) {
+                            FixKey* keys, bool use_keys, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const dim3 grid((unsigned)n);
   // in place (the gets go to the column the has came from): the build that skips unchanged runs
   const bool skip = p.writeback && p.out_gets == p.has;
+  if (keys && !(skip && steady)) return hipErrorInvalidValue;
   const bool known = with_bin_shape(bin, [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    if (keys) {
+      hipExtLaunchKernelGGL((k_block_dense_fixed<G, R>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
+                            par, glist, gcount, guard, keys, use_keys ? 1 : 0);
+      return;
+    }
     with_bool(skip, [&](auto sk) {
       with_bool(steady, [&](auto sd) {
         hipExtLaunchKernelGGL((k_block_dense<G, R, decltype(sk)::value, decltype(sd)::value>), grid, dim3(G), 0, st,
@@ -898,6 +1006,25 @@ hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, 
     });
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// dm_store_stats: the valid keys among n (one workgroup, on demand; never on the tick)
+__global__ __launch_bounds__(1024) void k_count_keys(const FixKey* __restrict__ keys, int n, int32_t* out) {
+  __shared__ int part[16];
+  int c = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) c += keys[i].valid ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += part[w];
+    *out = tot;
+  }
+}
+hipError_t launch_count_keys(const FixKey* keys, int n, int32_t* out, hipStream_t st) {
+  k_count_keys<<<1, 1024, 0, st>>>(keys, n, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,

@@ -18,7 +18,7 @@ from .workloads import CFG_FIELDS
 _BIN_NAMES = ("small_tiles", "sub16x4", "sub32x4", "wave64x4", "block128x4", "block128x8", "block256x8",
               "block2k4k", "sub8x2", "sub16x2", "large_resources", "large_chunks", "leases", "bin_shapes",
               "redo_resident_cap", "spec_fits", "aux_own_queues", "stream_parts", "queue_perm", "wb_inplace",
-              "steady_parts")
+              "steady_parts", "fixed_parts")
 
 
 def _ptr(a):
@@ -355,11 +355,13 @@ class Engine:
 
     def store_stats(self) -> dict:
         """dm_store_stats: dense resources (read at 24 B per lease) and their rows,
-        resources that may hold explicit expiries, resources."""
-        arr = (ctypes.c_int64 * 4)()
-        self._chk(self._L.dm_store_stats(self._ctx, arr, 4))
+        resources that may hold explicit expiries, resources, and the workgroup-bin resources
+        whose fixed-point key is valid in a part whose keys are in use (their next in-place
+        tick loads no row of them while their capacity and kind stay)."""
+        arr = (ctypes.c_int64 * 5)()
+        self._chk(self._L.dm_store_stats(self._ctx, arr, 5))
         return {"dense_resources": int(arr[0]), "dense_leases": int(arr[1]), "explicit_resources": int(arr[2]),
-                "resources": int(arr[3])}
+                "resources": int(arr[3]), "fixed_items": int(arr[4])}
 
 
 def device_count() -> int:

@@ -49,8 +49,15 @@ extern "C" {
    before any writeback tick); slot 20 is the number of workgroup-bin parts whose last
    tick ran the steady builds of the dense kernel (every item dense with no released row
    or arrival: Clean's pass is left out; DM_STEADY=0 in the environment, read when the
-   context is created, keeps them off), and the call returns 21.  (Added slots, as slot
-   18 was: the version stays 7, which the clean and re-layout additions pinned.)
+   context is created, keeps them off), and the call returns 21; slot 21 is the number of
+   those parts whose last tick ran with the fixed-point keys in use (the FIXED build of the
+   dense kernel: a resource whose last tick changed nothing, and whose capacity and kind
+   are what that tick computed with, is not read at all; DM_FIXED=0 in the environment,
+   read when the context is created, keeps it off), and the call returns 22;
+   dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
+   are in use, and returns 5 (a caller that passes max = 4 gets the four it got).  (Added
+   slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
+   pinned.)
    6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
    without waiting; its outcome reported by a later call).
    5 (round 6): dm_store_lost (the read calls work on a lost store); dm_plan_info's slot 18 is the class streams' hardware-queue assignment the
@@ -519,11 +526,15 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * runs on the i-th auxiliary queue's perm[i]-th creation; timed on the context's first
  * forked writeback ticks, -1 until then), and the column the store's last writeback tick
  * wrote (1: the has column, in place; 0: the alternate column; -1: none yet), and the
- * workgroup-bin parts whose last tick ran the dense kernel's steady builds; returns 21 */
+ * workgroup-bin parts whose last tick ran the dense kernel's steady builds, and those of
+ * them that ran with the fixed-point keys in use; returns 22 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
- * their rows, resources that may hold explicit expiries, resources; returns 4 */
+ * their rows, resources that may hold explicit expiries, resources, and (only when max
+ * > 4: it is counted on the device on demand) the workgroup-bin resources whose
+ * fixed-point key is valid in a part whose keys are in use: while their capacity and kind
+ * stay, the next writeback tick in place loads no row of them; returns 5 */
 int dm_store_stats(dm_ctx* ctx, int64_t* out, int max);
 
 /* ---- round-oriented GetCapacity dispatch (dm_server.cpp) ----

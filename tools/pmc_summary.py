@@ -17,9 +17,9 @@ import sys
 
 CLASS = [
     # template args <G, R[, BATCH]>: BATCH 2 is the HBM-streaming variant of the same bin
-    (r"k_block_dense<128, 4(, \w+)*>", "block128x4_dense"), (r"k_block_dense<128, 8(, \w+)*>", "block128x8_dense"), (r"k_block_dense<64, 16(, \w+)*>", "block128x8_dense"),
-    (r"k_block_dense<256, 8(, \w+)*>", "block256x8_dense"), (r"k_block_dense<512, 8(, \w+)*>", "block2k4k_dense"),
-    (r"k_block_dense<256, 16(, \w+)*>", "block2k4k_dense"),
+    (r"k_block_dense(_fixed)?<128, 4(, \w+)*>", "block128x4_dense"), (r"k_block_dense(_fixed)?<128, 8(, \w+)*>", "block128x8_dense"), (r"k_block_dense(_fixed)?<64, 16(, \w+)*>", "block128x8_dense"),
+    (r"k_block_dense(_fixed)?<256, 8(, \w+)*>", "block256x8_dense"), (r"k_block_dense(_fixed)?<512, 8(, \w+)*>", "block2k4k_dense"),
+    (r"k_block_dense(_fixed)?<256, 16(, \w+)*>", "block2k4k_dense"),
     (r"k_publish\b", "hier_publish"), (r"k_hier_tick\b", "hier_root"),
     (r"k_tick_done\b", "tick_done"), (r"k_count_undense\b", "count_undense"),
     (r"k_large_spec\b", "large_spec"), (r"k_large_redo(_team)?\b", "large_redo"),

@@ -8,6 +8,11 @@
 Both dumps sample the same seeded rows (bench.DUMP_SEED).  Rows are grouped by resource
 (lease_rows // ROWS_PER_RESOURCE, 1000 for configs[3]): a resource counts as a fixed
 point when every sampled row of it is unchanged.
+
+fixed_share() adds what a tick that recognises such a resource before its passes has to
+see unchanged besides the rows: the record it reads (the running sums, and with the
+exchange the template's capacity and kind, which k_hier_tick rewrites every step).  A
+dump without templates (--hier off) has none to change.
 """
 import os
 import sys
@@ -15,15 +20,26 @@ import sys
 import numpy as np
 
 
-def share(dir_a, dir_b, per_res=1000):
-    ld = lambda d, n: np.load(os.path.join(d, n + ".npy"))
-    rows = ld(dir_a, "lease_rows").astype(np.int64)
-    assert np.array_equal(rows, ld(dir_b, "lease_rows").astype(np.int64)), "the dumps sample different rows"
-    same = ld(dir_a, "lease_gets").view(np.int64) == ld(dir_b, "lease_gets").view(np.int64)
-    res = rows // per_res
-    ids, inv = np.unique(res, return_inverse=True)
+def _ld(d, n):
+    p = os.path.join(d, n + ".npy")
+    return np.load(p) if os.path.exists(p) else None
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _rows_by_resource(dir_a, dir_b, per_res):
+    rows = _ld(dir_a, "lease_rows").astype(np.int64)
+    assert np.array_equal(rows, _ld(dir_b, "lease_rows").astype(np.int64)), "the dumps sample different rows"
+    same = _bits(_ld(dir_a, "lease_gets")) == _bits(_ld(dir_b, "lease_gets"))
+    ids, inv = np.unique(rows // per_res, return_inverse=True)
     changed = np.bincount(inv, weights=~same, minlength=len(ids))
-    fixed = changed == 0
+    return rows, same, ids, inv, changed == 0
+
+
+def share(dir_a, dir_b, per_res=1000):
+    rows, same, ids, inv, fixed = _rows_by_resource(dir_a, dir_b, per_res)
     # the kernel skips a wave's 64-row run: a sampled row's run is unchanged when every
     # sampled row of the same run is (an upper bound per run, exact per resource)
     return {"rows": int(len(rows)), "row_share": float(same.mean()),
@@ -32,7 +48,43 @@ def share(dir_a, dir_b, per_res=1000):
             "unchanged_rows_outside_fixed_resources": float((same & ~fixed[inv]).mean())}
 
 
+def fixed_share(dir_a, dir_b, per_res=1000):
+    """Per sampled resource: rows unchanged and record unchanged (it could skip its row
+    loads), and rows unchanged but record changed (it would pass the hint and fail the
+    confirmation), the latter split by what changed."""
+    _, _, ids, _, rows_same = _rows_by_resource(dir_a, dir_b, per_res)
+
+    def field_same(name):
+        a, b = _ld(dir_a, name), _ld(dir_b, name)
+        if a is None or b is None:
+            return None
+        return (_bits(a) == _bits(b))[ids]
+
+    tmpl = [field_same("template_capacity"), field_same("template_kind")]
+    have_tmpl = tmpl[0] is not None and tmpl[1] is not None
+    tmpl_same = tmpl[0] & tmpl[1] if have_tmpl else np.ones(len(ids), bool)
+    sums_same = np.ones(len(ids), bool)
+    for n in ("resource_count", "resource_sum_has", "resource_sum_wants"):
+        s = field_same(n)
+        if s is not None:
+            sums_same &= s
+    out = {"resources_sampled": int(len(ids)), "templates_in_dump": bool(have_tmpl),
+           "rows_unchanged": float(rows_same.mean()),
+           "rows_and_template_unchanged": float((rows_same & tmpl_same).mean()),
+           "rows_template_and_sums_unchanged": float((rows_same & tmpl_same & sums_same).mean()),
+           "rows_unchanged_template_changed": float((rows_same & ~tmpl_same).mean()),
+           "rows_unchanged_sums_changed": float((rows_same & ~sums_same).mean()),
+           "template_changed": float((~tmpl_same).mean())}
+    if have_tmpl:
+        out["rows_unchanged_capacity_changed"] = float((rows_same & ~tmpl[0]).mean())
+        out["rows_unchanged_kind_changed"] = float((rows_same & ~tmpl[1]).mean())
+    return out
+
+
 if __name__ == "__main__":
     per = int(sys.argv[3]) if len(sys.argv) > 3 else 1000
     for k, v in share(sys.argv[1], sys.argv[2], per).items():
+        print(f"{k:40s} {v}")
+    print()
+    for k, v in fixed_share(sys.argv[1], sys.argv[2], per).items():
         print(f"{k:40s} {v}")
