@@ -418,6 +418,19 @@ struct dm_ctx {
   uint64_t fix_live[kSplitSlots] = {};
   unsigned fixed_mask = 0;  // bit i: split slot i's last tick ran with keys in use (dm_plan_info slot 21)
   DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
+  // The sweep (dm_tick_group.hip k_fixed_sweep): a FIXED launch with keys in use runs as
+  // one lane per item, which finishes the items whose key holds and lists the others
+  // (sw_list[slot], one entry per item of the part at most), then the FIXED build over
+  // the list.  sw_cnt: the list's two-slot count ring, the last {count, epoch} told the
+  // host; sw_par: the ring slot of the next sweep; h_sw (host-mapped): {count, row epoch}
+  // per slot, from which the next launches' grids are sized.  DM_SWEEP=0: a FIXED launch
+  // with keys in use stays k_block_dense_fixed over every item.
+  int sweep_ok = 1;
+  DBuf<SweepEntry> sw_list[kSplitSlots];
+  DBuf<int32_t> sw_cnt[kSplitSlots];
+  int sw_par[kSplitSlots] = {};
+  HBuf<uint64_t> h_sw;
+  unsigned sweep_mask = 0;  // bit i: split slot i's last tick ran the sweep (dm_plan_info slot 22)
   int bin_parts[kNumBins] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
   // off for a leaf whose ticks an exchange on another stream waits for (dm_hier_attach):
   // there the exchange's two waits and the parts' CU share cost more than the parts

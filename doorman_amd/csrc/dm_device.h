@@ -101,6 +101,18 @@ struct FixKey {
 };
 static_assert(sizeof(FixKey) == 16, "one 16-B scalar load per item");
 
+// One entry of a part's sweep worklist (k_fixed_sweep -> k_block_dense_list,
+// dm_tick_group.hip): the work item's own fields and its index in the bin (its item and
+// its key), so that the entry is the row kernel's only load before the rows.
+struct SweepEntry {
+  int32_t seg;
+  int32_t n;  // WorkItem::n, the hint word included
+  int64_t lo;
+  int32_t idx;
+  int32_t pad[3];
+};
+static_assert(sizeof(SweepEntry) == 32, "one 32-B scalar load per entry");
+
 // The sub-wave bins of one tick for k_subs, in launch order, each bin in several
 // shapes G x R (G lanes per resource, R rows per lane; a bin's items ordered by shape,
 // build_plan): bin 7 (5-16 rows) 2x3 (5-6), 2x4 (7-8), 4x3 (9-12), 4x4 (13-16); bin 8 (17-32) 8x3 /

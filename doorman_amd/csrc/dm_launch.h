@@ -16,6 +16,10 @@ hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, in
 hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
                             int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
                             FixKey* keys, bool use_keys, hipStream_t st);
+hipError_t launch_bin_sweep(int bin, const DevParams& p, WorkItem* segs, int n, FixKey* keys, SweepEntry* list,
+                            int32_t* lcnt, int lpar, unsigned long long* host_count, unsigned long long epoch,
+                            int list_grid, int32_t* queue, int32_t* qcnt, int par, int32_t* glist, int32_t* gcount,
+                            hipStream_t st);
 hipError_t launch_count_keys(const FixKey* keys, int n, int32_t* out, hipStream_t st);
 hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,
                                 hipStream_t st);

@@ -242,6 +242,11 @@ static int init_split_slots(dm_ctx* c, hipStream_t st) {
     DM_HIP(c, c->dq_cnt[i].ensure(3), "dense split queue");  // two-slot count + the last count told the host
     DM_HIP(c, hipMemsetAsync(c->dq_cnt[i].p, 0, 3 * sizeof(int32_t), st), "dense split queue");
     c->dq_par[i] = 0;
+    // the sweep's count ring, where a tick has allocated it (dm_tick.cpp bin_part)
+    __atomic_store_n(c->h_sw.p + 2 * i, (uint64_t)0, __ATOMIC_RELAXED);
+    __atomic_store_n(c->h_sw.p + 2 * i + 1, (uint64_t)0, __ATOMIC_RELAXED);
+    if (c->sw_cnt[i].p) DM_HIP(c, hipMemsetAsync(c->sw_cnt[i].p, 0, 4 * sizeof(int32_t), st), "sweep count");
+    c->sw_par[i] = 0;
   }
   return DM_OK;
 }
@@ -285,6 +290,7 @@ int dm::upload_plan(dm_ctx* c) {
     DM_HIP(c, c->h_dq.alloc(dm_ctx::kSplitSlots, mapped), "dense split word");
     DM_HIP(c, c->h_rec.alloc(dm_ctx::kSplitSlots * 2, mapped), "dense split check");
     DM_HIP(c, c->h_guard.alloc(dm_ctx::kSplitSlots, mapped), "dense split guard");
+    DM_HIP(c, c->h_sw.alloc(dm_ctx::kSplitSlots * 2, mapped), "sweep count");
   }
   c->rows_changed();  // new work items: no hints
   {

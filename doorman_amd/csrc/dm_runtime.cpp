@@ -171,6 +171,7 @@ int dm_create(int device, dm_ctx** out) {
   }
   if (const char* sd = getenv("DM_STEADY")) c->steady_ok = atoi(sd);
   if (const char* fx = getenv("DM_FIXED")) c->fixed_ok = atoi(fx) != 0;
+  if (const char* sw = getenv("DM_SWEEP")) c->sweep_ok = atoi(sw) != 0;
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
   // hardware queue.  Plain streams share the process's GPU_MAX_HW_QUEUES (4) queues
@@ -320,7 +321,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[13 + kNumBins];
+  int64_t v[14 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -341,7 +342,8 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   v[10 + kNumBins] = c->wb_inplace;
   v[11 + kNumBins] = __builtin_popcount(c->steady_mask);  // bin parts whose last tick ran a steady build
   v[12 + kNumBins] = __builtin_popcount(c->fixed_mask);   // ... and ran it with the fixed-point keys in use
-  const int n = 13 + kNumBins;
+  v[13 + kNumBins] = __builtin_popcount(c->sweep_mask);   // ... as the sweep and the row kernel over its worklist
+  const int n = 14 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

@@ -505,12 +505,37 @@ int Tick::bin_part(int b, int lb, int nparts, bool split_dense, int j) {
       c->fix_live[i] = fixed ? c->row_epoch : 0;
       if (use_keys) c->fixed_mask |= 1u << i;
       FixKey* keys = fixed ? c->fix_keys[b - 3].p + lo : nullptr;
+      // The sweep: with keys in use, one lane per item finishes the items whose key holds
+      // and lists the others, and the FIXED build runs over the list (k_fixed_sweep).  Its
+      // grid is sized from the count the device last told in this row epoch, with a
+      // margin (a hint: the kernel strides over the list); the part's items until then.
+      const bool sweep = use_keys && c->sweep_ok;
+      int list_grid = n;
+      if (sweep) {
+        c->sweep_mask |= 1u << i;
+        DM_HIP(c, c->sw_list[i].ensure((size_t)n), "sweep list");
+        if (!c->sw_cnt[i].p) {
+          DM_HIP(c, c->sw_cnt[i].ensure(4), "sweep count");  // two-slot count + the last {count, epoch} told the host
+          DM_HIP(c, hipMemsetAsync(c->sw_cnt[i].p, 0, 4 * sizeof(int32_t), s), "sweep count");
+          c->sw_par[i] = 0;
+        }
+        const uint64_t* sw = c->h_sw.p + 2 * i;
+        if (__atomic_load_n(sw + 1, __ATOMIC_ACQUIRE) == c->row_epoch) {
+          const int64_t told = (int64_t)__atomic_load_n(sw, __ATOMIC_RELAXED);
+          list_grid = (int)std::min<int64_t>(n, std::max<int64_t>(16, told + told / 8 + (told ? 64 : 0)));
+        }
+      }
       DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
+               if (sweep)
+                 return launch_bin_sweep(lb, pj, items, n, keys, c->sw_list[i].p, c->sw_cnt[i].p, c->sw_par[i],
+                                         (unsigned long long*)(c->h_sw.d + 2 * i), (unsigned long long)c->row_epoch,
+                                         list_grid, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc, s);
                return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
                                        skip ? c->h_guard.d + i : nullptr, skip ? done : nullptr, steady, keys,
                                        use_keys, s);
              }),
              "group kernel (dense split)");
+      if (sweep) c->sw_par[i] ^= 1;
       if (!skip) {
         // the rest kernel strides over whatever the dense kernel queues; its grid is
         // only sized from the last split tick's queue (a hint: correctness never
@@ -542,6 +567,7 @@ int Tick::bins() {
   const bool split_dense = c->hints_set;
   c->steady_mask = 0;
   c->fixed_mask = 0;
+  c->sweep_mask = 0;
   for (int b = kNumBins - 1; b >= 0; --b) {
     if (c->h_bins[b].empty()) continue;
     if (b == 7 || b == 8 || b <= 2) continue;  // k_subs

@@ -74,7 +74,11 @@ __device__ __forceinline__ void put_key(FixKey* key, const FixKey& fk, int use_k
   if (!use_keys || nk.cbits != fk.cbits || nk.kind != fk.kind || nk.valid != fk.valid) *key = nk;
 }
 
-template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false, bool FIXED = false>
+// LIST: the caller is a loop over items (k_block_dense_list).  Behind an earlier item's
+// stores the compiler loads the record with vector loads, a register per dword and lane
+// through every pass (128 x 8: 88 VGPRs against 65); the record is moved back to SGPRs.
+template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false, bool FIXED = false,
+          bool LIST = false>
 __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
                                               Lds<G>& lds, int32_t* general_list, int32_t* general_count,
                                               int32_t* queue = nullptr, int32_t* qcount = nullptr,
@@ -157,7 +161,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
       sr[k] = hint;  // uniform: the mask's rows are taken out below (one register, not R)
     }
   }
-  const Res rs = load_res(p, seg);
+  const Res rs = LIST ? uniform(load_res(p, seg)) : load_res(p, seg);
   // arrivals outlive the followers (at or after follow_exp): only a tick past follow_exp
   // needs their own expiries, from the columns
   const bool arr_lapse = arrivals && p.now > rs.follow_exp;
@@ -597,6 +601,109 @@ __global__ __launch_bounds__(G) void k_block_dense_fixed(DevParams p, WorkItem* 
   }
 }
 
+// The sweep: a FIXED launch with keys in use (above) spends a workgroup on every item only
+// to find, from two scalar loads, that most need no rows (C3: 69,400 of 100,000; such a
+// launch over items all at their fixed point runs 55 us with no row loaded,
+// profiles/sweep_share.md).  That test is a lane's work.  k_fixed_sweep takes one lane per
+// item of the part: the item, its key and its record, exactly the tests of
+// group_segment<.., FIXED> before its rows (the steady `rest` test, a zero hint word, the
+// key against the record); an item that passes them all gets the same write_resource call
+// and is done, any other is appended to the part's worklist with its key in memory cleared.
+// k_block_dense_list then runs the FIXED build over the worklist alone: every item it sees
+// has an invalid key in memory, so it loads none (FixKey{0, 0, 0}), loads its rows at once
+// and stores a key only for an item that turns out fixed.  Everything behind the key test
+// (the rest queue, k_general's list, the keys) is group_segment's code as it was.
+// Appends: a ballot and prefix within the wave, one LDS step across the waves, one
+// returning atomicAdd per 1,024 items on the count word (one per item or wave on one word:
+// DESIGN.md section 3.1).  The list's order varies from run to run; no result depends on
+// it (resources are independent, each one's sums stay in its workgroup's fixed order).
+// lcnt is a two-slot ring as qcnt is: this tick's count in lcnt[par], the sweep clears
+// lcnt[par ^ 1]; the list kernel tells the host the count ({count, row epoch},
+// host-mapped: the next launches' grid size, a hint only) when either differs from the
+// last told (lcnt[2], lcnt[3]).
+__global__ __launch_bounds__(1024) void k_fixed_sweep(DevParams p, const WorkItem* __restrict__ items, int nitems,
+                                                      FixKey* __restrict__ keys, SweepEntry* __restrict__ list,
+                                                      int32_t* lcnt, int par) {
+  __shared__ int wtot[16];
+  const int i = (int)(blockIdx.x * 1024u + threadIdx.x);
+  if (i == 0) lcnt[par ^ 1] = 0;
+  bool app = false;
+  WorkItem wi{0, 0, 0};
+  if (i < nitems) {
+    wi = items[i];
+    const FixKey fk = keys[i];
+    const int hw = wi.n >> 16;
+    bool done = false;
+    if (hw != 0 && fk.valid) {
+      const Res rs = load_res(p, wi.seg);
+      const int hint = hw & 0xFF;
+      const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
+      if (!rest && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
+        write_resource(p, wi.seg, rs, Clean{rs.agg_count, rs.agg_has, rs.agg_wants}, 0.0, hint);
+        done = true;
+      }
+    }
+    if (!done) {
+      app = true;
+      if (fk.valid) keys[i] = FixKey{0, 0, 0};
+    }
+  }
+  const uint64_t bal = __ballot(app);
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wtot[wave] = __popcll(bal);
+  __syncthreads();
+  if (threadIdx.x == 0) {  // the waves' totals -> their first slots in the list
+    int tot = 0;
+    for (int w = 0; w < 16; ++w) tot += wtot[w];
+    int base = tot > 0 ? atomicAdd(lcnt + par, tot) : 0;
+    for (int w = 0; w < 16; ++w) {
+      const int c = wtot[w];
+      wtot[w] = base;
+      base += c;
+    }
+  }
+  __syncthreads();
+  const int slot = wtot[wave] + pre;  // (below nitems: the slot's count started at zero)
+  if (app && slot < nitems) list[slot] = SweepEntry{wi.seg, wi.n, wi.lo, i, {0, 0, 0}};
+}
+
+template <int G, int R>
+__global__ __launch_bounds__(G) void k_block_dense_list(DevParams p, WorkItem* __restrict__ items, int nitems,
+                                                        const SweepEntry* __restrict__ list, int32_t* lcnt, int lpar,
+                                                        unsigned long long* host_count, unsigned long long epoch,
+                                                        int32_t* queue, int32_t* qcnt, int par, int32_t* general_list,
+                                                        int32_t* general_count, FixKey* __restrict__ keys) {
+  __shared__ Lds<G> lds;
+  const int count = min(lcnt[lpar], nitems);
+  SweepEntry e = list[blockIdx.x];  // with the count (the grid is at most nitems: in the list, used only below count)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (lcnt[2] != count || lcnt[3] != (int32_t)epoch)) {
+    __hip_atomic_store(host_count, (unsigned long long)(unsigned)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    lcnt[2] = count;
+    lcnt[3] = (int32_t)epoch;
+  }
+  for (int q = blockIdx.x; q < count; q += gridDim.x) {
+    if (q != (int)blockIdx.x) e = uniform(list[q]);
+    const WorkItem wi{e.seg, e.n, e.lo};
+    // (the lane index anew for every item: what the compiler derives from it once for the
+    // whole loop stays in VGPRs across the item's passes: 103 against 65)
+    int t = (int)threadIdx.x;
+    asm volatile("" : "+v"(t));
+    if ((wi.n >> 16) == 0) {  // (its key is invalid in memory: the sweep saw to it)
+      if (threadIdx.x == 0) {
+        const int qi = atomicAdd(qcnt + par, 1);
+        if (qi < nitems) queue[qi] = e.idx;
+      }
+    } else {
+      group_segment<G, R, kDenseOnly, true, true, true, true>(p, wi, items + e.idx, t, lds, general_list,
+                                                              general_count, queue, qcnt + par, e.idx, nullptr, nitems,
+                                                              keys + e.idx, FixKey{0, 0, 0}, 1);
+    }
+    __syncthreads();  // the next item reuses the single-use LDS slots
+  }
+}
+
 template <int G, int R>
 __global__ __launch_bounds__(G) void k_block_rest(DevParams p, WorkItem* __restrict__ items,
                                                   const int32_t* __restrict__ queue, int32_t* qcnt, int par,
@@ -1004,6 +1111,25 @@ hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, 
                               nullptr, done, 0, p, segs, n, queue, qcnt, par, glist, gcount, guard);
       });
     });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// A FIXED launch with keys in use, as the sweep and the row kernel over its worklist
+// (k_fixed_sweep): the rest launch follows as after launch_bin_dense's steady builds.
+// list_grid: the row kernel's workgroups, a hint (it strides over the list).
+hipError_t launch_bin_sweep(int bin, const DevParams& p, WorkItem* segs, int n, FixKey* keys, SweepEntry* list,
+                            int32_t* lcnt, int lpar, unsigned long long* host_count, unsigned long long epoch,
+                            int list_grid, int32_t* queue, int32_t* qcnt, int par, int32_t* glist, int32_t* gcount,
+                            hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!(p.writeback && p.out_gets == p.has) || !keys) return hipErrorInvalidValue;
+  const dim3 lg((unsigned)std::max(1, std::min(n, list_grid)));
+  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    k_fixed_sweep<<<dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, st>>>(p, segs, n, keys, list, lcnt, lpar);
+    k_block_dense_list<G, R><<<lg, dim3(G), 0, st>>>(p, segs, n, list, lcnt, lpar, host_count, epoch, queue, qcnt, par,
+                                                     glist, gcount, keys);
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -53,7 +53,11 @@ extern "C" {
    those parts whose last tick ran with the fixed-point keys in use (the FIXED build of the
    dense kernel: a resource whose last tick changed nothing, and whose capacity and kind
    are what that tick computed with, is not read at all; DM_FIXED=0 in the environment,
-   read when the context is created, keeps it off), and the call returns 22;
+   read when the context is created, keeps it off), and the call returns 22; slot 22 is
+   the number of those parts whose last tick ran as the sweep (one lane per item finishes
+   the items whose key holds and lists the others; the dense kernel runs over the list;
+   DM_SWEEP=0 in the environment, read when the context is created, keeps the dense
+   kernel over every item), and the call returns 23;
    dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
    are in use, and returns 5 (a caller that passes max = 4 gets the four it got).  (Added
    slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
