@@ -22,6 +22,9 @@
 #include "../../include/doorman_hip.h"
 #include "dm_device.h"
 #include "dm_launch.h"
+#include "dm_split_form.h"
+
+struct dm_ctx;
 
 namespace dm {
 
@@ -168,6 +171,65 @@ struct ProfEvent {
   hipEvent_t a, b;
 };
 
+// One slot's words of a host-mapped allocation: the host's pointer and the device's.
+template <typename T>
+struct Mapped {
+  T *h = nullptr, *d = nullptr;
+};
+
+// The state of one stream part of one workgroup bin (bins 3-6): everything the part's
+// ticks (dm_tick.cpp bin_part, in the forms of dm_split_form.h) keep from one to the next.
+// dm_ctx::slot(b, j) finds it; a bin that is not in stream parts uses part 0's alone.
+struct SplitSlot {
+  int b = 3, j = 0;  // its bin and stream part
+  const int64_t* lo = nullptr;  // dm_ctx::part_lo[b] + j: its items are bins[b][lo[0] .. lo[1]) ...
+  int64_t items() const { return lo[1] - lo[0]; }
+  const DBuf<FixKey>* bin_keys = nullptr;  // ... and its keys that range of dm_ctx::fix_keys[b - 3]
+  FixKey* keys() const { return bin_keys->p + lo[0]; }
+  // The rest queue (k_block_dense appends, k_block_rest decides), one entry per item at
+  // most; qcnt: its two-slot count ring and the last count told the host; qpar: the ring
+  // slot of the next split tick.  queued (host-mapped): items the last split tick queued,
+  // from which try_split decides with skip (ticks in the one-kernel form since the split
+  // was last tried) and wait (ticks before the next try).
+  DBuf<int32_t> queue, qcnt;
+  int qpar = 0, skip = 0, wait = 64;
+  Mapped<int32_t> queued;
+  // host-mapped: {undense counts, epoch} of the row epoch's density check
+  // (k_count_undense, enqueued in ver_epoch), and the guard a dense kernel sets should
+  // it queue an item on a tick whose rest kernel was skipped (dm_ctx::check_device)
+  Mapped<uint64_t> rec;
+  Mapped<int32_t> guard;
+  uint64_t ver_epoch = 0;
+  // The row epoch in which the part's last tick launched the FIXED build, which keeps a
+  // key per item (0: it did not): keys are trusted only while this is the current epoch.
+  // bin_part assigns it from choose_form's result (PartForm::fix_live has the rule and
+  // why the host keeps it); rows_changed() and dm_ctx::reset_keys clear it.
+  uint64_t fix_live = 0;
+  // The sweep (k_fixed_sweep) lists the items whose key does not hold in sw_list, one
+  // entry per item at most.  sw_cnt: the list's two-slot count ring and the last {count,
+  // epoch} told the host; lpar: the ring slot of the next sweep; sweep (host-mapped):
+  // {count, row epoch}, which sizes the next grids.  Allocated by the first tick that sweeps.
+  DBuf<SweepEntry> sw_list;
+  DBuf<int32_t> sw_cnt;
+  int lpar = 0;
+  Mapped<uint64_t> sweep;
+  PartForm last;  // its last tick's form (all clear: no launch); dm_plan_info slots 20-22 count these
+  // What the device last told the host, for the form's choice: each record's epoch first,
+  // with acquire order (the device stores the count, then the epoch with release order).
+  // Only the words the choice can use are read, as ever: the queued count for a part that
+  // may split, the records for one that tries to, the sweep's where keys may be in use.
+  int64_t read_queued() const { return __atomic_load_n(queued.h, __ATOMIC_RELAXED); }
+  void read_records(FormInputs& in) const {
+    in.rec_epoch = __atomic_load_n(rec.h + 1, __ATOMIC_ACQUIRE);
+    in.rec_counts = __atomic_load_n(rec.h, __ATOMIC_RELAXED);
+    if (in.fix_live != in.row_epoch) return;
+    in.sw_epoch = __atomic_load_n(sweep.h + 1, __ATOMIC_ACQUIRE);
+    in.sw_told = (int64_t)__atomic_load_n(sweep.h, __ATOMIC_RELAXED);
+  }
+  int reset(dm_ctx* c, hipStream_t st);  // a new plan, or parts turned on or off (dm_plan.cpp)
+};
+static_assert(!std::is_copy_constructible<SplitSlot>::value, "a split slot owns its queues");
+
 }  // namespace dm
 
 using namespace dm;
@@ -278,7 +340,7 @@ struct dm_ctx {
   void rows_changed() {
     chain_live_ok = false;
     row_epoch += 1;
-    for (uint64_t& e : fix_live) e = 0;  // no fixed-point key is trusted across a write (below)
+    for (SplitSlot& s : split) s.fix_live = 0;  // no fixed-point key is trusted across a write (SplitSlot)
   }
   std::vector<int64_t> h_seg_off;
   std::vector<int64_t> h_refresh_s;
@@ -376,22 +438,18 @@ struct dm_ctx {
   // the sub-wave bins run in one launch (k_subs): C2 tick 144-145 -> 138 us against
   // one launch per bin (tools/ab.py, both orders, one box; the per-bin form was
   // retired in round 5)
-  // The 128-thread bins (3, 4) split by the dense hint (k_block_dense + k_block_rest)
-  // on a tick that follows a writeback tick (only those set hints), unless the last
-  // split tick the host has heard of queued more than a quarter of the bin's items
-  // for k_block_rest (then it tries again after 64 ticks, doubling the wait after every
-  // try that still queued too many, up to 4096: C2's bins, whose resources keep
-  // released rows, run 21 % slower split, and a try's k_block_rest strides over
-  // thousands of items).  DM_DENSE_SPLIT=0: never split.
+  // The workgroup bins (3-6) split by the dense hint (k_block_dense + k_block_rest) on a
+  // tick that follows a writeback tick (only those set hints), unless the split form's
+  // back-off says no (dm_split_form.h try_split).  DM_DENSE_SPLIT=0: never split.
   int dense_split = 0xF;  // bit i: bin 3+i runs in the split form (DM_DENSE_SPLIT: 0 off, 1 all, else the mask)
   static constexpr int kSplitBins = 4;  // bins 3..6
+  static bool is_split_bin(int b) { return b >= 3 && b < 3 + kSplitBins; }
   // A split part whose items are all verified dense, none with released rows or arrivals
   // (k_count_undense's two counts), runs the steady builds of k_block_dense outside
   // recompute mode: Clean's result is known, so its pass is left out (dm_tick_group.hip
   // group_segment STEADY).  DM_STEADY=0: never; 2 (A/B only): the steady ticks' launches,
   // dense then rest, with the plain builds: what the trailing rest launch costs.
   int steady_ok = 1;
-  unsigned steady_mask = 0;  // bit i: split slot i's last tick ran a steady build (dm_plan_info slot 20)
   // Stream parts: a workgroup bin that is the store's only work class, and small enough
   // that a launch's ramp and drain are a visible share of it, runs as kParts launches
   // over contiguous halves of its items on two auxiliary streams, never joined from
@@ -399,58 +457,52 @@ struct dm_ctx {
   // drains, so the GPU never idles between ticks (an N = 8 shard of configs[3], 12.5M
   // leases: 57.3 -> 48.8 us per tick, tools/shard_split.py; the whole configs[3], 100M
   // leases: 430 -> 425 us, not worth its cross-queue waits in the exchange).  Every
-  // split-bin state below is per part: slot (b - 3) * kParts + part.
+  // split-bin state is per part: the split slot (SplitSlot) of bin b's part j.
   static constexpr int kParts = 2;
   static constexpr int kSplitSlots = kSplitBins * kParts;
-  // Fixed points (dm_device.h FixKey, dm_tick_group.hip group_segment FIXED): a part that
-  // runs a steady build on a writeback tick in place runs the FIXED build, which keeps a
-  // key per item (fix_keys[b - 3], parallel to bins[b]) and loads no row of an item whose
-  // valid key matches its capacity and kind.  A valid key says that nothing but FIXED
-  // builds has touched the item's rows, running sums or state since it was set; the
-  // device cannot know that, so the host does: fix_live[slot] is the row epoch in which
-  // the part's last tick launched the FIXED build (0: it did not).  Keys are in use for a
-  // launch only while that is the current epoch; every other launch of the part (the
-  // mixed kernel, a plain or non-skipping dense build, an alternate-column, non-writeback
-  // or recompute tick, DM_STEADY=2) and every rows_changed() clears it, and the first
-  // FIXED launch after that ignores and rewrites every key.  DM_FIXED=0: never.
+  SplitSlot split[kSplitSlots];
+  static int slot_of(int b, int j) { return (b - 3) * kParts + j; }
+  static int slot_bin(int i) { return 3 + i / kParts; }  // slot_of's inverse
+  static int slot_part(int i) { return i % kParts; }
+  SplitSlot& slot(int b, int j) { return split[slot_of(b, j)]; }
+  // DM_FIXED=0: no part runs the FIXED build (SplitSlot::fix_live).  fix_keys[b - 3]: the
+  // keys of bin b's items, parallel to bins[b]; each slot sees its part's (SplitSlot::keys).
   int fixed_ok = 1;
   DBuf<FixKey> fix_keys[kSplitBins];
-  uint64_t fix_live[kSplitSlots] = {};
-  unsigned fixed_mask = 0;  // bit i: split slot i's last tick ran with keys in use (dm_plan_info slot 21)
   DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
-  // The sweep (dm_tick_group.hip k_fixed_sweep): a FIXED launch with keys in use runs as
-  // one lane per item, which finishes the items whose key holds and lists the others
-  // (sw_list[slot], one entry per item of the part at most), then the FIXED build over
-  // the list.  sw_cnt: the list's two-slot count ring, the last {count, epoch} told the
-  // host; sw_par: the ring slot of the next sweep; h_sw (host-mapped): {count, row epoch}
-  // per slot, from which the next launches' grids are sized.  DM_SWEEP=0: a FIXED launch
-  // with keys in use stays k_block_dense_fixed over every item.
+  // Wherever a workgroup bin's items are uploaded, its fixed-point keys start invalid, and
+  // no part of it has keys in use.
+  hipError_t reset_keys(int b, hipStream_t st) {
+    DBuf<FixKey>& k = fix_keys[b - 3];
+    hipError_t e = k.ensure(std::max<size_t>(h_bins[b].size(), 1));
+    if (e == hipSuccess) e = hipMemsetAsync(k.p, 0, k.n * sizeof(FixKey), st);
+    for (int j = 0; j < kParts; ++j) slot(b, j).fix_live = 0;
+    return e;
+  }
+  // DM_SWEEP=0: a FIXED launch with keys in use stays k_block_dense_fixed over every item.
   int sweep_ok = 1;
-  DBuf<SweepEntry> sw_list[kSplitSlots];
-  DBuf<int32_t> sw_cnt[kSplitSlots];
-  int sw_par[kSplitSlots] = {};
-  HBuf<uint64_t> h_sw;
-  unsigned sweep_mask = 0;  // bit i: split slot i's last tick ran the sweep (dm_plan_info slot 22)
   int bin_parts[kNumBins] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
   // off for a leaf whose ticks an exchange on another stream waits for (dm_hier_attach):
   // there the exchange's two waits and the parts' CU share cost more than the parts
   // gain (the N = 8 rehearsal step 58.7 -> 66 us; one wait: 60-62 us; round 5)
   bool parts_ok = true;
   int64_t part_lo[kNumBins][kParts + 1] = {};  // item bounds of each part
-  DBuf<int32_t> dq_list[kSplitSlots], dq_cnt[kSplitSlots];
-  int dq_par[kSplitSlots] = {};
-  int dq_skip[kSplitSlots] = {};   // ticks in the one-kernel form since the split was last tried
-  int dq_wait[kSplitSlots] = {64, 64, 64, 64, 64, 64, 64, 64};  // ticks before the next try
   bool bin6_wide = false;  // bin 6 on 512 x 8 workgroups (kBin6Wide): it holds most of the rows
   bool bin4_wave = false;  // bin 4 on one wave per resource (kBin4Wave): most of its resources FairShare
   std::vector<int32_t> h_kind;  // the loaded configuration's kinds (bin 4's shape)
-  HBuf<int32_t> h_dq;  // host-mapped: items the last split tick queued, per bin
-  // host-mapped, per split bin: {undense count, epoch} of the epoch's check
-  // (k_count_undense), and the guard a dense kernel sets should it queue an item on a
-  // tick whose rest kernel was skipped
-  HBuf<uint64_t> h_rec;
-  HBuf<int32_t> h_guard;
-  uint64_t dq_ver_epoch[kSplitSlots] = {};  // the epoch each slot's check was enqueued in
+  // The split slots' host-mapped words, one allocation per kind (upload_plan), reached
+  // through the slots: a word per slot of h_dq and h_guard, two of h_rec and h_sw.
+  HBuf<int32_t> h_dq, h_guard;
+  HBuf<uint64_t> h_rec, h_sw;
+  void bind_split_slots() {  // once, when the words exist
+    for (int i = 0; i < kSplitSlots; ++i) {
+      SplitSlot& s = split[i];
+      s.b = slot_bin(i), s.j = slot_part(i);
+      s.lo = part_lo[s.b] + s.j, s.bin_keys = &fix_keys[s.b - 3];
+      s.queued = {h_dq.p + i, h_dq.d + i}, s.guard = {h_guard.p + i, h_guard.d + i};
+      s.rec = {h_rec.p + 2 * i, h_rec.d + 2 * i}, s.sweep = {h_sw.p + 2 * i, h_sw.d + 2 * i};
+    }
+  }
   // large-path partials
   DBuf<int64_t> pa_cnt, pa_cnt_all, pa_smin, pa_smax, pb_w, pc_sgt;
   DBuf<double> pa_has, pa_wants, pa_has_all, pa_wants_all, pb_x, pb_y, pc_ee, pd_delta;
@@ -662,8 +714,8 @@ struct dm_ctx {
   // that touches the store and after every host wait that may have completed a tick.
   int check_device() {
     if (!store_lost) {
-      for (int i = 0; h_guard.p && i < kSplitSlots; ++i)
-        if (__atomic_load_n(h_guard.p + i, __ATOMIC_RELAXED)) {
+      for (const SplitSlot& s : split)
+        if (s.guard.h && __atomic_load_n(s.guard.h, __ATOMIC_RELAXED)) {
           store_lost = true;
           lost_msg = "a dense kernel queued an item on a tick that skipped its rest kernel";
         }

@@ -10,22 +10,39 @@
 namespace dm {
 // dm_tick_group.hip
 hipError_t launch_tile_small(const DevParams& p, const Tile* tiles, const TileEntry* list, int n, hipStream_t st);
-hipError_t launch_bin(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* glist, int32_t* gcount,
-                      hipStream_t st);
+// The workgroup bins' launchers (bins 3-6) take the launch's items as one argument, and
+// the split form's take the device side of the part's split slot (dm_ctx.h SplitSlot) as
+// another.  Host-side only: each launcher unpacks them into its kernel's own arguments.
+struct BinItems {
+  int bin;  // the shape: the bin, or kBin4Wave / kBin6Wide
+  WorkItem* items;
+  int n;
+};
+struct SplitArgs {
+  int32_t *queue, *qcnt;  // the rest queue and its count ring ...
+  int par;                // ... and this tick's slot of it
+  int32_t *glist, *gcount;  // k_general's worklist and its count
+  int32_t* guard;  // (host-mapped, or null) set should the launch queue an item
+};
+struct SweepArgs {
+  FixKey* keys;
+  SweepEntry* list;  // the sweep's worklist, ...
+  int32_t* lcnt;     // ... its count ring ...
+  int lpar;          // ... and this tick's slot of it
+  unsigned long long *host_count, epoch;  // (host-mapped) where the row kernel tells {count, row epoch}
+  int list_grid;  // the row kernel's workgroups, a hint (it strides over the list)
+};
+hipError_t launch_bin(const BinItems& w, const DevParams& p, int32_t* glist, int32_t* gcount, hipStream_t st);
 hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, int32_t* gcount, hipStream_t st);
-hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
+hipError_t launch_bin_dense(const BinItems& w, const DevParams& p, const SplitArgs& a, hipEvent_t done, bool steady,
                             FixKey* keys, bool use_keys, hipStream_t st);
-hipError_t launch_bin_sweep(int bin, const DevParams& p, WorkItem* segs, int n, FixKey* keys, SweepEntry* list,
-                            int32_t* lcnt, int lpar, unsigned long long* host_count, unsigned long long epoch,
-                            int list_grid, int32_t* queue, int32_t* qcnt, int par, int32_t* glist, int32_t* gcount,
+hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
                             hipStream_t st);
 hipError_t launch_count_keys(const FixKey* keys, int n, int32_t* out, hipStream_t st);
 hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,
                                 hipStream_t st);
-hipError_t launch_bin_rest(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                           int32_t* host_count, int rest_grid, int32_t* glist, int32_t* gcount, hipEvent_t done,
-                           hipStream_t st);
+hipError_t launch_bin_rest(const BinItems& w, const DevParams& p, const SplitArgs& a, int32_t* host_count,
+                           int rest_grid, hipEvent_t done, hipStream_t st);
 // dm_tick_large.hip
 int redo_blocks_per_cu();
 hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls,

@@ -181,7 +181,7 @@ static void plan_parts(dm_ctx* c) {
     }
   for (int b = 0; b < kNumBins; ++b) {
     const int64_t n = (int64_t)c->h_bins[b].size();
-    const bool split = c->parts_ok && nonempty == 1 && only == b && b >= 3 && b < 3 + dm_ctx::kSplitBins && c->h_tiles.empty() &&
+    const bool split = c->parts_ok && nonempty == 1 && only == b && dm_ctx::is_split_bin(b) && c->h_tiles.empty() &&
                        c->h_chunks.empty() && !c->maybe_general && n >= kPartMinItems && c->N * 28 <= kPartBytes;
     c->bin_parts[b] = split ? dm_ctx::kParts : 1;
     for (int j = 0; j <= dm_ctx::kParts; ++j)
@@ -193,8 +193,6 @@ static void plan_parts(dm_ctx* c) {
 // kBin4Wave (dm_device.h): bin 4 in stream parts and most of its resources FairShare
 // by the loaded kinds.  (Without parts the shape did not pay: configs[3]'s N = 8 shard
 // and the whole configs[3] unchanged, its N = 4 shard +3 %, profiles/r05_ab/b4_one_wave.txt.)
-static int reset_keys(dm_ctx* c, int b, hipStream_t st);
-
 static bool bin4_prefers_wave(const dm_ctx* c) {
   const std::vector<WorkItem>& items = c->h_bins[4];
   if (items.empty() || c->bin_parts[4] < 2 || (int64_t)c->h_kind.size() != c->R) return false;
@@ -211,43 +209,38 @@ int dm::update_bin4_shape(dm_ctx* c, hipStream_t st) {
   if (wave == c->bin4_wave) return DM_OK;
   c->bin4_wave = wave;
   DM_HIP(c, upload(c->bins[4], c->h_bins[4].data(), c->h_bins[4].size(), st), "plan bins");
-  return reset_keys(c, 4, st);
-}
-
-// Wherever a workgroup bin's items are uploaded, its fixed-point keys start invalid, and
-// no part of it has keys in use (dm_ctx::fix_live).
-static int reset_keys(dm_ctx* c, int b, hipStream_t st) {
-  DBuf<FixKey>& k = c->fix_keys[b - 3];
-  DM_HIP(c, k.ensure(std::max<size_t>(c->h_bins[b].size(), 1)), "fixed-point keys");
-  DM_HIP(c, hipMemsetAsync(k.p, 0, k.n * sizeof(FixKey), st), "fixed-point keys");
-  for (int j = 0; j < dm_ctx::kParts; ++j) c->fix_live[(b - 3) * dm_ctx::kParts + j] = 0;
+  DM_HIP(c, c->reset_keys(4, st), "fixed-point keys");
   return DM_OK;
 }
 
-// The stream parts of the plan and every split slot's state: rest queues, two-slot
-// counters, the epoch checks (a new plan, or parts turned off).
+// One split slot back to its start: the host-mapped words, the back-off, the rest queue
+// sized for the part's items with its count ring, the epoch checks, and the sweep's ring
+// where a tick has allocated it (dm_tick.cpp launch_dense_form).
+int dm::SplitSlot::reset(dm_ctx* c, hipStream_t st) {
+  __atomic_store_n(rec.h + 1, (uint64_t)0, __ATOMIC_RELAXED);
+  __atomic_store_n(guard.h, 0, __ATOMIC_RELAXED);
+  ver_epoch = 0;
+  fix_live = 0;
+  __atomic_store_n(queued.h, 0, __ATOMIC_RELAXED);
+  skip = 0;
+  wait = 64;
+  DM_HIP(c, queue.ensure((size_t)std::max<int64_t>(items(), 1)), "dense split queue");
+  DM_HIP(c, qcnt.ensure(3), "dense split queue");  // two-slot count + the last count told the host
+  DM_HIP(c, hipMemsetAsync(qcnt.p, 0, 3 * sizeof(int32_t), st), "dense split queue");
+  qpar = 0;
+  __atomic_store_n(sweep.h, (uint64_t)0, __ATOMIC_RELAXED);
+  __atomic_store_n(sweep.h + 1, (uint64_t)0, __ATOMIC_RELAXED);
+  if (sw_cnt.p) DM_HIP(c, hipMemsetAsync(sw_cnt.p, 0, 4 * sizeof(int32_t), st), "sweep count");
+  lpar = 0;
+  return DM_OK;
+}
+
+// The stream parts of the plan and every split slot's state (a new plan, or parts turned
+// on or off).
 static int init_split_slots(dm_ctx* c, hipStream_t st) {
   plan_parts(c);
-  for (int i = 0; i < dm_ctx::kSplitSlots; ++i) {
-    __atomic_store_n(c->h_rec.p + 2 * i + 1, (uint64_t)0, __ATOMIC_RELAXED);
-    __atomic_store_n(c->h_guard.p + i, 0, __ATOMIC_RELAXED);
-    c->dq_ver_epoch[i] = 0;
-    c->fix_live[i] = 0;
-    __atomic_store_n(c->h_dq.p + i, 0, __ATOMIC_RELAXED);
-    c->dq_skip[i] = 0;
-    c->dq_wait[i] = 64;
-    const int b = 3 + i / dm_ctx::kParts, j = i % dm_ctx::kParts;
-    const size_t nb = (size_t)std::max<int64_t>(c->part_lo[b][j + 1] - c->part_lo[b][j], 1);
-    DM_HIP(c, c->dq_list[i].ensure(nb), "dense split queue");
-    DM_HIP(c, c->dq_cnt[i].ensure(3), "dense split queue");  // two-slot count + the last count told the host
-    DM_HIP(c, hipMemsetAsync(c->dq_cnt[i].p, 0, 3 * sizeof(int32_t), st), "dense split queue");
-    c->dq_par[i] = 0;
-    // the sweep's count ring, where a tick has allocated it (dm_tick.cpp bin_part)
-    __atomic_store_n(c->h_sw.p + 2 * i, (uint64_t)0, __ATOMIC_RELAXED);
-    __atomic_store_n(c->h_sw.p + 2 * i + 1, (uint64_t)0, __ATOMIC_RELAXED);
-    if (c->sw_cnt[i].p) DM_HIP(c, hipMemsetAsync(c->sw_cnt[i].p, 0, 4 * sizeof(int32_t), st), "sweep count");
-    c->sw_par[i] = 0;
-  }
+  for (SplitSlot& s : c->split)
+    if (int rc = s.reset(c, st)) return rc;
   return DM_OK;
 }
 
@@ -291,6 +284,7 @@ int dm::upload_plan(dm_ctx* c) {
     DM_HIP(c, c->h_rec.alloc(dm_ctx::kSplitSlots * 2, mapped), "dense split check");
     DM_HIP(c, c->h_guard.alloc(dm_ctx::kSplitSlots, mapped), "dense split guard");
     DM_HIP(c, c->h_sw.alloc(dm_ctx::kSplitSlots * 2, mapped), "sweep count");
+    c->bind_split_slots();
   }
   c->rows_changed();  // new work items: no hints
   {
@@ -351,7 +345,7 @@ int dm::upload_plan(dm_ctx* c) {
   DM_HIP(c, c->gcount.ensure(1), "worklist");
   // (last: the allocations above keep their order)
   for (int b = 3; b < 3 + dm_ctx::kSplitBins; ++b)
-    if (int rc = reset_keys(c, b, st)) return rc;
+    DM_HIP(c, c->reset_keys(b, st), "fixed-point keys");
   DM_HIP(c, c->fix_count.ensure(1), "fixed-point keys");
   return DM_OK;
 }

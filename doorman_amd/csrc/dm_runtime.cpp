@@ -340,9 +340,12 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   // the column the last writeback tick wrote: 1 the has column (in place), 0 the alternate
   // column, -1 before any writeback tick
   v[10 + kNumBins] = c->wb_inplace;
-  v[11 + kNumBins] = __builtin_popcount(c->steady_mask);  // bin parts whose last tick ran a steady build
-  v[12 + kNumBins] = __builtin_popcount(c->fixed_mask);   // ... and ran it with the fixed-point keys in use
-  v[13 + kNumBins] = __builtin_popcount(c->sweep_mask);   // ... as the sweep and the row kernel over its worklist
+  v[11 + kNumBins] = v[12 + kNumBins] = v[13 + kNumBins] = 0;
+  for (const SplitSlot& s : c->split) {
+    v[11 + kNumBins] += s.last.steady;    // bin parts whose last tick ran a steady build
+    v[12 + kNumBins] += s.last.use_keys;  // ... and ran it with the fixed-point keys in use
+    v[13 + kNumBins] += s.last.sweep;     // ... as the sweep and the row kernel over its worklist
+  }
   const int n = 14 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
@@ -374,14 +377,12 @@ int dm_store_stats(dm_ctx* c, int64_t* out, int max) {
     }
   }
   v[3] = c->R;
-  // the valid fixed-point keys of the parts whose keys are in use (dm_ctx::fix_live),
+  // the valid fixed-point keys of the parts whose keys are in use (SplitSlot::fix_live),
   // counted here on demand, never by the tick
-  for (int i = 0; i < dm_ctx::kSplitSlots && max > 4; ++i) {
-    const int b = 3 + i / dm_ctx::kParts, j = i % dm_ctx::kParts;
-    const int64_t lo = c->part_lo[b][j], n = c->part_lo[b][j + 1] - lo;
-    if (n <= 0 || c->fix_live[i] != c->row_epoch || !c->fix_keys[b - 3].p) continue;
+  for (const SplitSlot& s : c->split) {
+    if (max <= 4 || s.fix_live != c->row_epoch || s.items() <= 0 || !s.bin_keys->p) continue;
     int32_t cnt = 0;
-    DM_HIP(c, launch_count_keys(c->fix_keys[b - 3].p + lo, (int)n, c->fix_count.p, c->stream), "count keys");
+    DM_HIP(c, launch_count_keys(s.keys(), (int)s.items(), c->fix_count.p, c->stream), "count keys");
     DM_HIP(c, download(&cnt, (const int32_t*)c->fix_count.p, 0, 1, c->stream), "count keys");
     DM_HIP(c, hipStreamSynchronize(c->stream), "count keys");
     v[4] += cnt;

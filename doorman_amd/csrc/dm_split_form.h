@@ -1,0 +1,119 @@
+// dm_split_form.h — which launches one stream part of a workgroup bin (bins 3-6) runs this
+// tick: the one decision behind Tick::bin_part (dm_tick.cpp), from what the host knows of
+// the part (its split slot, dm_ctx.h SplitSlot) and of the tick.  Plain C++17, no HIP: the
+// rules are tested on the CPU (tests/test_split_form.py).
+//
+// The forms, in the order the tests below admit them:
+//   mixed           k_block over every item, hint or not
+//   dense + rest    k_block_dense over the items whose hint is set, k_block_rest over the
+//                   items it queued
+//   dense alone     the rest launch skipped (skip_rest): every item verified dense in this
+//                   row epoch, so nothing can be queued (the guard catches the impossible)
+//   steady          k_block_dense's steady builds, then the rest launch
+//   FIXED           the steady build of a writeback tick in place, rewriting every key ...
+//   FIXED with keys ... or trusting them (use_keys) ...
+//   the sweep       ... as k_fixed_sweep and k_block_dense_list over its worklist
+#pragma once
+#include <algorithm>
+#include <cstdint>
+
+namespace dm {
+
+struct PartForm {
+  bool split = false;      // the split form (else the mixed kernel, and nothing below is set)
+  bool steady = false;     // the steady builds
+  bool skip_rest = false;  // no rest launch: the dense launch carries the guard and the tick's event
+  bool fixed = false;      // the FIXED build
+  bool use_keys = false;   // ... trusting the items' valid keys
+  bool sweep = false;      // ... as the sweep and the row kernel over its worklist
+  int rest_grid = 0;       // k_block_rest's workgroups
+  int list_grid = 0;       // k_block_dense_list's workgroups
+  // The part's fix_live after this tick: the row epoch when the FIXED build is launched,
+  // else 0 (the mixed kernel included).  This one assignment is the key rule: a key is
+  // trusted only while nothing but FIXED launches touched the part in this row epoch.
+  // Fixed points (dm_device.h FixKey, dm_tick_group.hip group_segment FIXED): a part that
+  // runs a steady build on a writeback tick in place runs the FIXED build, which keeps a
+  // key per item and loads no row of an item whose valid key matches its capacity and
+  // kind.  A valid key says that nothing but FIXED builds has touched the item's rows,
+  // running sums or state since it was set; the device cannot know that, so the host
+  // does: fix_live is the row epoch in which the part's last tick launched the FIXED
+  // build (0: it did not).  Keys are in use for a launch only while that is the current
+  // epoch; every other launch of the part (the mixed kernel, a plain or non-skipping
+  // dense build, an alternate-column, non-writeback or recompute tick, DM_STEADY=2) and
+  // every rows_changed() clears it, and the first FIXED launch after that ignores and
+  // rewrites every key.
+  uint64_t fix_live = 0;
+};
+
+// The back-off of the split form.  The 128-thread bins split by the dense hint unless the
+// last split tick the host has heard of queued more than a quarter of the part's items for
+// k_block_rest; then the part runs the mixed kernel and tries again after `wait` ticks (64
+// at first), doubling the wait after every try that still queued too many, up to 4096 (C2's
+// bins, whose resources keep released rows, run 21 % slower split, and a try's k_block_rest
+// strides over thousands of items).  Returns whether to try the split form this tick.
+inline bool try_split(int64_t queued, int n, int& skip, int& wait) {
+  const bool good = 4 * queued <= n;
+  if (good) wait = 64;
+  if (!good && ++skip < wait) return false;
+  if (!good) wait = std::min(2 * wait, 4096);
+  skip = 0;
+  return true;
+}
+
+struct FormInputs {
+  bool hints = false;        // the work items carry dense hints (only a writeback tick sets them)
+  bool dense_split = false;  // the bin's bit of DM_DENSE_SPLIT
+  int steady_ok = 1;         // DM_STEADY (2: the steady ticks' launches with the plain builds)
+  bool fixed_ok = true;      // DM_FIXED
+  bool sweep_ok = true;      // DM_SWEEP
+  int nparts = 1;            // the bin's stream parts
+  uint64_t row_epoch = 0;
+  uint64_t rec_epoch = 0;    // the density record: the epoch of the part's last check ...
+  uint64_t rec_counts = 0;   // ... low half: items not dense; high half: dense items with released rows or arrivals
+  bool recompute = false, writeback = false;
+  bool inplace = false;      // the gets go to the column the has came from
+  uint64_t fix_live = 0;     // the part's, before this tick
+  uint64_t sw_epoch = 0;     // the sweep record: the epoch of the count the device last told ...
+  int64_t sw_told = 0;       // ... and the count
+  int n = 0;                 // the part's items
+  int64_t queued = 0;        // items the last split tick the host has heard of queued
+};
+
+// `tried`: try_split's answer (asked only of a part with hints in a bin that splits).
+inline PartForm choose_form(const FormInputs& in, bool tried) {
+  PartForm f;
+  f.split = in.hints && in.dense_split && tried;
+  if (!f.split) return f;  // the mixed kernel keeps no key
+  const bool verified = in.rec_epoch == in.row_epoch;
+  // The steady builds: every item verified dense and none with released rows or arrivals
+  // (the counts' high half), no recompute.  What the host cannot rule out is a lapse of
+  // the followers (lease lengths change on the device), so the steady kernel queues such
+  // an item and the rest kernel always follows it, with the tick's event; the guard is
+  // for launches that queue nothing.
+  // Not for a bin in stream parts: its ticks are short enough for the rest launch to
+  // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
+  // profiles/steady_ab.md).
+  const bool steady_form = in.steady_ok && in.nparts == 1 && verified && in.rec_counts == 0 && !in.recompute;
+  f.steady = steady_form && in.steady_ok != 2;
+  f.skip_rest = !steady_form && verified && (uint32_t)in.rec_counts == 0;
+  // The FIXED build: a steady build on a writeback tick in place.  It may trust the
+  // items' keys when the part's last tick was one too, in this row epoch; otherwise it
+  // rewrites every key and the next one may.
+  f.fixed = f.steady && in.fixed_ok && in.writeback && in.inplace;
+  f.use_keys = f.fixed && in.fix_live == in.row_epoch;
+  f.fix_live = f.fixed ? in.row_epoch : 0;
+  f.sweep = f.use_keys && in.sweep_ok;
+  // Grids are hints: both kernels stride over their lists, so correctness never depends
+  // on them.  The rest kernel's is sized from the last split tick's queue (an empty queue
+  // costs 16 workgroups that read one count); the row kernel's from the count the device
+  // last told in this row epoch, plus an eighth and 64 (the part's items until then).
+  f.rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, in.queued));
+  f.list_grid = in.n;
+  if (in.sw_epoch == in.row_epoch) {
+    const int64_t told = in.sw_told;
+    f.list_grid = (int)std::min<int64_t>(in.n, std::max<int64_t>(16, told + told / 8 + (told ? 64 : 0)));
+  }
+  return f;
+}
+
+}  // namespace dm

@@ -1,6 +1,10 @@
 // dm_tick.cpp — dm_apportion: one tick's launches over the plan's work classes and their
 // streams (struct Tick), and what a tick does first: the readiness check, a pipelined
 // leaf's staged templates, the queue calibration's windows.
+// A workgroup bin's stream part (Tick::bin_part) works on its split slot (dm_ctx.h
+// SplitSlot): it reads the slot's host-mapped words, asks dm_split_form.h for the form of
+// this tick's launches (try_split, choose_form: the one place the forms and the key rule
+// are written), and hands the form to launch_dense_form, launch_rest or launch_mixed.
 #include <ctime>
 
 #include "dm_ctx.h"
@@ -196,14 +200,14 @@ static hipError_t calib_step(dm_ctx* c) {
   return calib_apply(c, best);
 }
 
-// Once per row epoch, after a writeback tick of workgroup bin b's part j (split slot
-// i): count its items left without a dense hint (k_count_undense -> h_rec).  A count
-// of 0 lets the following ticks of the epoch skip the part's k_block_rest.
-static hipError_t check_dense(dm_ctx* c, int i, int b, int j, hipStream_t s) {
-  const int64_t lo = c->part_lo[b][j], n = c->part_lo[b][j + 1] - lo;
-  if (c->dq_ver_epoch[i] == c->row_epoch || n <= 0) return hipSuccess;
-  c->dq_ver_epoch[i] = c->row_epoch;
-  return launch_count_undense(c->bins[b].p + lo, (int)n, (unsigned long long*)(c->h_rec.d + 2 * i),
+// Once per row epoch, after a writeback tick of a workgroup bin's stream part (its split
+// slot sl): count its items left without a dense hint (k_count_undense -> sl.rec).  A
+// count of 0 lets the following ticks of the epoch skip the part's k_block_rest.
+static hipError_t check_dense(dm_ctx* c, SplitSlot& sl, hipStream_t s) {
+  const int64_t n = sl.items();
+  if (sl.ver_epoch == c->row_epoch || n <= 0) return hipSuccess;
+  sl.ver_epoch = c->row_epoch;
+  return launch_count_undense(c->bins[sl.b].p + sl.lo[0], (int)n, (unsigned long long*)sl.rec.d,
                               (unsigned long long)c->row_epoch, s);
 }
 
@@ -235,7 +239,19 @@ struct Tick {
   int large_chain();  // the large-resource chain
   int subs();         // the sub-wave launch
   int bins();         // the workgroup bins ...
-  int bin_part(int b, int lb, int nparts, bool split_dense, int j);  // ... and one stream part of one
+  // ... and one stream part of one: what its launches share, the form's choice
+  // (dm_split_form.h), then the form's launches
+  struct Part {
+    SplitSlot& sl;
+    BinItems w;      // its items, in the launchers' shape
+    hipStream_t s;
+    DevParams p;     // the tick's, with the part's own flags word
+    hipEvent_t done;  // the part's tick event, for its last kernel (null: no queue waits for the tick)
+  };
+  int bin_part(int b, int lb, int nparts, int j);
+  int launch_dense_form(Part& pt, const PartForm& f);  // the dense kernel in the form's build, or the sweep
+  int launch_rest(Part& pt, const PartForm& f);        // the rest kernel over what it queued
+  int launch_mixed(Part& pt);                          // the one-kernel form
   int finish();       // the join, the general kernel and the state updates
 };
 
@@ -452,125 +468,103 @@ int Tick::subs() {
   return DM_OK;
 }
 
-int Tick::bin_part(int b, int lb, int nparts, bool split_dense, int j) {
-  const int64_t lo = c->part_lo[b][j];
-  const int n = (int)(c->part_lo[b][j + 1] - lo);
+int Tick::bin_part(int b, int lb, int nparts, int j) {
+  SplitSlot& sl = c->slot(b, j);
+  const int n = (int)sl.items();
   if (n == 0) return DM_OK;
-  WorkItem* items = c->bins[b].p + lo;
-  hipStream_t s = j == 0 ? cls_stream(b) : c->aux[c->part_stream(b, j)];
-  DevParams pj = p;
+  Part pt{sl, BinItems{lb, c->bins[b].p + sl.lo[0], n}, j == 0 ? cls_stream(b) : c->aux[c->part_stream(b, j)], p,
+          nullptr};
   if (nparts > 1 && p.pub) {  // the part's own flags word (DevParams::pub_word)
-    pj.pub_word = j;
-    pj.pub_first = c->h_bins[b][(size_t)lo].seg;
+    pt.p.pub_word = j;
+    pt.p.pub_first = c->h_bins[b][(size_t)sl.lo[0]].seg;
   }
   // the tick's last kernel of this part (the dense kernel, or the rest kernel after
   // it) completes the part's tick event when another queue waits for the tick
-  hipEvent_t done = nullptr;
   if (one_class && c->tick_signal_wanted) {
-    done = c->tick_ev[j][c->tick_seq % dm_ctx::kTickEv];
+    pt.done = c->tick_ev[j][c->tick_seq % dm_ctx::kTickEv];
     c->tick_part_mask |= fork ? 1u << (j == 0 ? c->class_stream[b] : c->part_stream(b, j)) : 0u;
   }
-  const int i = (b - 3) * dm_ctx::kParts + j;  // split slot (bins 3-6)
-  if (b >= 3 && b < 3 + dm_ctx::kSplitBins && ((c->dense_split >> (b - 3)) & 1) && split_dense) {
-    // only a writeback tick sets hints, so the split form follows one
-    const int par = c->dq_par[i];
-    const int64_t queued = __atomic_load_n(c->h_dq.p + i, __ATOMIC_RELAXED);
-    const bool good = 4 * queued <= n;
-    if (good) c->dq_wait[i] = 64;
-    if (good || ++c->dq_skip[i] >= c->dq_wait[i]) {
-      if (!good) c->dq_wait[i] = std::min(2 * c->dq_wait[i], 4096);
-      c->dq_skip[i] = 0;
-      // Every item verified dense in this row epoch: nothing can be queued, so the
-      // dense kernel is the part's only launch (the guard catches the impossible).
-      const uint64_t* rec = c->h_rec.p + 2 * i;
-      const bool verified = __atomic_load_n(rec + 1, __ATOMIC_ACQUIRE) == c->row_epoch;
-      const uint64_t counts = __atomic_load_n(rec, __ATOMIC_RELAXED);  // low half: items not dense
-      // The steady builds: every item verified dense and none with released rows or
-      // arrivals (the counts' high half), no recompute.  What the host cannot rule out
-      // is a lapse of the followers (lease lengths change on the device), so the steady
-      // kernel queues such an item and the rest kernel always follows it, with the
-      // tick's event; the guard is for launches that queue nothing.
-      // Not for a bin in stream parts: its ticks are short enough for the rest launch to
-      // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
-      // profiles/steady_ab.md).
-      const bool steady_form = c->steady_ok && nparts == 1 && verified && counts == 0 && !p.recompute;
-      const bool steady = steady_form && c->steady_ok != 2;
-      const bool skip = !steady_form && verified && (uint32_t)counts == 0;
-      if (steady) c->steady_mask |= 1u << i;
-      // The FIXED build: a steady build on a writeback tick in place.  It may trust the
-      // items' keys when the part's last tick was one too, in this row epoch (fix_live,
-      // dm_ctx.h); otherwise it rewrites every key and the next one may.
-      const bool fixed = steady && c->fixed_ok && wb && pj.out_gets == pj.has;
-      const bool use_keys = fixed && c->fix_live[i] == c->row_epoch;
-      c->fix_live[i] = fixed ? c->row_epoch : 0;
-      if (use_keys) c->fixed_mask |= 1u << i;
-      FixKey* keys = fixed ? c->fix_keys[b - 3].p + lo : nullptr;
-      // The sweep: with keys in use, one lane per item finishes the items whose key holds
-      // and lists the others, and the FIXED build runs over the list (k_fixed_sweep).  Its
-      // grid is sized from the count the device last told in this row epoch, with a
-      // margin (a hint: the kernel strides over the list); the part's items until then.
-      const bool sweep = use_keys && c->sweep_ok;
-      int list_grid = n;
-      if (sweep) {
-        c->sweep_mask |= 1u << i;
-        DM_HIP(c, c->sw_list[i].ensure((size_t)n), "sweep list");
-        if (!c->sw_cnt[i].p) {
-          DM_HIP(c, c->sw_cnt[i].ensure(4), "sweep count");  // two-slot count + the last {count, epoch} told the host
-          DM_HIP(c, hipMemsetAsync(c->sw_cnt[i].p, 0, 4 * sizeof(int32_t), s), "sweep count");
-          c->sw_par[i] = 0;
-        }
-        const uint64_t* sw = c->h_sw.p + 2 * i;
-        if (__atomic_load_n(sw + 1, __ATOMIC_ACQUIRE) == c->row_epoch) {
-          const int64_t told = (int64_t)__atomic_load_n(sw, __ATOMIC_RELAXED);
-          list_grid = (int)std::min<int64_t>(n, std::max<int64_t>(16, told + told / 8 + (told ? 64 : 0)));
-        }
-      }
-      DM_HIP(c, timed(KC_DENSE3 + (b - 3), s, [&] {
-               if (sweep)
-                 return launch_bin_sweep(lb, pj, items, n, keys, c->sw_list[i].p, c->sw_cnt[i].p, c->sw_par[i],
-                                         (unsigned long long*)(c->h_sw.d + 2 * i), (unsigned long long)c->row_epoch,
-                                         list_grid, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc, s);
-               return launch_bin_dense(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, gl, gc,
-                                       skip ? c->h_guard.d + i : nullptr, skip ? done : nullptr, steady, keys,
-                                       use_keys, s);
-             }),
-             "group kernel (dense split)");
-      if (sweep) c->sw_par[i] ^= 1;
-      if (!skip) {
-        // the rest kernel strides over whatever the dense kernel queues; its grid is
-        // only sized from the last split tick's queue (a hint: correctness never
-        // depends on it): an empty queue costs 16 workgroups that read one count
-        const int rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, queued));
-        DM_HIP(c, timed(KC_REST3 + (b - 3), s, [&] {
-                 return launch_bin_rest(lb, pj, items, n, c->dq_list[i].p, c->dq_cnt[i].p, par, c->h_dq.d + i,
-                                        rest_grid, gl, gc, done, s);
-               }),
-               "group kernel (dense split)");
-        c->dq_par[i] ^= 1;
-      }
-      if (wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
-      return DM_OK;
+  // what the host knows of the part and of the tick -> the form of the part's launches
+  FormInputs in;
+  in.hints = c->hints_set;  // only a writeback tick sets hints, so the split form follows one
+  in.dense_split = (c->dense_split >> (b - 3)) & 1;
+  in.steady_ok = c->steady_ok;
+  in.fixed_ok = c->fixed_ok;
+  in.sweep_ok = c->sweep_ok;
+  in.nparts = nparts;
+  in.row_epoch = c->row_epoch;
+  in.recompute = p.recompute;
+  in.writeback = wb;
+  in.inplace = pt.p.out_gets == pt.p.has;
+  in.fix_live = sl.fix_live;
+  in.n = n;
+  const bool may_split = in.hints && in.dense_split;
+  if (may_split) in.queued = sl.read_queued();
+  const bool tried = may_split && try_split(in.queued, n, sl.skip, sl.wait);
+  if (tried) sl.read_records(in);
+  const PartForm f = sl.last = choose_form(in, tried);
+  sl.fix_live = f.fix_live;  // the key rule (SplitSlot::fix_live): every launch of the part passes here
+  int rc = DM_OK;
+  if (!f.split)
+    rc = launch_mixed(pt);
+  else if (!(rc = launch_dense_form(pt, f)) && !f.skip_rest)
+    rc = launch_rest(pt, f);
+  if (rc) return rc;
+  if (wb) DM_HIP(c, check_dense(c, sl, pt.s), "dense split check");
+  return DM_OK;
+}
+
+int Tick::launch_dense_form(Part& pt, const PartForm& f) {
+  SplitSlot& sl = pt.sl;
+  // the guard and the tick's event go to a dense launch that no rest launch follows
+  const SplitArgs a{sl.queue.p, sl.qcnt.p, sl.qpar, gl, gc, f.skip_rest ? sl.guard.d : nullptr};
+  FixKey* keys = f.fixed ? sl.keys() : nullptr;
+  if (f.sweep) {
+    DM_HIP(c, sl.sw_list.ensure((size_t)pt.w.n), "sweep list");
+    if (!sl.sw_cnt.p) {
+      DM_HIP(c, sl.sw_cnt.ensure(4), "sweep count");  // two-slot count + the last {count, epoch} told the host
+      DM_HIP(c, hipMemsetAsync(sl.sw_cnt.p, 0, 4 * sizeof(int32_t), pt.s), "sweep count");
+      sl.lpar = 0;
     }
   }
-  if (b >= 3 && b < 3 + dm_ctx::kSplitBins) c->fix_live[i] = 0;  // the mixed kernel keeps no key
-  if (done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
+  DM_HIP(c, timed(KC_DENSE3 + (sl.b - 3), pt.s, [&] {
+           if (f.sweep)
+             return launch_bin_sweep(pt.w, pt.p, a,
+                                     SweepArgs{keys, sl.sw_list.p, sl.sw_cnt.p, sl.lpar,
+                                               (unsigned long long*)sl.sweep.d, (unsigned long long)c->row_epoch,
+                                               f.list_grid},
+                                     pt.s);
+           return launch_bin_dense(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, f.steady, keys, f.use_keys, pt.s);
+         }),
+         "group kernel (dense split)");
+  if (f.sweep) sl.lpar ^= 1;
+  return DM_OK;
+}
+
+int Tick::launch_rest(Part& pt, const PartForm& f) {
+  SplitSlot& sl = pt.sl;
+  const SplitArgs a{sl.queue.p, sl.qcnt.p, sl.qpar, gl, gc, nullptr};
+  DM_HIP(c, timed(KC_REST3 + (sl.b - 3), pt.s,
+                  [&] { return launch_bin_rest(pt.w, pt.p, a, sl.queued.d, f.rest_grid, pt.done, pt.s); }),
+         "group kernel (dense split)");
+  sl.qpar ^= 1;
+  return DM_OK;
+}
+
+int Tick::launch_mixed(Part& pt) {
+  if (pt.done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
     c->tick_flagged = false;
     c->tick_part_mask = 0;
   }
-  DM_HIP(c, timed(KC_BIN0 + b, s, [&] { return launch_bin(lb, pj, items, n, gl, gc, s); }), "group kernel");
-  if (b >= 3 && b < 3 + dm_ctx::kSplitBins && wb) DM_HIP(c, check_dense(c, i, b, j, s), "dense split check");
+  DM_HIP(c, timed(KC_BIN0 + pt.sl.b, pt.s, [&] { return launch_bin(pt.w, pt.p, gl, gc, pt.s); }), "group kernel");
   return DM_OK;
 }
 
 int Tick::bins() {
-  // the workgroup bins split by the dense hint after a writeback tick (hints set)
-  const bool split_dense = c->hints_set;
-  c->steady_mask = 0;
-  c->fixed_mask = 0;
-  c->sweep_mask = 0;
+  for (SplitSlot& s : c->split) s.last = PartForm{};  // (dm_plan_info: the forms of this tick's launches)
   for (int b = kNumBins - 1; b >= 0; --b) {
     if (c->h_bins[b].empty()) continue;
-    if (b == 7 || b == 8 || b <= 2) continue;  // k_subs
+    if (!dm_ctx::is_split_bin(b)) continue;  // the sub-wave bins: k_subs
     const int lb = (b == 6 && c->bin6_wide)   ? kBin6Wide
                    : (b == 4 && c->bin4_wave) ? kBin4Wave
                                               : b;  // the launchers' bin (shape)
@@ -581,7 +575,7 @@ int Tick::bins() {
       c->tick_part_mask = 0;
     }
     for (int j = 0; j < nparts; ++j)
-      if (int rc = bin_part(b, lb, nparts, split_dense, j)) return rc;
+      if (int rc = bin_part(b, lb, nparts, j)) return rc;
   }
   return DM_OK;
 }

@@ -74,6 +74,29 @@ __device__ __forceinline__ void put_key(FixKey* key, const FixKey& fk, int use_k
   if (!use_keys || nk.cbits != fk.cbits || nk.kind != fk.kind || nk.valid != fk.valid) *key = nk;
 }
 
+// What group_segment<.., FIXED> and the sweep's lanes (k_fixed_sweep) do with an item whose
+// key holds: the record as the full path would write it (follow_exp moves, the exchange's
+// block is published, the state byte stays), the sums it read and a delta of +0.0.
+// (The two tests before it -- the steady `rest` test and the key against the record -- stay
+// written out in both places: as functions they change the kernels' code, the compiler
+// ordering the tests' terms differently behind a call.  k_fixed_sweep's copy must stay
+// equal to group_segment's.)
+__device__ __forceinline__ void write_fixed(const DevParams& p, int seg, const Res& rs, int hint) {
+  write_resource(p, seg, rs, Clean{rs.agg_count, rs.agg_has, rs.agg_wants}, 0.0, hint);
+}
+// One thread hands item qidx to the rest queue: its key cleared first (KEY), at most one
+// entry per item and tick (a guarded tick's count may grow past qcap), and the guard set
+// where the launch has one.  (The count's slot is qcnt + par, added here and not by the
+// caller: ahead of the key's store the addition moves k_block_dense_fixed's code.)
+template <bool KEY>
+__device__ __forceinline__ void hand_off(FixKey* key, const FixKey& fk, int use_keys, int32_t* queue, int32_t* qcnt,
+                                         int par, int32_t qidx, int qcap, int32_t* guard) {
+  if constexpr (KEY) put_key(key, fk, use_keys, false, 0.0, 0);  // before the hand-off
+  const int q = atomicAdd(qcnt + par, 1);
+  if (q < qcap) queue[q] = qidx;
+  if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // LIST: the caller is a loop over items (k_block_dense_list).  Behind an earlier item's
 // stores the compiler loads the record with vector loads, a register per dword and lane
 // through every pass (128 x 8: 88 VGPRs against 65); the record is moved back to SGPRs.
@@ -174,12 +197,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
     const bool stale = dense_subclients(rs) != hint;
     const bool rest = STEADY ? stale || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute : stale || arr_lapse;
     if (rest) {  // stale hint: k_block_rest reads the column
-      if (t == 0) {
-        if constexpr (FIXED) put_key(key, fk, use_keys, false, 0.0, 0);  // before the hand-off
-        const int q = atomicAdd(qcount, 1);
-        if (q < qcap) queue[q] = qidx;  // at most one entry per item and tick (a guarded tick's count may grow)
-        if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      if (t == 0) hand_off<FIXED>(key, fk, use_keys, queue, qcount, 0, qidx, qcap, guard);
       return;
     }
     if constexpr (FIXED) {
@@ -187,10 +205,9 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
         // The key's tick computed with this capacity and kind, outside learning mode, from
         // the rows, running sums and state that are still there (FixKey): this tick would
         // store no gets, reduce a delta of +0.0 and write the sums it read.  It writes the
-        // record as the full path would (follow_exp moves, the exchange's block is
-        // published, the state byte stays) and is done.
+        // record as the full path would and is done.
         if (fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
-          if (t == 0) write_resource(p, seg, rs, Clean{rs.agg_count, rs.agg_has, rs.agg_wants}, 0.0, hint);
+          if (t == 0) write_fixed(p, seg, rs, hint);
           return;
         }
 #pragma unroll
@@ -557,11 +574,8 @@ __global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __rest
   if ((int)blockIdx.x < nitems) {
     const WorkItem wi = items[blockIdx.x];
     if ((wi.n >> 16) == 0) {
-      if (threadIdx.x == 0) {
-        const int q = atomicAdd(qcnt + par, 1);
-        if (q < nitems) queue[q] = (int32_t)blockIdx.x;
-        if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      if (threadIdx.x == 0)
+        hand_off<false>(nullptr, FixKey{0, 0, 0}, 0, queue, qcnt, par, (int32_t)blockIdx.x, nitems, guard);
     } else {
       group_segment<G, R, kDenseOnly, SKIP, STEADY>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
                                                     general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
@@ -587,12 +601,8 @@ __global__ __launch_bounds__(G) void k_block_dense_fixed(DevParams p, WorkItem* 
     const WorkItem wi = items[blockIdx.x];
     const FixKey fk = keys[blockIdx.x];
     if ((wi.n >> 16) == 0) {
-      if (threadIdx.x == 0) {
-        put_key(keys + blockIdx.x, fk, use_keys, false, 0.0, 0);  // before the hand-off
-        const int q = atomicAdd(qcnt + par, 1);
-        if (q < nitems) queue[q] = (int32_t)blockIdx.x;
-        if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      if (threadIdx.x == 0)
+        hand_off<true>(keys + blockIdx.x, fk, use_keys, queue, qcnt, par, (int32_t)blockIdx.x, nitems, guard);
     } else {
       group_segment<G, R, kDenseOnly, true, true, true>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
                                                         general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
@@ -607,7 +617,7 @@ __global__ __launch_bounds__(G) void k_block_dense_fixed(DevParams p, WorkItem* 
 // profiles/sweep_share.md).  That test is a lane's work.  k_fixed_sweep takes one lane per
 // item of the part: the item, its key and its record, exactly the tests of
 // group_segment<.., FIXED> before its rows (the steady `rest` test, a zero hint word, the
-// key against the record); an item that passes them all gets the same write_resource call
+// key against the record); an item that passes them all gets the same write_fixed call
 // and is done, any other is appended to the part's worklist with its key in memory cleared.
 // k_block_dense_list then runs the FIXED build over the worklist alone: every item it sees
 // has an invalid key in memory, so it loads none (FixKey{0, 0, 0}), loads its rows at once
@@ -639,7 +649,7 @@ __global__ __launch_bounds__(1024) void k_fixed_sweep(DevParams p, const WorkIte
       const int hint = hw & 0xFF;
       const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
       if (!rest && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
-        write_resource(p, wi.seg, rs, Clean{rs.agg_count, rs.agg_has, rs.agg_wants}, 0.0, hint);
+        write_fixed(p, wi.seg, rs, hint);
         done = true;
       }
     }
@@ -691,10 +701,7 @@ __global__ __launch_bounds__(G) void k_block_dense_list(DevParams p, WorkItem* _
     int t = (int)threadIdx.x;
     asm volatile("" : "+v"(t));
     if ((wi.n >> 16) == 0) {  // (its key is invalid in memory: the sweep saw to it)
-      if (threadIdx.x == 0) {
-        const int qi = atomicAdd(qcnt + par, 1);
-        if (qi < nitems) queue[qi] = e.idx;
-      }
+      if (threadIdx.x == 0) hand_off<false>(nullptr, FixKey{0, 0, 0}, 0, queue, qcnt, par, e.idx, nitems, nullptr);
     } else {
       group_segment<G, R, kDenseOnly, true, true, true, true>(p, wi, items + e.idx, t, lds, general_list,
                                                               general_count, queue, qcnt + par, e.idx, nullptr, nitems,
@@ -1063,12 +1070,11 @@ void with_bool(bool b, F&& f) {
 }
 
 // the workgroup bins (3-6) in their one-kernel form; the sub-wave bins run in k_subs
-hipError_t launch_bin(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* glist, int32_t* gcount,
-                      hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+hipError_t launch_bin(const BinItems& w, const DevParams& p, int32_t* glist, int32_t* gcount, hipStream_t st) {
+  if (w.n <= 0) return hipSuccess;
+  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    k_block<G, R><<<n, G, 0, st>>>(p, segs, n, glist, gcount);
+    k_block<G, R><<<w.n, G, 0, st>>>(p, w.items, w.n, glist, gcount);
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
 }
@@ -1090,25 +1096,25 @@ hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, in
 // known for (group_segment STEADY); the caller launches the rest kernel after them.
 // keys (optional; only with steady, on a writeback tick in place): the FIXED build, over the
 // keys of these items; use_keys: valid keys may be trusted (else every key is rewritten).
-hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                            int32_t* glist, int32_t* gcount, int32_t* guard, hipEvent_t done, bool steady,
+hipError_t launch_bin_dense(const BinItems& w, const DevParams& p, const SplitArgs& a, hipEvent_t done, bool steady,
                             FixKey* keys, bool use_keys, hipStream_t st) {
+  const int n = w.n;
   if (n <= 0) return hipSuccess;
   const dim3 grid((unsigned)n);
   // in place (the gets go to the column the has came from): the build that skips unchanged runs
   const bool skip = p.writeback && p.out_gets == p.has;
   if (keys && !(skip && steady)) return hipErrorInvalidValue;
-  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     if (keys) {
-      hipExtLaunchKernelGGL((k_block_dense_fixed<G, R>), grid, dim3(G), 0, st, nullptr, done, 0, p, segs, n, queue, qcnt,
-                            par, glist, gcount, guard, keys, use_keys ? 1 : 0);
+      hipExtLaunchKernelGGL((k_block_dense_fixed<G, R>), grid, dim3(G), 0, st, nullptr, done, 0, p, w.items, n, a.queue,
+                            a.qcnt, a.par, a.glist, a.gcount, a.guard, keys, use_keys ? 1 : 0);
       return;
     }
     with_bool(skip, [&](auto sk) {
       with_bool(steady, [&](auto sd) {
         hipExtLaunchKernelGGL((k_block_dense<G, R, decltype(sk)::value, decltype(sd)::value>), grid, dim3(G), 0, st,
-                              nullptr, done, 0, p, segs, n, queue, qcnt, par, glist, gcount, guard);
+                              nullptr, done, 0, p, w.items, n, a.queue, a.qcnt, a.par, a.glist, a.gcount, a.guard);
       });
     });
   });
@@ -1117,19 +1123,18 @@ hipError_t launch_bin_dense(int bin, const DevParams& p, WorkItem* segs, int n, 
 
 // A FIXED launch with keys in use, as the sweep and the row kernel over its worklist
 // (k_fixed_sweep): the rest launch follows as after launch_bin_dense's steady builds.
-// list_grid: the row kernel's workgroups, a hint (it strides over the list).
-hipError_t launch_bin_sweep(int bin, const DevParams& p, WorkItem* segs, int n, FixKey* keys, SweepEntry* list,
-                            int32_t* lcnt, int lpar, unsigned long long* host_count, unsigned long long epoch,
-                            int list_grid, int32_t* queue, int32_t* qcnt, int par, int32_t* glist, int32_t* gcount,
+hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
                             hipStream_t st) {
+  const int n = w.n;
   if (n <= 0) return hipSuccess;
-  if (!(p.writeback && p.out_gets == p.has) || !keys) return hipErrorInvalidValue;
-  const dim3 lg((unsigned)std::max(1, std::min(n, list_grid)));
-  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+  if (!(p.writeback && p.out_gets == p.has) || !sw.keys) return hipErrorInvalidValue;
+  const dim3 lg((unsigned)std::max(1, std::min(n, sw.list_grid)));
+  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    k_fixed_sweep<<<dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, st>>>(p, segs, n, keys, list, lcnt, lpar);
-    k_block_dense_list<G, R><<<lg, dim3(G), 0, st>>>(p, segs, n, list, lcnt, lpar, host_count, epoch, queue, qcnt, par,
-                                                     glist, gcount, keys);
+    k_fixed_sweep<<<dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, st>>>(p, w.items, n, sw.keys, sw.list, sw.lcnt,
+                                                                              sw.lpar);
+    k_block_dense_list<G, R><<<lg, dim3(G), 0, st>>>(p, w.items, n, sw.list, sw.lcnt, sw.lpar, sw.host_count, sw.epoch,
+                                                     a.queue, a.qcnt, a.par, a.glist, a.gcount, sw.keys);
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
 }
@@ -1159,15 +1164,14 @@ hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long
   return hipGetLastError();
 }
 
-hipError_t launch_bin_rest(int bin, const DevParams& p, WorkItem* segs, int n, int32_t* queue, int32_t* qcnt, int par,
-                           int32_t* host_count, int rest_grid, int32_t* glist, int32_t* gcount, hipEvent_t done,
-                           hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  const dim3 rg((unsigned)std::max(1, std::min(n, rest_grid)));
-  const bool known = with_bin_shape(bin, [&](auto g, auto r) {
+hipError_t launch_bin_rest(const BinItems& w, const DevParams& p, const SplitArgs& a, int32_t* host_count,
+                           int rest_grid, hipEvent_t done, hipStream_t st) {
+  if (w.n <= 0) return hipSuccess;
+  const dim3 rg((unsigned)std::max(1, std::min(w.n, rest_grid)));
+  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    hipExtLaunchKernelGGL((k_block_rest<G, R>), rg, dim3(G), 0, st, nullptr, done, 0, p, segs, queue, qcnt, par,
-                          host_count, glist, gcount);
+    hipExtLaunchKernelGGL((k_block_rest<G, R>), rg, dim3(G), 0, st, nullptr, done, 0, p, w.items, a.queue, a.qcnt, a.par,
+                          host_count, a.glist, a.gcount);
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
 }
