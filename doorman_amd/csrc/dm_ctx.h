@@ -1,7 +1,9 @@
 // dm_ctx.h — what the host units of the runtime share: the context (one per GPU: the
 // device-resident columnar lease store, its dispatch plan, streams and policy state), the
-// types that own its device memory, pinned host memory and events, the entry macros of
-// the C-ABI calls, and the functions that cross a unit boundary.  The only definition of
+// types that own its device memory, pinned host memory and events, the four owners of its
+// cross-stream order (StreamOrder, TickDone, TemplatePipe, QueueCalibration: they carry out
+// what dm_tick_order.h decides), the entry macros of the C-ABI calls, and the functions
+// that cross a unit boundary.  The only definition of
 // dm_ctx; the units around it are dm_runtime.cpp (context life, streams, profiling),
 // dm_plan.cpp, dm_tick.cpp, dm_decide.cpp, dm_store.cpp, dm_store_update.cpp and
 // dm_hier_host.cpp.  See DESIGN.md §3-§5.
@@ -23,6 +25,7 @@
 #include "dm_device.h"
 #include "dm_launch.h"
 #include "dm_split_form.h"
+#include "dm_tick_order.h"
 
 struct dm_ctx;
 
@@ -230,41 +233,24 @@ struct SplitSlot {
 };
 static_assert(!std::is_copy_constructible<SplitSlot>::value, "a split slot owns its queues");
 
-}  // namespace dm
+// The four owners of a context's cross-stream state.  dm_tick_order.h decides which stream
+// waits for which (plain C++, tested on the CPU); these hold the HIP handles and carry the
+// decision out, and the host units ask, then do.
 
-using namespace dm;
+constexpr int kStreamParts = 2;  // dm_ctx::kParts: the stream parts a tick's events are kept for
 
-struct dm_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  // auxiliary streams: independent size bins of one tick run concurrently
-  static constexpr int kAux = 4;
-  // auxiliary stream of each work class: bins 0..kNumBins-1, small tiles, large chain
-  // (round 4 moved every bin to each other stream in A/Bs: this split won every one)
-  // (round 5, with the small tiles: bin 3 on stream 3 112.8-117.3 us, on stream 1
-  // 112.8-114.2, bin 6 on stream 3 127-129, against 111.0-112.4 us; profiles/r05_c2_classes.md)
-  static constexpr int kClassStream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};  // C2: 200 -> 189 us (small class alone)
-  // this store's assignment (plan_streams): kClassStream, except that on a store that
-  // leaves some auxiliary stream without work, classes that would share a stream move
-  // onto the idle ones (a shard of a Zipf population holds only some classes)
-  int class_stream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};
-  int64_t h_shape_lo[kSubShapes] = {}, h_shape_n[kSubShapes] = {};  // sub-wave shapes' items within their bins
-  hipStream_t aux[kAux] = {};
-  bool aux_own_queue = false;  // each auxiliary stream has a hardware queue of its own (CU mask)
-  uint64_t aux_seq = 0;        // the stream set's creation order in the process (take_aux)
-  hipStream_t cpy = nullptr;  // store-update column copies (overlap a running tick)
-  Event ev_stage[2];  // staged update copies -> per-chunk validation
-  // Cross-stream order between the context's streams (fork / join of a tick's work
-  // classes, the pipelined hierarchy's template slots, dm_stream_wait): an event
-  // recorded on the producing stream and waited on by the consuming one.  An event wait
-  // idles the consuming queue ~12-20 us on the box (tools/xs_probe.py); stream-memory
-  // tokens (hipStreamWriteValue64 / WaitValue64, which this ROCm runs as blit kernels
-  // of 3-5 us each plus a dispatch gap) measured no cheaper per step (round 4: 75.0 vs
-  // 72.2 us per N = 8 shard step) and were retired in round 5, as was the tick-done
-  // word (the tick's last kernels' stop events replaced it: tick_ev below).  A wait on
-  // a token signalled on the waiting stream itself is skipped (stream order).
-  static constexpr int kTplSlots = 4;  // staged templates: in use + pending (lag 2) + the one being written
+// The context stream, the auxiliary streams (independent size bins of one tick run
+// concurrently on them) and the order between them.
+// Cross-stream order between the context's streams (fork / join of a tick's work
+// classes, the pipelined hierarchy's template slots, dm_stream_wait): an event
+// recorded on the producing stream and waited on by the consuming one.  An event wait
+// idles the consuming queue ~12-20 us on the box (tools/xs_probe.py); stream-memory
+// tokens (hipStreamWriteValue64 / WaitValue64, which this ROCm runs as blit kernels
+// of 3-5 us each plus a dispatch gap) measured no cheaper per step (round 4: 75.0 vs
+// 72.2 us per N = 8 shard step) and were retired in round 5, as was the tick-done
+// word (the tick's last kernels' stop events replaced it: TickDone below).  A wait on
+// a token signalled on the waiting stream itself is skipped (stream order).
+struct StreamOrder {
   enum : int {
     XS_FORK = 0,
     XS_JOIN0 = 1,                       // + aux stream
@@ -280,11 +266,11 @@ struct dm_ctx {
     hipStream_t s = nullptr;  // the stream it was signalled on
     bool rec = false;         // recorded (else the wait records on s first: lazy signal)
   };
-  // A pipelined leaf's staged templates from another stream: the host waits for the
-  // exchange that made them and the leaf's stream gets no barrier (a queue waiting on
-  // another queue here costs ~12-16 us even when the signal is long set -- the step of
-  // an N = 8 shard idled that long every tick, tools/step_trace.py); the host stays at
-  // most ~one step ahead, the device never waits.
+  const hipStream_t* main = nullptr;  // the context stream (dm_ctx::stream, which dm_set_stream changes)
+  TickSignal* sig = nullptr;          // the context's (TickDone): which auxiliary streams hold unjoined work
+  hipStream_t aux[kAux] = {};
+  bool aux_own_queue = false;  // each auxiliary stream has a hardware queue of its own (CU mask)
+  uint64_t aux_seq = 0;        // the stream set's creation order in the process (take_aux)
   Event xs_ev[XS_N];
   hipError_t xs_signal(int w, hipStream_t s, XsTok* tok) {
     tok->w = w;
@@ -311,6 +297,141 @@ struct dm_ctx {
     hipError_t e = xs_signal(w, from, &t);
     return e == hipSuccess ? xs_wait(t, to) : e;
   }
+  // A forked tick's work classes run on the auxiliary streams.  Normally they are
+  // joined back into the context stream at the end of the tick; with DM_DEFER_JOIN
+  // the join waits for the next library call that needs it (each cross-queue hop
+  // costs ~20 us on the GPU, so back-to-back ticks keep every class streaming).
+  // aux_pending: class work not yet joined into the context stream.
+  // main_dirty: the context stream holds work the auxiliary streams have not
+  // waited for (the next fork must record an event).
+  bool aux_pending = false, main_dirty = true;
+  hipError_t join() {
+    if (!aux_pending) return hipSuccess;
+    aux_pending = false;
+    sig->unjoined = 0;
+    for (int i = 0; i < kAux; ++i) {
+      hipError_t e = xs_order(XS_JOIN0 + i, aux[i], *main);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  void main_has_work() { main_dirty = true; }
+  bool needs_fork() const { return main_dirty; }
+  // Before a forked tick's launches: the class streams wait for what the context stream
+  // holds (when it holds any), and `used`, the streams with work this tick, count as
+  // unjoined.  After them, forked(): there is class work to join.  Two moments, as they
+  // always were: a tick whose launch fails in between leaves no join pending.
+  hipError_t fork(unsigned used) {
+    if (needs_fork()) {
+      XsTok fk;
+      hipError_t e = xs_signal(XS_FORK, *main, &fk);
+      for (int i = 0; i < kAux && e == hipSuccess; ++i) e = xs_wait(fk, aux[i]);
+      if (e != hipSuccess) return e;
+      main_dirty = false;
+    }
+    sig->unjoined |= used;
+    return hipSuccess;
+  }
+  void forked() { aux_pending = true; }
+};
+
+// The tick-done signal (dm_tick_order.h TickSignal) and the events it counts: one per tick
+// and stream part, in a ring; a tick's last kernels complete them.
+struct TickDone {
+  TickSignal sig;
+  Event ev[kStreamParts][kTickEv];  // per stream part (one part: [0])
+  hipEvent_t event(int part) const { return ev[part][sig.seq % kTickEv]; }  // this tick's, for the part's last kernel
+  // stream s after tick `seq`: its parts' events
+  hipError_t wait(uint64_t seq, hipStream_t s) const {
+    const int k = (int)(seq % kTickEv);
+    for (int j = 0; j < std::max(sig.nev[k], 1); ++j) {
+      hipError_t e = hipStreamWaitEvent(s, ev[j][k], 0);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+};
+
+// A pipelined leaf's templates (dm_hier_pipeline; the host half: dm_tick_order.h
+// TemplateQueue): the staged slots and the tokens that order their writers and readers.
+// Staged templates from another stream: the host waits for the exchange that made them
+// and the leaf's stream gets no barrier (a queue waiting on another queue here costs
+// ~12-16 us even when the signal is long set -- the step of an N = 8 shard idled that long
+// every tick, tools/step_trace.py); the host stays at most ~one step ahead, the device
+// never waits.
+struct TemplatePipe {
+  TemplateQueue q;
+  bool on = false;
+  DBuf<ResCfg> cfg[kTplSlots];
+  DBuf<ResCold> cold[kTplSlots];
+  StreamOrder::XsTok ready[kTplSlots];  // root stream: the slot's templates are written
+  StreamOrder::XsTok free[kTplSlots];   // leaf stream: the ticks that read the slot are done
+  bool free_rec[kTplSlots] = {};        // free holds a signal
+  uint64_t free_seq[kTplSlots] = {};    // a slot is free once this tick's event completed (0: use free)
+  void reset() {  // every slot free, none read
+    q.reset();
+    for (bool& r : free_rec) r = false;
+  }
+  // Stream s has drained and may not outlive the call: the slots' lazy signals on it are
+  // complete, never record on it again.
+  void forget_stream(hipStream_t s) {
+    for (int i = 0; i < kTplSlots; ++i)
+      for (StreamOrder::XsTok* t : {&ready[i], &free[i]})
+        if (!t->rec && t->s == s) t->s = nullptr;
+  }
+};
+
+// The queue calibration's streams and windows (the schedule and the choice:
+// dm_tick_order.h QueueCalib; carried out by calib_step, dm_tick.cpp):
+// aux[i] = phys[perm[i]].
+struct QueueCalibration {
+  QueueCalib cal;
+  int perm[kAux] = {0, 1, 2, 3};
+  hipStream_t phys[kAux] = {};
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;  // each window's start and end on the context stream
+  QueueCalibration() = default;
+  QueueCalibration(const QueueCalibration&) = delete;
+  QueueCalibration& operator=(const QueueCalibration&) = delete;
+  void free() {
+    for (auto& pr : ev) {
+      if (pr.first) (void)hipEventDestroy(pr.first);
+      if (pr.second) (void)hipEventDestroy(pr.second);
+    }
+    ev.clear();
+  }
+};
+
+}  // namespace dm
+
+using namespace dm;
+
+struct dm_ctx {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  static constexpr int kAux = dm::kAux;
+  // Which stream waits for which (the types above): the streams and their fork and join,
+  // the tick-done signal, a pipelined leaf's template slots, the queue calibration.
+  StreamOrder order;
+  TickDone done;
+  TemplatePipe tpl;
+  QueueCalibration qcal;
+  dm_ctx() {
+    order.main = &stream;
+    order.sig = &done.sig;
+  }
+  // auxiliary stream of each work class: bins 0..kNumBins-1, small tiles, large chain
+  // (round 4 moved every bin to each other stream in A/Bs: this split won every one)
+  // (round 5, with the small tiles: bin 3 on stream 3 112.8-117.3 us, on stream 1
+  // 112.8-114.2, bin 6 on stream 3 127-129, against 111.0-112.4 us; profiles/r05_c2_classes.md)
+  static constexpr int kClassStream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};  // C2: 200 -> 189 us (small class alone)
+  // this store's assignment (plan_streams): kClassStream, except that on a store that
+  // leaves some auxiliary stream without work, classes that would share a stream move
+  // onto the idle ones (a shard of a Zipf population holds only some classes)
+  int class_stream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};
+  int64_t h_shape_lo[kSubShapes] = {}, h_shape_n[kSubShapes] = {};  // sub-wave shapes' items within their bins
+  hipStream_t cpy = nullptr;  // store-update column copies (overlap a running tick)
+  Event ev_stage[2];  // staged update copies -> per-chunk validation
   std::string err;
 
   int64_t R = 0, N = 0;
@@ -372,24 +493,6 @@ struct dm_ctx {
   // a new store
   bool hints_set = false;
   int64_t seg_uniform = 0;  // rows per resource when every resource has the same count, else 0
-  // A forked tick's work classes run on the auxiliary streams.  Normally they are
-  // joined back into the context stream at the end of the tick; with DM_DEFER_JOIN
-  // the join waits for the next library call that needs it (each cross-queue hop
-  // costs ~20 us on the GPU, so back-to-back ticks keep every class streaming).
-  // aux_pending: class work not yet joined into the context stream.
-  // main_dirty: the context stream holds work the auxiliary streams have not
-  // waited for (the next fork must record an event).
-  bool aux_pending = false, main_dirty = true;
-  hipError_t join_aux() {
-    if (!aux_pending) return hipSuccess;
-    aux_pending = false;
-    aux_unjoined = 0;
-    for (int i = 0; i < kAux; ++i) {
-      hipError_t e = xs_order(XS_JOIN0 + i, aux[i], stream);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
   // the store-update kernels' view of the dense state (dm_device.h DenseUpd)
   DenseUpd dense_upd() const {
     DenseUpd d{};
@@ -400,30 +503,6 @@ struct dm_ctx {
     d.rmask = rmask.p;
     return d;
   }
-  // Queue calibration (calib_step): which of the four auxiliary streams -- four hardware
-  // queues -- carries which work class moved configs[2]'s tick from 111 to 157 us over
-  // the 24 assignments (profiles/r05_queues.txt), and a queue's place in the process's
-  // creation order, which a host that made streams of its own first shifts, decides
-  // which assignment is best.  So the context times every assignment on its first
-  // forked writeback ticks (windows of kCalibWin ticks, each between joins of every
-  // class stream, HIP events on the context stream), times the best kCalibFinal again
-  // over longer windows, and keeps the fastest: aux[i] = aux_phys[perm[i]].
-  // (the skip: a context's first ticks run slow -- first-touch, and the GPU reaches its
-  // sustained-load operating point only after ~0.1-0.3 s of back-to-back work,
-  // profiles/r06_c4_variants.md -- which biases the candidates timed first; round 2
-  // therefore also interleaves its candidates, kCalibRep2 short windows each, and sums
-  // them, so that a drift of the clocks falls on every candidate alike)
-  static constexpr int kCalibSkip = 1024, kCalibWin = 6, kCalibFinal = 3, kCalibWin2 = 4, kCalibRep2 = 4;
-  int calib = 0;  // 0 pending, 1 round 1, 2 round 2, 3 waiting for the events, 4 done / off
-  int calib_skip = 0, calib_k = 0, calib_t = 0, calib_round = 0;
-  int perm[kAux] = {0, 1, 2, 3};
-  hipStream_t aux_phys[kAux] = {};
-  std::vector<std::array<int, kAux>> calib_cand;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> calib_ev;
-  std::vector<int> calib_of_ev;  // candidate timed by each window
-  std::vector<float> calib_ms;
-  bool calib_log = false;
-  int64_t calib_best = -1;  // the chosen permutation (perm[0] + 4 perm[1] + 16 perm[2] + 64 perm[3])
   // plan
   std::vector<Tile> h_tiles;  // small resources (n <= kSmallMax) in tiles (k_tile_small)
   std::vector<TileEntry> h_tile_list;  // the list tiles' resources
@@ -458,7 +537,7 @@ struct dm_ctx {
   // leases: 57.3 -> 48.8 us per tick, tools/shard_split.py; the whole configs[3], 100M
   // leases: 430 -> 425 us, not worth its cross-queue waits in the exchange).  Every
   // split-bin state is per part: the split slot (SplitSlot) of bin b's part j.
-  static constexpr int kParts = 2;
+  static constexpr int kParts = kStreamParts;
   static constexpr int kSplitSlots = kSplitBins * kParts;
   SplitSlot split[kSplitSlots];
   static int slot_of(int b, int j) { return (b - 3) * kParts + j; }
@@ -640,48 +719,6 @@ struct dm_ctx {
   void* hs_gathered = nullptr;
   ncclComm_t nccl_comm = nullptr;
   bool hs_ordered = false;  // dm_hier_step already ordered the exchange stream after the tick
-  // leaf side: pipelined templates (dm_hier_pipeline).  An exchange stages this
-  // leaf's new templates in a free slot; the leaf's ticks take the staged templates
-  // of the exchanges enqueued before the previous tick (one tick of lag).
-  bool tpl_pipe = false;
-  int tpl_lag = 1;  // ticks between an exchange and the first tick that takes its templates, minus one
-  DBuf<ResCfg> tpl_cfg[kTplSlots];
-  DBuf<ResCold> tpl_cold[kTplSlots];
-  XsTok tpl_ready[kTplSlots];        // root stream: the slot's templates are written
-  XsTok tpl_free[kTplSlots];         // leaf stream: the ticks that read the slot are done
-  bool tpl_free_rec[kTplSlots] = {};  // tpl_free holds a signal
-  struct Staged {
-    int slot;
-    int64_t tag;  // leaf ticks issued before the exchange was enqueued
-  };
-  std::vector<Staged> tpl_pending;          // oldest first
-  std::vector<int> tpl_free_slots;
-  int64_t ticks_issued = 0;
-  // The tick-done signal: ticks numbered by tick_seq (never reset).  The last kernel of
-  // a one-class split tick (C1, C3: the dense kernel, or the rest kernel after it) is
-  // launched with a stop event (hipExtLaunchKernel: the kernel's own completion signal,
-  // no marker packet of its own on the leaf's queue -- each marker cost a ~10-us bubble
-  // per N = 8 shard step), one event per tick in a ring; another queue waits on it.
-  // Round 4 stored a word from a one-wave k_tick_done after the dense kernel (5 us of
-  // the leaf's queue): the N = 8 rehearsal step 60.2-60.7 -> 58.7-58.8 us (round 5,
-  // gpurun_out/r5b2shard, three alternations).
-  // The event covers the tick's leases and sums, not every launch of it: once per row
-  // epoch a writeback tick enqueues k_count_undense after the event-carrying kernel on
-  // the same stream (check_dense).  That kernel only reads the work items' hints and
-  // writes a host-mapped count, which no consumer of the event (the exchange, a template
-  // slot's reuse) touches; a consumer that needed it would have to join the stream.
-  uint64_t tick_seq = 0;          // the last tick's number
-  bool tick_flagged = false;      // ... and whether its last kernels complete tick_ev[*][tick_seq % kTickEv]
-  static constexpr int kTickEv = 16;
-  Event tick_ev[kParts][kTickEv];  // per stream part (one part: [0])
-  int tick_nev[kTickEv] = {};                // the parts that completed each flagged tick's events
-  unsigned tick_part_mask = 0;               // auxiliary streams of the last flagged tick's parts
-  // auxiliary streams with work not yet joined into the context stream
-  unsigned aux_unjoined = 0;
-  // the last tick's events cover every auxiliary stream's unjoined work, so a consumer
-  // may wait on them instead of joining (which would make the next tick's parts wait
-  // for each other: 49 -> 74 us per tick on the N = 8 shard, tools/shard_split.py)
-  bool tick_covers() const { return tick_flagged && tick_part_mask != 0 && (aux_unjoined & ~tick_part_mask) == 0; }
   // a stream part's auxiliary stream (part 0: the bin's class stream).  Part 1 beside
   // bins 4-6's stream 1: stream 2 or 0 run C1 at 40.6-40.8 us per tick, stream 3 at
   // 61.6-64.2 us (which hardware queues pair well: take_aux; profiles/r05_parts_ab.txt)
@@ -689,10 +726,6 @@ struct dm_ctx {
     if (j == 0) return class_stream[b];
     return class_stream[b] != 2 ? 2 : 0;
   }
-  // set by the first consumer on another stream (the exchange's order, a template
-  // slot's reuse): before it, no tick carries the event
-  bool tick_signal_wanted = false;
-  uint64_t tpl_free_seq[kTplSlots] = {};  // a slot is free once this tick's event completed (0: use tpl_free)
   HBuf<uint32_t> h_flags;  // pinned host mirror of upd_flags
   // profiling
   bool profiling = false;
@@ -791,8 +824,8 @@ struct dm_ctx {
 #define DM_ENTER(ctx)                                         \
   do {                                                        \
     DM_CHECK_CTX(ctx);                                        \
-    DM_HIP(ctx, (ctx)->join_aux(), "join auxiliary streams"); \
-    (ctx)->main_dirty = true;                                 \
+    DM_HIP(ctx, (ctx)->order.join(), "join auxiliary streams"); \
+    (ctx)->order.main_has_work();                             \
   } while (0)
 
 // Entry of every call that reads or updates the store: refuse a lost store
@@ -843,7 +876,6 @@ int update_bin4_shape(dm_ctx* c, hipStream_t st);
 int set_parts_ok(dm_ctx* c, bool ok);
 // dm_tick.cpp
 int ready(dm_ctx* c);
-void calib_free(dm_ctx* c);
 // dm_store_update.cpp
 void async_drain(dm_ctx* c);
 int async_retire_all(dm_ctx* c);

@@ -1,6 +1,8 @@
 // dm_hier_host.cpp — the host side of the hierarchy (dm_hier.hip): a leaf's published
 // totals and ring, the root's exchange round and its templates for the leaf, the
-// attached pair's step, and librccl, loaded on first use.
+// attached pair's step, and librccl, loaded on first use.  How the root's stream gets behind
+// the leaf's ticks is asked of dm_tick_order.h (root_round_order, slot_reuse,
+// follow_last_tick) and carried out here.
 #include <dlfcn.h>
 
 #include "dm_ctx.h"
@@ -49,7 +51,7 @@ int dm_publish_ring(dm_ctx* c, int n, void* const* bufs) {
   // every buffer's record 0 starts clear: a tick clears only its own flags words of
   // the next buffer (DevParams::pub_word)
   for (int i = 0; i < n; ++i) DM_HIP(c, hipMemsetAsync(bufs[i], 0, sizeof(double2), c->stream), "publish ring");
-  if (n > 0) c->main_dirty = true;
+  if (n > 0) c->order.main_has_work();
   return DM_OK;
 }
 
@@ -84,23 +86,27 @@ int dm_hier_layout(dm_ctx* root, int n_servers, const int64_t* shard_lo, int64_t
 int dm_hier_pipeline(dm_ctx* leaf, int on) {
   DM_ENTER(leaf);
   if (!leaf->cfg_loaded) return leaf->fail(DM_E_STATE, "load the leaf's configuration first");
-  if (on < 0 || on > dm_ctx::kTplSlots - 1) return leaf->fail(DM_E_INVAL, "pipeline lag must be 0..3");
-  if (!on && leaf->tpl_pipe && !leaf->tpl_pending.empty()) {  // take the newest staged templates now
-    const int take = leaf->tpl_pending.back().slot;
-    DM_HIP(leaf, leaf->xs_wait(leaf->tpl_ready[take], leaf->stream), "staged templates");
-    std::swap(leaf->cfg, leaf->tpl_cfg[take]);
-    std::swap(leaf->cold, leaf->tpl_cold[take]);
+  if (on < 0 || on > kTplSlots - 1) return leaf->fail(DM_E_INVAL, "pipeline lag must be 0..3");
+  TemplatePipe& tp = leaf->tpl;
+  if (!on && tp.on && tp.q.newest() >= 0) {  // take the newest staged templates now
+    const int take = tp.q.newest();
+    DM_HIP(leaf, leaf->order.xs_wait(tp.ready[take], leaf->stream), "staged templates");
+    std::swap(leaf->cfg, tp.cfg[take]);
+    std::swap(leaf->cold, tp.cold[take]);
   }
-  leaf->tpl_pending.clear();
-  leaf->tpl_free_slots.clear();
-  for (int i = 0; i < dm_ctx::kTplSlots; ++i) {
-    leaf->tpl_free_slots.push_back(i);
-    leaf->tpl_free_rec[i] = false;
-  }
+  tp.reset();
   if (on) DM_HIP(leaf, hipStreamSynchronize(leaf->stream), "template slots");  // no tick still reads a slot
-  leaf->tpl_pipe = on != 0;
-  leaf->tpl_lag = on > 1 ? on : 1;
+  tp.on = on != 0;
+  tp.q.lag = on > 1 ? on : 1;
   return DM_OK;
+}
+
+// Stream s behind the leaf's last tick, as dm_tick_order.h decided: on the tick's events,
+// or on an event recorded on the leaf's context stream.
+static hipError_t wait_leaf(dm_ctx* leaf, TickWait how, hipStream_t s) {
+  if (how == TickWait::tick_events) return leaf->done.wait(leaf->done.sig.seq, s);
+  if (how == TickWait::event) return leaf->order.xs_order(StreamOrder::XS_LEAF, leaf->stream, s);
+  return hipSuccess;
 }
 
 // One exchange round of the hierarchy (server.go:227-323 -> :822-901): decide the
@@ -109,16 +115,6 @@ int dm_hier_pipeline(dm_ctx* leaf, int on) {
 // its leaf -- in place, or into a staged slot the leaf takes one tick later
 // (dm_hier_pipeline).  Stream-ordered: the all-gather that produced `gathered`
 // must precede it on the root's stream.
-// The exchange's stream after leaf tick `seq`: its parts' events (dm_ctx::tick_ev).
-static hipError_t wait_tick(dm_ctx* leaf, uint64_t seq, hipStream_t s) {
-  const int k = (int)(seq % dm_ctx::kTickEv);
-  for (int j = 0; j < std::max(leaf->tick_nev[k], 1); ++j) {
-    hipError_t e = hipStreamWaitEvent(s, leaf->tick_ev[j][k], 0);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
 int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t now_ns, dm_ctx* leaf, int server) {
   DM_ENTER(root);
   DM_STORE_OK(root);
@@ -145,53 +141,48 @@ int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t
     return root->fail(DM_E_STATE, "the leaf must hold exactly this server's resources");
   const int64_t stride = root->hier_G != 0 ? root->hier_stride : 1 + root->R;
   const bool same = root->stream == leaf->stream;
-  // A pipelined leaf whose last tick's events cover its streams stays unjoined (the
-  // round writes a free template slot, and waits on those events); otherwise the leaf's
-  // streams join first.
-  const bool cover = !same && leaf->tpl_pipe && leaf->tick_covers();
-  if (!cover) {
-    DM_HIP(root, leaf->join_aux(), "join leaf streams");
-    leaf->main_dirty = true;
+  TemplatePipe& tp = leaf->tpl;
+  const RoundOrder ro = root_round_order(leaf->done.sig, same, tp.on, root->hs_ordered);
+  if (ro.join) {
+    DM_HIP(root, leaf->order.join(), "join leaf streams");
+    leaf->order.main_has_work();
   }
   DM_HIP(root, root->hier_status.ensure((size_t)kHierMaxServers), "hierarchy status");
   root->hier_servers = n_servers;
-  if (!same && !root->hs_ordered) {  // the root round after the leaf's prior work (its publish)
-    if (cover) DM_HIP(root, wait_tick(leaf, leaf->tick_seq, root->stream), "leaf->root order");
-    else DM_HIP(root, leaf->xs_order(dm_ctx::XS_LEAF, leaf->stream, root->stream), "leaf->root order");
-  }
+  DM_HIP(root, wait_leaf(leaf, ro.wait, root->stream), "leaf->root order");
   ResCfg* tcfg = leaf->cfg.p;
   ResCold* tcold = leaf->cold.p;
   const ResCfg* pcfg = leaf->cfg.p;
   const ResCold* pcold = leaf->cold.p;
   int slot = -1;
-  if (leaf->tpl_pipe) {
-    if (leaf->tpl_free_slots.empty())
+  if (tp.on) {
+    if ((slot = tp.q.next_free()) < 0)
       return root->fail(DM_E_STATE, "too many staged exchanges: tick the leaf between exchanges");
-    slot = leaf->tpl_free_slots.front();
-    DM_HIP(root, leaf->tpl_cfg[slot].ensure((size_t)leaf->R), "template slot");
-    DM_HIP(root, leaf->tpl_cold[slot].ensure((size_t)leaf->R), "template slot");
-    if (leaf->stream != root->stream) leaf->tick_signal_wanted = true;
-    if (leaf->stream == root->stream) {
-      // stream order: the ticks that read the slot's old templates precede this round
-    } else if (leaf->tpl_free_rec[slot] && leaf->tpl_free_seq[slot] > 0) {  // the ticks that read the slot's old
-      if (cover && root->hs_ordered && leaf->tpl_free_seq[slot] <= leaf->tick_seq) {  // templates are done
-        // this round already waits for the leaf's last tick, whose events cover every
-        // earlier tick on the same streams
-      } else if (leaf->tick_seq - leaf->tpl_free_seq[slot] < (uint64_t)dm_ctx::kTickEv - 1) {
-        DM_HIP(root, wait_tick(leaf, leaf->tpl_free_seq[slot], root->stream), "template slot");
-      } else {  // that tick's events were recorded again since: everything the leaf holds
-        DM_HIP(root, leaf->join_aux(), "join leaf streams");
-        leaf->main_dirty = true;
-        DM_HIP(root, leaf->xs_order(dm_ctx::XS_LEAF, leaf->stream, root->stream), "template slot");
-      }
+    DM_HIP(root, tp.cfg[slot].ensure((size_t)leaf->R), "template slot");
+    DM_HIP(root, tp.cold[slot].ensure((size_t)leaf->R), "template slot");
+    if (!same) leaf->done.sig.want();
+    // the ticks that read the slot's old templates are done before the round writes it
+    switch (slot_reuse(leaf->done.sig, same, tp.free_rec[slot], tp.free_seq[slot], ro.cover, root->hs_ordered)) {
+      case SlotReuse::stream_order:
+      case SlotReuse::covered:
+      case SlotReuse::none: break;
+      case SlotReuse::tick_events:
+        DM_HIP(root, leaf->done.wait(tp.free_seq[slot], root->stream), "template slot");
+        break;
+      case SlotReuse::join_then_event:
+        DM_HIP(root, leaf->order.join(), "join leaf streams");
+        leaf->order.main_has_work();
+        DM_HIP(root, wait_leaf(leaf, TickWait::event, root->stream), "template slot");
+        break;
+      case SlotReuse::lazy_token:
+        DM_HIP(root, leaf->order.xs_wait(tp.free[slot], root->stream), "template slot");
+        break;
     }
-    else if (leaf->tpl_free_rec[slot])
-      DM_HIP(root, leaf->xs_wait(leaf->tpl_free[slot], root->stream), "template slot");
-    tcfg = leaf->tpl_cfg[slot].p;
-    tcold = leaf->tpl_cold[slot].p;
-    if (!leaf->tpl_pending.empty()) {  // a rejected round keeps the newest staged templates
-      pcfg = leaf->tpl_cfg[leaf->tpl_pending.back().slot].p;
-      pcold = leaf->tpl_cold[leaf->tpl_pending.back().slot].p;
+    tcfg = tp.cfg[slot].p;
+    tcold = tp.cold[slot].p;
+    if (tp.q.newest() >= 0) {  // a rejected round keeps the newest staged templates
+      pcfg = tp.cfg[tp.q.newest()].p;
+      pcold = tp.cold[tp.q.newest()].p;
     }
   }
   DevParams p{};
@@ -233,16 +224,14 @@ int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t
   DM_HIP(root, root->timed(KC_HIER_ROOT, root->stream, [&] { return launch_hier_tick(p, ha, root->stream); }),
          "hierarchy root tick");
   if (slot >= 0) {
-    leaf->tpl_free_slots.erase(leaf->tpl_free_slots.begin());
     if (same)  // the leaf's ticks follow in stream order
-      leaf->xs_signal_lazy(dm_ctx::XS_READY0 + slot, root->stream, &leaf->tpl_ready[slot]);
+      leaf->order.xs_signal_lazy(StreamOrder::XS_READY0 + slot, root->stream, &tp.ready[slot]);
     else
-      DM_HIP(root,
-             leaf->xs_signal(dm_ctx::XS_READY0 + slot, root->stream, &leaf->tpl_ready[slot]),
+      DM_HIP(root, leaf->order.xs_signal(StreamOrder::XS_READY0 + slot, root->stream, &tp.ready[slot]),
              "staged templates");
-    leaf->tpl_pending.push_back(dm_ctx::Staged{slot, leaf->ticks_issued});
+    tp.q.stage(slot);
   } else if (!same) {  // the leaf's next tick after its new templates
-    DM_HIP(root, leaf->xs_order(dm_ctx::XS_ROOT, root->stream, leaf->stream), "root->leaf order");
+    DM_HIP(root, leaf->order.xs_order(StreamOrder::XS_ROOT, root->stream, leaf->stream), "root->leaf order");
   }
   root->maybe_general = true;  // rows carry heterogeneous subclient counts
   root->all_sub_one = false;
@@ -345,7 +334,7 @@ int dm_hier_attach(dm_ctx* leaf, dm_ctx* root, int server, void* const* ring, in
   if (root->hier_G > 1 && !gathered) return root->fail(DM_E_INVAL, "several servers need a gathered buffer");
   int rc = dm_publish_ring(leaf, nring, ring);
   if (rc) return rc;
-  if ((rc = dm_hier_pipeline(leaf, leaf->tpl_pipe ? leaf->tpl_lag : 1))) return rc;
+  if ((rc = dm_hier_pipeline(leaf, leaf->tpl.on ? leaf->tpl.q.lag : 1))) return rc;
   if ((rc = dm_set_stream(root, exchange_stream ? exchange_stream : leaf->stream))) return rc;
   // an exchange on a stream of its own waits for every leaf tick: no stream parts
   if ((rc = set_parts_ok(leaf, root->stream == leaf->stream))) return rc;
@@ -369,15 +358,11 @@ int dm_hier_step(dm_ctx* leaf, dm_ctx* root, int64_t now_ns) {
     // the exchange stream after the tick that wrote the block: on the tick's events when
     // its last kernels complete them (no marker on the leaf's queues; the leaf's stream
     // parts stay unjoined), else after a join, on an event
-    const bool cover = leaf->stream != root->stream && leaf->tick_covers();
-    if (!cover) DM_HIP(root, leaf->join_aux(), "join leaf streams");
-    if (leaf->stream != root->stream) leaf->tick_signal_wanted = true;
-    if (leaf->stream == root->stream) {
-      // stream order
-    } else if (cover || (leaf->tick_flagged && leaf->tick_part_mask == 0))
-      DM_HIP(root, wait_tick(leaf, leaf->tick_seq, root->stream), "leaf->exchange order");
-    else
-      DM_HIP(root, leaf->xs_order(dm_ctx::XS_LEAF, leaf->stream, root->stream), "leaf->exchange order");
+    const bool same = leaf->stream == root->stream;
+    const FollowOrder fo = follow_last_tick(leaf->done.sig, same);
+    if (fo.join) DM_HIP(root, leaf->order.join(), "join leaf streams");
+    if (!same) leaf->done.sig.want();
+    DM_HIP(root, wait_leaf(leaf, fo.wait, root->stream), "leaf->exchange order");
     const size_t bytes = (size_t)root->hier_stride * 16;
     // (timed as one class on the exchange stream while profiling: bench.py's exchange_us)
     if (root->nccl_comm) {  // every server's block, in server order, over xGMI

@@ -250,9 +250,9 @@ int dm::set_parts_ok(dm_ctx* c, bool ok) {
   if (c->parts_ok == ok) return DM_OK;
   c->parts_ok = ok;
   if (!c->h_dq.p) return DM_OK;  // no plan yet: upload_plan reads the flag
-  DM_HIP(c, c->join_aux(), "join");
+  DM_HIP(c, c->order.join(), "join");
   if (int rc = c->synced("stream parts")) return rc;
-  c->main_dirty = true;
+  c->order.main_has_work();
   if (int rc = init_split_slots(c, c->stream)) return rc;
   return update_bin4_shape(c, c->stream);
 }

@@ -31,10 +31,10 @@ int dm_device_count(int* out) {
   return DM_OK;
 }
 
-// The context's cross-stream order (dm_ctx::xs_signal): one event per hop kind.
+// The context's cross-stream order (StreamOrder::xs_signal): one event per hop kind.
 static hipError_t xs_setup(dm_ctx* c) {
-  for (int i = 0; i < dm_ctx::XS_N; ++i) {
-    hipError_t e = c->xs_ev[i].create(hipEventDisableTiming);
+  for (int i = 0; i < StreamOrder::XS_N; ++i) {
+    hipError_t e = c->order.xs_ev[i].create(hipEventDisableTiming);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -89,30 +89,30 @@ static hipError_t take_aux(dm_ctx* c, int ncu) {
         best = i;
     if (best < g_aux_free.size()) {
       const AuxSet& a = g_aux_free[best];
-      for (int k = 0; k < dm_ctx::kAux; ++k) c->aux[k] = a.s[k];
+      for (int k = 0; k < dm_ctx::kAux; ++k) c->order.aux[k] = a.s[k];
       c->own_stream = a.own;
       c->cpy = a.cpy;
-      c->aux_own_queue = a.own_queue;
-      c->aux_seq = a.seq;
+      c->order.aux_own_queue = a.own_queue;
+      c->order.aux_seq = a.seq;
       g_aux_free.erase(g_aux_free.begin() + (ptrdiff_t)best);
       return hipSuccess;
     }
-    c->aux_seq = g_aux_seq++;
+    c->order.aux_seq = g_aux_seq++;
     static bool registered = false;
     if (!registered) registered = std::atexit(release_aux_pool) == 0;
   }
   const size_t mwords = (size_t)std::max(1, (ncu + 31) / 32);
   std::vector<uint32_t> mask(mwords, 0u);
   for (int b = 0; b < ncu; ++b) mask[(size_t)(b / 32)] |= 1u << (b % 32);
-  c->aux_own_queue = true;
+  c->order.aux_own_queue = true;
   // the creation order is measured (above)
   hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
   for (int i = 0; i < dm_ctx::kAux && e == hipSuccess; ++i) {
-    hipStream_t* slot = &c->aux[i];
+    hipStream_t* slot = &c->order.aux[i];
     e = ncu > 0 ? hipExtStreamCreateWithCUMask(slot, (uint32_t)mwords, mask.data()) : hipErrorNotSupported;
     if (e != hipSuccess) {  // no CU masks here: a plain stream (correct, queue sharing as above)
       (void)hipGetLastError();
-      c->aux_own_queue = false;
+      c->order.aux_own_queue = false;
       e = hipStreamCreateWithFlags(slot, hipStreamNonBlocking);
     }
   }
@@ -121,15 +121,15 @@ static hipError_t take_aux(dm_ctx* c, int ncu) {
 }
 
 static void give_aux(dm_ctx* c) {
-  if (!c->aux[0] || !c->own_stream || !c->cpy) return;
+  if (!c->order.aux[0] || !c->own_stream || !c->cpy) return;
   (void)hipStreamSynchronize(c->own_stream);
   (void)hipStreamSynchronize(c->cpy);
-  AuxSet a{c->device, c->aux_seq, {}, c->own_stream, c->cpy, c->aux_own_queue};
+  AuxSet a{c->device, c->order.aux_seq, {}, c->own_stream, c->cpy, c->order.aux_own_queue};
   c->own_stream = c->cpy = nullptr;
   for (int k = 0; k < dm_ctx::kAux; ++k) {
-    (void)hipStreamSynchronize(c->aux[k]);
-    a.s[k] = c->aux[k];
-    c->aux[k] = nullptr;
+    (void)hipStreamSynchronize(c->order.aux[k]);
+    a.s[k] = c->order.aux[k];
+    c->order.aux[k] = nullptr;
   }
   std::lock_guard<std::mutex> lk(g_aux_mu);
   g_aux_free.push_back(a);
@@ -162,8 +162,8 @@ int dm_create(int device, dm_ctx** out) {
   if (const char* sc = getenv("DM_SPEC_CHAIN")) c->spec_chain = atoi(sc) != 0;
   if (const char* rl = getenv("DM_REDO_LIGHT")) c->redo_light = atoi(rl);
   if (const char* qc = getenv("DM_QUEUE_CALIB")) {  // 0: keep the creation-order queue assignment; 2: log
-    if (atoi(qc) == 0) c->calib = 4;
-    c->calib_log = atoi(qc) == 2;
+    if (atoi(qc) == 0) c->qcal.cal.phase = QueueCalib::Phase::Done;
+    c->qcal.cal.log = atoi(qc) == 2;
   }
   if (const char* ds = getenv("DM_DENSE_SPLIT")) {
     const int v = (int)strtol(ds, nullptr, 0);
@@ -196,7 +196,7 @@ int dm_create(int device, dm_ctx** out) {
     if (e == hipSuccess) e = a.ev_done.create(hipEventDisableTiming);
   }
   for (int j = 0; j < dm_ctx::kParts; ++j)
-    for (int i = 0; i < dm_ctx::kTickEv && e == hipSuccess; ++i) e = c->tick_ev[j][i].create(hipEventDefault);
+    for (int i = 0; i < kTickEv && e == hipSuccess; ++i) e = c->done.ev[j][i].create(hipEventDefault);
   if (e != hipSuccess) {
     g_last_error = std::string("stream/event setup: ") + hipGetErrorString(e);
     dm_destroy(c);
@@ -216,15 +216,15 @@ void dm_destroy(dm_ctx* c) {
   // deferred tick work (DM_DEFER_JOIN) and update copies may still run on the
   // auxiliary streams: drain every stream before any buffer is freed
   for (int i = 0; i < dm_ctx::kAux; ++i)
-    if (c->aux[i]) (void)hipStreamSynchronize(c->aux[i]);
+    if (c->order.aux[i]) (void)hipStreamSynchronize(c->order.aux[i]);
   if (c->cpy) (void)hipStreamSynchronize(c->cpy);
   (void)hipStreamSynchronize(c->stream);
   c->collect_profile();
   for (auto e : c->event_pool) (void)hipEventDestroy(e);
-  calib_free(c);
+  c->qcal.free();
   give_aux(c);  // kept for the next context on this device (take_aux)
   for (int i = 0; i < dm_ctx::kAux; ++i)  // (a set not returned whole)
-    if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]);
+    if (c->order.aux[i]) (void)hipStreamDestroy(c->order.aux[i]);
   if (c->cpy) {
     (void)hipStreamSynchronize(c->cpy);
     (void)hipStreamDestroy(c->cpy);
@@ -240,11 +240,9 @@ int dm_set_stream(dm_ctx* c, void* s) {
   DM_HIP(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
   // the template slots' lazy signals on the old stream are complete now, and that
   // stream may not outlive this call: never record on it again
-  for (int i = 0; i < dm_ctx::kTplSlots; ++i)
-    for (dm_ctx::XsTok* t : {&c->tpl_ready[i], &c->tpl_free[i]})
-      if (!t->rec && t->s == c->stream) t->s = nullptr;
+  c->tpl.forget_stream(c->stream);
   c->stream = s ? (hipStream_t)s : c->own_stream;
-  c->main_dirty = true;
+  c->order.main_has_work();
   return DM_OK;
 }
 
@@ -258,7 +256,7 @@ int dm_join(dm_ctx* c) {
 int dm_stream_wait(dm_ctx* c, void* s) {
   DM_ENTER(c);
   if (!s) return c->fail(DM_E_INVAL, "null stream");
-  DM_HIP(c, c->xs_order(dm_ctx::XS_EXT, c->stream, (hipStream_t)s), "stream order");
+  DM_HIP(c, c->order.xs_order(StreamOrder::XS_EXT, c->stream, (hipStream_t)s), "stream order");
   return DM_OK;
 }
 
@@ -330,13 +328,13 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   v[4 + kNumBins] = (c->bin6_wide ? 1 : 0) | (c->bin4_wave ? 2 : 0);  // bit 0: bin 6 on 512 x 8 (else 256 x 16); bit 1: bin 4 on 64 x 16
   v[5 + kNumBins] = c->redo_cap;  // 3/4 of the redo's full-build workgroups the GPU holds at once
   v[6 + kNumBins] = 1;            // every store may speculate (the redo by teams has no bound)
-  v[7 + kNumBins] = c->aux_own_queue ? 1 : 0;  // the work classes' streams each have a hardware queue
+  v[7 + kNumBins] = c->order.aux_own_queue ? 1 : 0;  // the work classes' streams each have a hardware queue
   int64_t parts = 1;  // the stream parts of the store's one workgroup bin (dm_ctx::kParts), else 1
   for (int b = 0; b < kNumBins; ++b) parts = std::max<int64_t>(parts, c->bin_parts[b]);
   v[8 + kNumBins] = parts;
-  // the class streams' queue assignment the calibration chose (dm_ctx::calib): perm[0] +
+  // the class streams' queue assignment the calibration chose (QueueCalib): perm[0] +
   // 4 perm[1] + 16 perm[2] + 64 perm[3], or -1 before it has finished (or with shared queues)
-  v[9 + kNumBins] = c->calib_best;
+  v[9 + kNumBins] = c->qcal.cal.best;
   // the column the last writeback tick wrote: 1 the has column (in place), 0 the alternate
   // column, -1 before any writeback tick
   v[10 + kNumBins] = c->wb_inplace;

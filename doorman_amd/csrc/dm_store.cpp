@@ -147,7 +147,7 @@ int dm_config_load(dm_ctx* c, int64_t R, const dm_resource_cfg* cfg) {
                    (int32_t)cfg->lease_length_s[r], cfg->kind[r]};
     rcold[r] = ResCold{cfg->safe_capacity[r], (int32_t)cfg->refresh_interval_s[r], 0};
   }
-  c->tpl_pending.clear();  // staged exchanges were computed for the old configuration
+  c->tpl.q.drop_pending();  // staged exchanges were computed for the old configuration
   DM_HIP(c, upload(c->cfg, rc.data(), (size_t)R, st), "upload config");
   DM_HIP(c, upload(c->cold, rcold.data(), (size_t)R, st), "upload config");
   c->h_refresh_s.assign(cfg->refresh_interval_s, cfg->refresh_interval_s + R);

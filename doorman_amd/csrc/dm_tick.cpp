@@ -1,6 +1,8 @@
 // dm_tick.cpp — dm_apportion: one tick's launches over the plan's work classes and their
 // streams (struct Tick), and what a tick does first: the readiness check, a pipelined
-// leaf's staged templates, the queue calibration's windows.
+// leaf's staged templates, the queue calibration's windows.  Which stream waits for which
+// is asked of dm_tick_order.h and carried out by the context's owners (dm_ctx.h StreamOrder,
+// TickDone, TemplatePipe, QueueCalibration).
 // A workgroup bin's stream part (Tick::bin_part) works on its split slot (dm_ctx.h
 // SplitSlot): it reads the slot's host-mapped words, asks dm_split_form.h for the form of
 // this tick's launches (try_split, choose_form: the one place the forms and the key rule
@@ -21,183 +23,101 @@ int dm::ready(dm_ctx* c) {
 // the exchanges enqueued before the previous tick (stream-ordered after their root
 // kernels); the slot they replace becomes free once the ticks that read it are done.
 static int commit_templates(dm_ctx* c) {
-  int take = -1;
-  size_t n = 0;
-  while (n < c->tpl_pending.size() && c->tpl_pending[n].tag + (c->tpl_lag - 1) < c->ticks_issued)
-    take = c->tpl_pending[n++].slot;
-  for (size_t i = 0; i + 1 < n; ++i) c->tpl_free_slots.push_back(c->tpl_pending[i].slot);  // superseded
-  c->tpl_pending.erase(c->tpl_pending.begin(), c->tpl_pending.begin() + (ptrdiff_t)n);
+  TemplatePipe& tp = c->tpl;
+  const int take = tp.q.take();
   if (take < 0) return DM_OK;
-  const dm_ctx::XsTok& rt = c->tpl_ready[take];
+  const StreamOrder::XsTok& rt = tp.ready[take];
   const bool host_wait = rt.rec && rt.s && rt.s != c->stream;
-  // deferred class work also read the old templates: joined, unless the last tick's
-  // events cover it (the slot's reuse then waits on them, below)
-  const bool keep = host_wait && c->tick_covers();
-  if (!keep) DM_HIP(c, c->join_aux(), "join");
+  const TakeOrder o = take_templates(c->done.sig, host_wait);
+  if (o.join) DM_HIP(c, c->order.join(), "join");
   if (host_wait) {
     // poll: the wake-up of a blocking wait comes too late for the next launch to be
     // queued in time.  Bounded by time (the exchange may wait on a slower rank's
     // all-gather): after 50 us of polling, a blocking wait frees the core.
-    hipError_t q = hipEventQuery(c->xs_ev[rt.w]);
+    hipError_t q = hipEventQuery(c->order.xs_ev[rt.w]);
     if (q == hipErrorNotReady) {
       timespec t0{}, t1{};
       clock_gettime(CLOCK_MONOTONIC, &t0);
       do {
-        q = hipEventQuery(c->xs_ev[rt.w]);
+        q = hipEventQuery(c->order.xs_ev[rt.w]);
         clock_gettime(CLOCK_MONOTONIC, &t1);
       } while (q == hipErrorNotReady &&
                (t1.tv_sec - t0.tv_sec) * 1000000000LL + (t1.tv_nsec - t0.tv_nsec) < 50000);
     }
-    if (q == hipErrorNotReady) q = hipEventSynchronize(c->xs_ev[rt.w]);
+    if (q == hipErrorNotReady) q = hipEventSynchronize(c->order.xs_ev[rt.w]);
     if (q != hipSuccess) return c->hip_fail(q, "staged templates");
   } else {
-    DM_HIP(c, c->xs_wait(rt, c->stream), "staged templates");
+    DM_HIP(c, c->order.xs_wait(rt, c->stream), "staged templates");
   }
-  if (!keep) c->main_dirty = true;  // the class streams fork after the wait
-  std::swap(c->cfg, c->tpl_cfg[take]);
-  std::swap(c->cold, c->tpl_cold[take]);
-  // the old templates (now in slot `take`) are free after the ticks already enqueued
-  // the next exchange into it waits for the ticks enqueued so far: on the last tick's
-  // events (tick_ev, every stream part's) when its last kernels complete them, else on
-  // a (lazy) event
-  c->tpl_free_seq[take] = c->tick_flagged ? c->tick_seq : 0;
-  c->xs_signal_lazy(dm_ctx::XS_FREE0 + take, c->stream, &c->tpl_free[take]);
-  c->tpl_free_rec[take] = true;
-  c->tpl_free_slots.push_back(take);
+  if (o.dirty) c->order.main_has_work();  // the class streams fork after the wait
+  std::swap(c->cfg, tp.cfg[take]);
+  std::swap(c->cold, tp.cold[take]);
+  // the old templates (now in slot `take`) are free after the ticks enqueued so far: the
+  // next exchange into it waits on the last tick's events (every stream part's) when its
+  // last kernels complete them, else on a (lazy) event
+  tp.free_seq[take] = o.free_seq;
+  c->order.xs_signal_lazy(StreamOrder::XS_FREE0 + take, c->stream, &tp.free[take]);
+  tp.free_rec[take] = true;
+  tp.q.release(take);
   return DM_OK;
 }
 
-// One forked writeback tick's part in the queue calibration (dm_ctx::calib), called
-// before the tick forks.  Window boundaries join every class stream into the context
+// The queue calibration (dm_tick_order.h QueueCalib says what each forked writeback tick
+// does, before it forks).  Window boundaries join every class stream into the context
 // stream (so the next window's assignment starts after the last one's work: a class's
 // consecutive ticks on two streams are then still ordered) and record an event there.
-static hipError_t calib_apply(dm_ctx* c, const std::array<int, dm_ctx::kAux>& pm) {
-  hipError_t e = c->join_aux();
+static hipError_t calib_apply(dm_ctx* c, const QueueCalib::Perm& pm) {
+  hipError_t e = c->order.join();
   if (e != hipSuccess) return e;
-  for (int i = 0; i < dm_ctx::kAux; ++i) {
-    c->perm[i] = pm[(size_t)i];
-    c->aux[i] = c->aux_phys[pm[(size_t)i]];
+  for (int i = 0; i < kAux; ++i) {
+    c->qcal.perm[i] = pm[(size_t)i];
+    c->order.aux[i] = c->qcal.phys[pm[(size_t)i]];
   }
-  c->main_dirty = true;  // the next tick forks: every class stream waits for the context stream
+  c->order.main_has_work();  // the next tick forks: every class stream waits for the context stream
   return hipSuccess;
 }
 
 static hipError_t calib_mark(dm_ctx* c, bool end) {
   if (end) {
     hipEvent_t ev;
-    hipError_t e = c->join_aux();
+    hipError_t e = c->order.join();
     if (e == hipSuccess) e = hipEventCreate(&ev);
     if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
     if (e != hipSuccess) return e;
-    c->calib_ev.back().second = ev;
-    c->main_dirty = true;
+    c->qcal.ev.back().second = ev;
+    c->order.main_has_work();
     return hipSuccess;
   }
   hipEvent_t ev;
   hipError_t e = hipEventCreate(&ev);
   if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
   if (e != hipSuccess) return e;
-  c->calib_ev.push_back({ev, nullptr});
-  c->calib_of_ev.push_back(c->calib_k);
+  c->qcal.ev.push_back({ev, nullptr});
   return hipSuccess;
 }
 
-void dm::calib_free(dm_ctx* c) {
-  for (auto& pr : c->calib_ev) {
-    if (pr.first) (void)hipEventDestroy(pr.first);
-    if (pr.second) (void)hipEventDestroy(pr.second);
-  }
-  c->calib_ev.clear();
-  c->calib_of_ev.clear();
-}
-
 static hipError_t calib_step(dm_ctx* c) {
-  if (c->calib == 4) return hipSuccess;
-  if (c->calib == 0) {
-    if (!c->aux_own_queue) {  // shared queues: the assignment does not choose hardware queues
-      c->calib = 4;
-      return hipSuccess;
-    }
-    if (++c->calib_skip < dm_ctx::kCalibSkip) return hipSuccess;
-    for (int i = 0; i < dm_ctx::kAux; ++i) c->aux_phys[i] = c->aux[i];
-    std::array<int, dm_ctx::kAux> pm{0, 1, 2, 3};
-    c->calib_cand.clear();
-    do c->calib_cand.push_back(pm);
-    while (std::next_permutation(pm.begin(), pm.end()));
-    c->calib = 1;
-    c->calib_round = 1;
-    c->calib_k = 0;
-    c->calib_t = 1;  // this tick is the window's first
-    hipError_t e = calib_apply(c, c->calib_cand[0]);
-    return e == hipSuccess ? calib_mark(c, false) : e;
-  }
-  if (c->calib == 1 || c->calib == 2) {
-    const int win = c->calib == 1 ? dm_ctx::kCalibWin : dm_ctx::kCalibWin2;
-    if (++c->calib_t <= win) return hipSuccess;
-    hipError_t e = calib_mark(c, true);
+  using Action = QueueCalib::Action;
+  QueueCalibration& qc = c->qcal;
+  Action a = qc.cal.on_tick(c->order.aux_own_queue);
+  hipError_t e = hipSuccess;
+  if (a.kind == Action::start)  // the first window: the streams as they were created
+    for (int i = 0; i < kAux; ++i) qc.phys[i] = c->order.aux[i];
+  if (a.kind == Action::close_then_start || a.kind == Action::close_then_wait) e = calib_mark(c, true);
+  if (a.kind == Action::poll) {  // the last window's end event done?  then every window's time
+    e = hipEventQuery(qc.ev.back().second);
+    if (e == hipErrorNotReady) return hipSuccess;
+    std::vector<float> ms(qc.ev.size(), 0.0f);
+    for (size_t w = 0; w < qc.ev.size() && e == hipSuccess; ++w)
+      e = hipEventElapsedTime(&ms[w], qc.ev[w].first, qc.ev[w].second);
     if (e != hipSuccess) return e;
-    c->calib_t = 1;
-    const int ncand = (int)c->calib_cand.size();
-    if (++c->calib_k < ncand) {
-      e = calib_apply(c, c->calib_cand[(size_t)c->calib_k]);
-      return e == hipSuccess ? calib_mark(c, false) : e;
-    }
-    c->calib = 3;  // wait for the windows' events (polled by later ticks)
-    return hipSuccess;
+    a = qc.cal.on_times(ms);
+    qc.free();
   }
-  // calib == 3: the last window's end event done?  then pick
-  const hipError_t q = hipEventQuery(c->calib_ev.back().second);
-  if (q == hipErrorNotReady) return hipSuccess;
-  if (q != hipSuccess) return q;
-  std::vector<std::pair<float, size_t>> t;
-  for (size_t w = 0; w < c->calib_ev.size(); ++w) {
-    float ms = 0.0f;
-    hipError_t e = hipEventElapsedTime(&ms, c->calib_ev[w].first, c->calib_ev[w].second);
-    if (e != hipSuccess) return e;
-    t.push_back({ms, w});
-  }
-  if (c->calib_log) {  // test hook (DM_QUEUE_CALIB=2): every window's assignment and time per tick
-    const int win = c->calib_round == 1 ? dm_ctx::kCalibWin : dm_ctx::kCalibWin2;
-    for (const auto& pr : t) {
-      const auto& pm = c->calib_cand[(size_t)c->calib_of_ev[pr.second]];
-      fprintf(stderr, "[dm queue calibration] round %d perm %d%d%d%d %.2f us/tick\n", win == dm_ctx::kCalibWin ? 1 : 2,
-              pm[0], pm[1], pm[2], pm[3], 1000.0 * pr.first / win);
-    }
-  }
-  std::sort(t.begin(), t.end());
-  if (c->calib == 3 && c->calib_round == 1) {  // round 2: the best of round 1 over longer windows
-    // the best kCalibFinal of round 1, and the creation-order assignment (the measured
-    // default) so that the choice is never worse than not calibrating
-    std::vector<std::array<int, dm_ctx::kAux>> fin;
-    const std::array<int, dm_ctx::kAux> ident{0, 1, 2, 3};
-    for (int i = 0; i < dm_ctx::kCalibFinal; ++i) fin.push_back(c->calib_cand[(size_t)c->calib_of_ev[t[(size_t)i].second]]);
-    if (std::find(fin.begin(), fin.end(), ident) == fin.end()) fin.push_back(ident);
-    calib_free(c);
-    c->calib_cand.clear();
-    for (int r = 0; r < dm_ctx::kCalibRep2; ++r)  // interleaved: fin[0], fin[1], ..., fin[0], ...
-      c->calib_cand.insert(c->calib_cand.end(), fin.begin(), fin.end());
-    c->calib = 2;
-    c->calib_round = 2;
-    c->calib_k = 0;
-    c->calib_t = 1;
-    hipError_t e = calib_apply(c, c->calib_cand[0]);
-    return e == hipSuccess ? calib_mark(c, false) : e;
-  }
-  // round 2: each candidate's windows summed
-  std::vector<std::pair<std::array<int, dm_ctx::kAux>, float>> sum;
-  for (const auto& pr : t) {
-    const auto& pm = c->calib_cand[(size_t)c->calib_of_ev[pr.second]];
-    auto it = std::find_if(sum.begin(), sum.end(), [&](const auto& x) { return x.first == pm; });
-    if (it == sum.end()) sum.push_back({pm, pr.first});
-    else it->second += pr.first;
-  }
-  const auto best = std::min_element(sum.begin(), sum.end(), [](const auto& a, const auto& b) {
-                      return a.second < b.second;
-                    })->first;
-  calib_free(c);
-  c->calib = 4;
-  c->calib_best = best[0] + 4 * best[1] + 16 * best[2] + 64 * best[3];
-  return calib_apply(c, best);
+  if (e != hipSuccess) return e;
+  if (a.kind == Action::none || a.kind == Action::close_then_wait) return hipSuccess;
+  e = calib_apply(c, a.perm);
+  return e == hipSuccess && a.kind != Action::done ? calib_mark(c, false) : e;
 }
 
 // Once per row epoch, after a writeback tick of a workgroup bin's stream part (its split
@@ -232,7 +152,7 @@ struct Tick {
   hipError_t timed(int cls, hipStream_t s, F&& fn) {
     return c->timed(cls, s, fn);
   }
-  hipStream_t cls_stream(int cls) const { return fork ? c->aux[c->class_stream[cls]] : st; }
+  hipStream_t cls_stream(int cls) const { return fork ? c->order.aux[c->class_stream[cls]] : st; }
 
   int outputs();      // the output columns and DevParams
   int streams();      // the worklist, the streams in use and the fork
@@ -347,7 +267,7 @@ int Tick::streams() {
   general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
   if (general) {  // only non-small resources are ever appended to the worklist
     DM_HIP(c, hipMemsetAsync(gc, 0, sizeof(int32_t), st), "worklist reset");
-    c->main_dirty = true;
+    c->order.main_has_work();
   }
   // Independent work classes: large resources (a 5-kernel chain), big groups,
   // small groups + packed.  With more than one class present they run on the
@@ -368,19 +288,15 @@ int Tick::streams() {
   bool parts_only = false;
   for (int b = 0; b < kNumBins; ++b) parts_only |= !c->h_bins[b].empty() && c->bin_parts[b] > 1;
   one_class = (!fork || parts_only) && nch == 0 && c->h_tiles.empty() && !general && nonempty_bins == 1;
-  if (fork && wb && c->tick_signal_wanted == false) DM_HIP(c, calib_step(c), "queue calibration");
+  if (fork && wb && !c->done.sig.wanted) DM_HIP(c, calib_step(c), "queue calibration");
   s_large = cls_stream(kNumBins + 1);
   s_small = cls_stream(kNumBins);
   if (!fork) {  // everything on the context stream, after any deferred class work
-    DM_HIP(c, c->join_aux(), "join");
-    c->main_dirty = true;
-  } else if (c->main_dirty) {  // class streams wait for what the context stream holds
-    dm_ctx::XsTok fk;
-    DM_HIP(c, c->xs_signal(dm_ctx::XS_FORK, st, &fk), "fork");
-    for (int i = 0; i < dm_ctx::kAux; ++i) DM_HIP(c, c->xs_wait(fk, c->aux[i]), "fork");
-    c->main_dirty = false;
+    DM_HIP(c, c->order.join(), "join");
+    c->order.main_has_work();
+  } else {  // class streams wait for what the context stream holds
+    DM_HIP(c, c->order.fork(used), "fork");
   }
-  if (fork) c->aux_unjoined |= used;
   return DM_OK;
 }
 
@@ -472,7 +388,7 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   SplitSlot& sl = c->slot(b, j);
   const int n = (int)sl.items();
   if (n == 0) return DM_OK;
-  Part pt{sl, BinItems{lb, c->bins[b].p + sl.lo[0], n}, j == 0 ? cls_stream(b) : c->aux[c->part_stream(b, j)], p,
+  Part pt{sl, BinItems{lb, c->bins[b].p + sl.lo[0], n}, j == 0 ? cls_stream(b) : c->order.aux[c->part_stream(b, j)], p,
           nullptr};
   if (nparts > 1 && p.pub) {  // the part's own flags word (DevParams::pub_word)
     pt.p.pub_word = j;
@@ -480,9 +396,9 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   }
   // the tick's last kernel of this part (the dense kernel, or the rest kernel after
   // it) completes the part's tick event when another queue waits for the tick
-  if (one_class && c->tick_signal_wanted) {
-    pt.done = c->tick_ev[j][c->tick_seq % dm_ctx::kTickEv];
-    c->tick_part_mask |= fork ? 1u << (j == 0 ? c->class_stream[b] : c->part_stream(b, j)) : 0u;
+  if (c->done.sig.carries(one_class)) {
+    pt.done = c->done.event(j);
+    c->done.sig.add_part(fork ? 1u << c->part_stream(b, j) : 0u);
   }
   // what the host knows of the part and of the tick -> the form of the part's launches
   FormInputs in;
@@ -552,10 +468,7 @@ int Tick::launch_rest(Part& pt, const PartForm& f) {
 }
 
 int Tick::launch_mixed(Part& pt) {
-  if (pt.done) {  // (a tick in the one-kernel form carries no event: consumers join instead)
-    c->tick_flagged = false;
-    c->tick_part_mask = 0;
-  }
+  if (pt.done) c->done.sig.unflag();  // (a tick in the one-kernel form carries no event: consumers join instead)
   DM_HIP(c, timed(KC_BIN0 + pt.sl.b, pt.s, [&] { return launch_bin(pt.w, pt.p, gl, gc, pt.s); }), "group kernel");
   return DM_OK;
 }
@@ -569,11 +482,7 @@ int Tick::bins() {
                    : (b == 4 && c->bin4_wave) ? kBin4Wave
                                               : b;  // the launchers' bin (shape)
     const int nparts = c->bin_parts[b];
-    if (one_class && c->tick_signal_wanted) {
-      c->tick_flagged = true;
-      c->tick_nev[c->tick_seq % dm_ctx::kTickEv] = nparts;
-      c->tick_part_mask = 0;
-    }
+    c->done.sig.flag(one_class, nparts);
     for (int j = 0; j < nparts; ++j)
       if (int rc = bin_part(b, lb, nparts, j)) return rc;
   }
@@ -585,15 +494,15 @@ int Tick::finish() {
     DM_HIP(c, timed(KC_SMALL, s_small, [&] { return launch_tile_small(p, c->tiles.p, c->tile_list.p, (int)c->h_tiles.size(), s_small); }),
            "small kernel");
   if (fork) {
-    c->aux_pending = true;
+    c->order.forked();
     // k_general consumes every class's worklist appends on the context stream
     const bool defer = (flags & DM_ASYNC) && (flags & DM_DEFER_JOIN) && !general;
-    if (!defer) DM_HIP(c, c->join_aux(), "join");
+    if (!defer) DM_HIP(c, c->order.join(), "join");
   }
   if (general) {
     const int blocks = (int)std::min<int64_t>(c->n_nonsmall, 1024);
     DM_HIP(c, timed(KC_GENERAL, st, [&] { return launch_general(p, gl, gc, blocks, st); }), "general kernel");
-    c->main_dirty = true;
+    c->order.main_has_work();
   }
   if (pingpong) std::swap(c->has, c->out_gets);  // the written column becomes the store's (stream order)
   c->last_writeback = wb;
@@ -615,10 +524,9 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   DM_CHECK_CTX(c);
   int rc = ready(c);
   if (rc) return rc;
-  if (c->tpl_pipe && (rc = commit_templates(c))) return rc;
-  c->ticks_issued += 1;
-  c->tick_seq += 1;
-  c->tick_flagged = false;
+  if (c->tpl.on && (rc = commit_templates(c))) return rc;
+  c->tpl.q.tick();
+  c->done.sig.begin();
   Tick t{c, now_ns, flags};
   if ((rc = t.outputs()) || (rc = t.streams()) || (rc = t.large_chain()) || (rc = t.subs()) ||
       (rc = t.bins()))
