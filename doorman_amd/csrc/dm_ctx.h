@@ -24,6 +24,7 @@
 #include "../../include/doorman_hip.h"
 #include "dm_device.h"
 #include "dm_launch.h"
+#include "dm_row_epoch.h"
 #include "dm_split_form.h"
 #include "dm_tick_order.h"
 
@@ -202,7 +203,7 @@ struct SplitSlot {
   // it queue an item on a tick whose rest kernel was skipped (dm_ctx::check_device)
   Mapped<uint64_t> rec;
   Mapped<int32_t> guard;
-  uint64_t ver_epoch = 0;
+  uint64_t ver_epoch = 0, ver_write = 0;  // the row and write epochs of the last check (check_dense)
   // The row epoch in which the part's last tick launched the FIXED build, which keeps a
   // key per item (0: it did not): keys are trusted only while this is the current epoch.
   // bin_part assigns it from choose_form's result (PartForm::fix_live has the rule and
@@ -457,11 +458,31 @@ struct dm_ctx {
   // writeback tick leaves every dense workgroup-bin resource dense (dm_tick_group.hip),
   // so a bin verified all-dense once in the epoch (k_count_undense) can skip its
   // k_block_rest: nothing can be queued.
-  uint64_t row_epoch = 1;
+  // One writer may leave it alone: a wants refresh under dm_keep_keys (dm_row_epoch.h has
+  // the rule and why it is safe), which ends as refresh_kept().  write_epoch moves with
+  // every write, kept or not: what the large chain's light redo asks (redo_epoch).
+  uint64_t row_epoch = 1, write_epoch = 1;
   void rows_changed() {
     chain_live_ok = false;
     row_epoch += 1;
+    write_epoch += 1;
     for (SplitSlot& s : split) s.fix_live = 0;  // no fixed-point key is trusted across a write (SplitSlot)
+  }
+  // dm_keep_keys.  kept_refreshes: dm_plan_info slot 23.  kept_rows: values the kept
+  // refreshes carried since the last tick, each of which may have cleared a key: the next
+  // sweep's row kernel is sized for them (FormInputs::refreshed).
+  bool keep_keys = false;
+  int64_t kept_refreshes = 0, kept_rows = 0;
+  void refresh_kept(int64_t n) {
+    chain_live_ok = false;
+    write_epoch += 1;
+    kept_refreshes += 1;
+    kept_rows += n;
+  }
+  bool keys_in_use() const {
+    for (const SplitSlot& s : split)
+      if (s.fix_live == row_epoch) return true;
+    return false;
   }
   std::vector<int64_t> h_seg_off;
   std::vector<int64_t> h_refresh_s;
@@ -549,6 +570,13 @@ struct dm_ctx {
   int fixed_ok = 1;
   DBuf<FixKey> fix_keys[kSplitBins];
   DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
+  // the key-clearing refresh kernels' view of the keys (dm_device.h KeyClear)
+  KeyClear key_clear() const {
+    KeyClear k{};
+    k.item_of = item_of.p;
+    for (int b = 0; b < kSplitBins; ++b) k.keys[b] = fix_keys[b].p;
+    return k;
+  }
   // Wherever a workgroup bin's items are uploaded, its fixed-point keys start invalid, and
   // no part of it has keys in use.
   hipError_t reset_keys(int b, hipStream_t st) {
@@ -606,7 +634,7 @@ struct dm_ctx {
   // k_large_redo's light build (dm_tick_large.hip) while the last redo the host saw found
   // nothing marked and no row changed since (DM_REDO_LIGHT: 0 never, 1 so, 2 always)
   int redo_light = 1;
-  uint64_t redo_epoch = 0;  // row_epoch at the last speculative tick
+  uint64_t redo_epoch = 0;  // write_epoch at the last speculative tick
   DBuf<int32_t> p_uni;
   // heterogeneous FairShare on the chain (allocated on the first tick that may need it)
   DBuf<uint32_t> ph_set;  // per large resource: distinct subclient counts (all ones between ticks)

@@ -446,6 +446,13 @@ struct DenseUpd {
   int32_t bin4_wave, bin6_wide;
   uint8_t* rmask;
 };
+// What the key-clearing builds of the wants-refresh kernels need (dm_update.hip): each
+// resource's item, whose index is its key's, and the four workgroup bins' key arrays
+// (parallel to DenseUpd::bins; null for a bin whose keys were never allocated).
+struct KeyClear {
+  const int32_t* item_of;
+  FixKey* keys[4];
+};
 __host__ __device__ inline void bin_shape(int bin, int bin4_wave, int bin6_wide, int* G, int* R) {
   *G = bin == 3 ? 128 : bin == 4 ? (bin4_wave ? 64 : 128) : bin == 5 ? 256 : (bin6_wide ? 512 : 256);
   *R = bin == 3 ? 4 : bin == 4 ? (bin4_wave ? 16 : 8) : bin == 5 ? 8 : (bin6_wide ? 8 : 16);

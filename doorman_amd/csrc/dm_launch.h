@@ -69,13 +69,16 @@ hipError_t launch_resolve_rows(int64_t n, const int64_t* rows, int64_t off, cons
                                hipStream_t st);
 hipError_t launch_gather_leases(int64_t n, const int64_t* rows, const double* gets, const int64_t* expiry,
                                double* out_gets, int64_t* out_exp, hipStream_t st);
+// kc (both refresh launchers): null launches the plain kernel; else its key-clearing build
+// (dm_row_epoch.h row_write_start says when)
 hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
                                const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
-                               hipStream_t st);
+                               const KeyClear* kc, hipStream_t st);
 hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
                                     int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
                                     const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
-                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi);
+                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi,
+                                    const KeyClear* kc = nullptr);
 hipError_t launch_carry_reject(const uint32_t* from, uint32_t* to, hipStream_t st);
 // dm_hier.hip
 hipError_t launch_publish(int64_t R, const ResAgg* agg, void* dst, uint32_t* sync, hipStream_t st);

@@ -1,0 +1,72 @@
+// dm_row_epoch.h — which calls that write rows start a row epoch (dm_ctx::rows_changed),
+// and which update-kernel build a wants refresh launches.  Plain C++17, no HIP: the rule is
+// tested on the CPU (tests/test_row_epoch.py).
+//
+// Two counters (dm_ctx.h): the write epoch moves with every call that writes a row, the row
+// epoch only with rows_changed().  Within one row epoch the fixed-point keys of a part stay
+// in use, its density verification stays valid and a large store's writeback ticks stay in
+// place (dm_split_form.h, dm_tick.cpp Tick::outputs); the write epoch is what the large
+// chain's light redo asks (no row written since the last speculative tick).
+//
+// Every writer ends as rows_changed() except one: with dm_keep_keys on, a wants refresh
+// (dm_store_update_wants, dm_store_update_wants_mask) that was neither rejected nor carried
+// a NaN is *kept*.  Such a refresh writes wants and adds to sum_wants, nothing else: no
+// subclients word, expiry, state byte, mask or work item.  So
+//   - no dense resource stops being dense, and none gains a released row or an arrival: the
+//     part's density record (SplitSlot::rec) says what it said, and a dense kernel that ran
+//     alone (PartForm::skip_rest, the form of a bin in stream parts) still cannot queue an
+//     item -- the guard stays for the impossible;
+//   - a resource's key is wrong only where a row's wants bits moved, and there the refresh
+//     kernel's key-clearing build has stored an invalid key (dm_update.hip), which the sweep
+//     and the FIXED builds read as "load the rows".
+// A NaN wants can end a resource's dense state (FairShare then needs k_general), so such a
+// call starts an epoch as it always did; so does a rejected one, which wrote nothing, and
+// every call the refresh's flags are not read in (the batches: the asynchronous one learns
+// of a NaN two batches later).
+#pragma once
+#include <cstdint>
+
+namespace dm {
+
+enum class RowWrite {
+  refresh,       // dm_store_update_wants
+  refresh_mask,  // dm_store_update_wants_mask
+  load,          // dm_store_load
+  plan,          // a new plan (upload_plan)
+  upsert,
+  release,
+  apply,         // dm_store_apply
+  apply_async,   // dm_store_apply_async
+  decide,
+  clean,
+  relayout,
+  config_load,
+  root_tick,     // dm_hier_root_tick
+};
+
+constexpr bool is_refresh(RowWrite w) { return w == RowWrite::refresh || w == RowWrite::refresh_mask; }
+
+// Before the launch.  defer: the call decides how it ends once its flags are back
+// (row_write_end); otherwise it calls rows_changed() at once, as every writer did.
+// clear_keys: launch the key-clearing build of the refresh kernel.  Only where keys are in
+// use (some part's fix_live is the row epoch): keys out of use are rewritten by the next
+// FIXED launch before any is read, so every other launch runs the plain kernels.
+struct RowWriteStart {
+  bool defer = false;
+  bool clear_keys = false;
+};
+inline RowWriteStart row_write_start(RowWrite w, bool keep_keys, bool keys_in_use) {
+  RowWriteStart s;
+  s.defer = keep_keys && is_refresh(w);
+  s.clear_keys = s.defer && keys_in_use;
+  return s;
+}
+
+// After the flags are back.  rejected: the call failed or its validation refused it (the
+// apply kernel did not run); nan: kUpdNaN.  true: a kept refresh (dm_ctx::refresh_kept);
+// false: rows_changed().
+inline bool row_write_kept(RowWrite w, bool keep_keys, bool rejected, bool nan) {
+  return keep_keys && is_refresh(w) && !rejected && !nan;
+}
+
+}  // namespace dm

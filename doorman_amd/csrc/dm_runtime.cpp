@@ -288,6 +288,12 @@ int dm_set_profiling(dm_ctx* c, int on) {
   return DM_OK;
 }
 
+int dm_keep_keys(dm_ctx* c, int on) {
+  DM_CHECK_CTX(c);
+  c->keep_keys = on != 0;
+  return DM_OK;
+}
+
 int dm_kernel_class_names(const char** names, int max) {
   if (!names && max > 0) return DM_E_INVAL;
   for (int i = 0; i < KC_COUNT && i < max; ++i) names[i] = kClassNames[i];
@@ -319,7 +325,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[14 + kNumBins];
+  int64_t v[15 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -344,7 +350,8 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
     v[12 + kNumBins] += s.last.use_keys;  // ... and ran it with the fixed-point keys in use
     v[13 + kNumBins] += s.last.sweep;     // ... as the sweep and the row kernel over its worklist
   }
-  const int n = 14 + kNumBins;
+  v[14 + kNumBins] = c->kept_refreshes;  // wants refreshes kept under dm_keep_keys since dm_create
+  const int n = 15 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

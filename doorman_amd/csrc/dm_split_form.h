@@ -75,6 +75,7 @@ struct FormInputs {
   uint64_t fix_live = 0;     // the part's, before this tick
   uint64_t sw_epoch = 0;     // the sweep record: the epoch of the count the device last told ...
   int64_t sw_told = 0;       // ... and the count
+  int64_t refreshed = 0;     // values of kept wants refreshes since the last tick: each may have cleared a key
   int n = 0;                 // the part's items
   int64_t queued = 0;        // items the last split tick the host has heard of queued
 };
@@ -106,11 +107,12 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   // Grids are hints: both kernels stride over their lists, so correctness never depends
   // on them.  The rest kernel's is sized from the last split tick's queue (an empty queue
   // costs 16 workgroups that read one count); the row kernel's from the count the device
-  // last told in this row epoch, plus an eighth and 64 (the part's items until then).
+  // last told in this row epoch (and the keys that kept refreshes may have cleared since),
+  // plus an eighth and 64 (the part's items until then).
   f.rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, in.queued));
   f.list_grid = in.n;
   if (in.sw_epoch == in.row_epoch) {
-    const int64_t told = in.sw_told;
+    const int64_t told = in.sw_told + in.refreshed;
     f.list_grid = (int)std::min<int64_t>(in.n, std::max<int64_t>(16, told + told / 8 + (told ? 64 : 0)));
   }
   return f;

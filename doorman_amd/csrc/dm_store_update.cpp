@@ -103,24 +103,53 @@ int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has
   return DM_OK;
 }
 
+// How a wants refresh ends (dm_row_epoch.h): with dm_keep_keys off it starts a row epoch
+// before it launches, as every writer does; with it on, once its flags are back -- a kept
+// refresh, or rows_changed() on every other way out of the call (a rejection, a NaN, a
+// failure on the way).
+namespace {
+struct RefreshEnd {
+  dm_ctx* c;
+  RowWrite w;
+  RowWriteStart start;
+  KeyClear kc;
+  bool ended = false;
+  RefreshEnd(dm_ctx* ctx, RowWrite kind)
+      : c(ctx), w(kind), start(row_write_start(kind, ctx->keep_keys, ctx->keys_in_use())), kc(ctx->key_clear()) {
+    if (!start.defer) end(true, false, 0);
+  }
+  ~RefreshEnd() { end(true, false, 0); }
+  const KeyClear* keys() const { return start.clear_keys ? &kc : nullptr; }  // the launchers' build
+  void end(bool rejected, bool nan, int64_t n) {
+    if (ended) return;
+    ended = true;
+    if (row_write_kept(w, c->keep_keys, rejected, nan))
+      c->refresh_kept(n);
+    else
+      c->rows_changed();
+  }
+};
+}  // namespace
+
 int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
   DM_ENTER(c);
   DM_STORE_OK(c);
   if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   if (n < 0 || (n > 0 && (!rows || !wants))) return c->fail(DM_E_INVAL, "bad update");
   if (n == 0) return DM_OK;
-  c->rows_changed();  // a NaN wants ends a resource's dense state
+  RefreshEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
   DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
   DM_HIP(c, c->st_wants.ensure((size_t)n), "stage wants");
   const StageCol cols[] = {{c->st_rows.p, rows, 8}, {c->st_wants.p, wants, 8}};
   int rc = staged_check(c, n, cols, 2, true, false);
   if (rc) return rc;
   DM_HIP(c, launch_update_wants(n, c->st_rows.p, c->st_wants.p, c->row_index(), c->sub.p, c->wants.p, c->agg.p,
-                                c->upd_flags.p, c->stream),
+                                c->upd_flags.p, re.keys(), c->stream),
          "update wants");
   uint32_t f = 0;
   rc = finish_update(c, n, &f);
   if (rc) return rc;
+  re.end(false, f & kUpdNaN, n);
   if (f & kUpdNaN) c->maybe_general = true;
   c->have_result = false;
   return DM_OK;
@@ -138,7 +167,7 @@ int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, con
     return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
   if (nwords == 0) return n == 0 ? DM_OK : c->fail(DM_E_INVAL, "packed values without a mask");
   if (first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
-  c->rows_changed();  // a NaN wants ends a resource's dense state
+  RefreshEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
   const int64_t nb = (nwords + 255) / 256;
   DM_HIP(c, c->st_mask.ensure((size_t)nwords), "stage mask");
   DM_HIP(c, c->st_wants.ensure((size_t)std::max<int64_t>(n, 1)), "stage wants");
@@ -153,7 +182,7 @@ int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, con
   DM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_stage[0], 0), "stage update");
   DM_HIP(c, launch_update_wants_mask(nwords, c->st_mask.p, first_row, c->N, n, c->st_wants.p, c->st_blk.p,
                                      c->st_wpre.p, c->row_index(), c->sub.p, c->wants.p, c->agg.p, c->upd_flags.p,
-                                     c->stream, 2, 0, INT64_MAX),
+                                     c->stream, 2, 0, INT64_MAX, re.keys()),
          "masked update");
   DM_HIP(c, hipMemcpyAsync(c->h_flags.p, c->upd_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream),
          "update flags");
@@ -161,6 +190,7 @@ int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, con
   const uint32_t f = *c->h_flags.p;
   if (f & kUpdRange) return c->fail(DM_E_RANGE, "mask bit past the store's end");
   if (f & kUpdCount) return c->fail(DM_E_INVAL, "packed values must match the mask's set bits");
+  re.end(false, f & kUpdNaN, n);
   if (f & kUpdNaN) c->maybe_general = true;
   c->have_result = false;
   return DM_OK;

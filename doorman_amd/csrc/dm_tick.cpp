@@ -125,8 +125,17 @@ static hipError_t calib_step(dm_ctx* c) {
 // count of 0 lets the following ticks of the epoch skip the part's k_block_rest.
 static hipError_t check_dense(dm_ctx* c, SplitSlot& sl, hipStream_t s) {
   const int64_t n = sl.items();
-  if (sl.ver_epoch == c->row_epoch || n <= 0) return hipSuccess;
+  // Again within the epoch after a kept wants refresh (dm_row_epoch.h) when the epoch's count
+  // found items that are not dense: the refresh may have repaired the NaN that ended a
+  // resource's dense state, and nothing else would count the part again before the next epoch
+  // (tests/test_keep_keys_gpu.py::test_nan_and_rejection: the keys come back after the repair).
+  bool again = false;
+  if (sl.ver_epoch == c->row_epoch && sl.ver_write != c->write_epoch)
+    again = __atomic_load_n(sl.rec.h + 1, __ATOMIC_ACQUIRE) == c->row_epoch &&
+            (uint32_t)__atomic_load_n(sl.rec.h, __ATOMIC_RELAXED) != 0;
+  if ((sl.ver_epoch == c->row_epoch && !again) || n <= 0) return hipSuccess;
   sl.ver_epoch = c->row_epoch;
+  sl.ver_write = c->write_epoch;
   return launch_count_undense(c->bins[sl.b].p + sl.lo[0], (int)n, (unsigned long long*)sl.rec.d,
                               (unsigned long long)c->row_epoch, s);
 }
@@ -340,9 +349,9 @@ int Tick::large_chain() {
     const SpecArgs S{c->p_spec.p, c->spec_seq, c->h_serr.d, c->p_spec_ring.p, (int)(c->spec_seq & 1), nch,
                      reinterpret_cast<uint32_t*>(c->h_serr.d + 1), c->p_team.p, c->nslots};
     c->spec_seq += 1;
-    const bool light = c->redo_light == 2 || (c->redo_light == 1 && c->redo_epoch == c->row_epoch &&
+    const bool light = c->redo_light == 2 || (c->redo_light == 1 && c->redo_epoch == c->write_epoch &&
                                               __atomic_exchange_n(c->h_serr.p + 1, 0, __ATOMIC_RELAXED) == 0);
-    c->redo_epoch = c->row_epoch;
+    c->redo_epoch = c->write_epoch;
     const int redo_phase = light ? 2 : 1;
     const int redo_grid = light ? c->team_grid_light : c->team_grid_full;
     for (int ph = 0; ph < 2; ++ph)
@@ -413,6 +422,7 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   in.writeback = wb;
   in.inplace = pt.p.out_gets == pt.p.has;
   in.fix_live = sl.fix_live;
+  in.refreshed = c->kept_rows;
   in.n = n;
   const bool may_split = in.hints && in.dense_split;
   if (may_split) in.queued = sl.read_queued();
@@ -486,6 +496,7 @@ int Tick::bins() {
     for (int j = 0; j < nparts; ++j)
       if (int rc = bin_part(b, lb, nparts, j)) return rc;
   }
+  c->kept_rows = 0;  // (every part's sweep is sized: FormInputs::refreshed)
   return DM_OK;
 }
 

@@ -124,23 +124,36 @@ __global__ void k_release(int64_t n, const int64_t* __restrict__ rows, RowIndex 
 // A released row is a free slot, not a client: a refresh of it changes nothing (a
 // returning client is an arrival, dm_store_upsert).  Written into it, the wants would
 // be subtracted from the resource's running sum by every later tick's Clean.
+//
+// Two builds of one body each (dm_update_wants.inc, dm_mask_apply.inc: the including
+// kernel sets kKeys).  The plain one is every launch's unless dm_keep_keys is on and some
+// part has fixed-point keys in use (dm_row_epoch.h); then the key-clearing build
+// (k_update_wants_keys, k_mask_apply_keys) also stores an invalid key for every
+// workgroup-bin resource in which a row changed.
+// A row is changed when it is not released and its new wants differ from the stored wants
+// as 64-bit patterns: -0.0 against +0.0 is a change, a client re-sending its stored value
+// is none (its delta is x - x = +0.0, which leaves the bits of every sum but -0.0, and the
+// sweep's write_fixed writes the sums it read either way, as the full path would).  The
+// stores to the wants column and the atomics on sum_wants are the plain build's.
+// Order: the key stores are on the context stream behind the call's wants stores.  The
+// call entered through DM_ENTER (dm_ctx.h), which joined every class stream's tick work
+// into the context stream (StreamOrder::join), so they follow the last tick's own key
+// stores; and it marked the context stream as holding work (main_has_work), so the next
+// tick's StreamOrder::fork makes every class stream wait for them, exactly as for the
+// wants its row loads need (a tick on the context stream alone is behind them anyway).
 __global__ void k_update_wants(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ wants,
                                RowIndex ix, const int32_t* __restrict__ s_sub, double* s_wants, ResAgg* agg,
                                const uint32_t* flags) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (*flags & kUpdReject) return;  // uniform over the grid
-  const bool active = i < n;
-  int seg = 0;
-  double d = 0.0;
-  if (active) {
-    const int64_t r = rows[i];
-    seg = seg_of_row(ix, r);
-    if (!sub_released(s_sub[r])) {
-      d = wants[i] - s_wants[r];
-      s_wants[r] = wants[i];
-    }
-  }
-  wave_seg_add(agg, active, seg, 0.0, d, 0, false, false);
+  constexpr bool kKeys = false;
+  const KeyClear kc{};
+#include "dm_update_wants.inc"
+}
+
+__global__ void k_update_wants_keys(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ wants,
+                                    RowIndex ix, const int32_t* __restrict__ s_sub, double* s_wants, ResAgg* agg,
+                                    const uint32_t* flags, KeyClear kc) {
+  constexpr bool kKeys = true;
+#include "dm_update_wants.inc"
 }
 
 // ---- wants updates as a row mask + packed values (dm_store_update_wants_mask) ----
@@ -215,6 +228,11 @@ __global__ __launch_bounds__(1024) void k_mask_scan(int64_t nblocks, int64_t* bl
 // per-lane registers while consecutive words lie inside it and leave with one
 // reduction + atomic when the resource changes; a word that spans resources adds
 // its runs directly (wave_seg_add).
+// The key-clearing build (k_update_wants has the rule; the body: dm_mask_apply.inc) keeps
+// "a row of this lane's changed" beside `acc` and clears a resource's key where its deltas
+// are flushed, by the lane that adds them, when some lane's did; a word that spans
+// resources clears per run (wave_seg_add<true>).  The compare sits inside the branch that
+// holds the row's values: 94 VGPRs against the plain build's 88, no scratch.
 constexpr int kMaskWords = 16;
 __global__ __launch_bounds__(256) void k_mask_apply(int64_t nwords, const uint64_t* __restrict__ mask,
                                                     int64_t first_row, const int64_t* __restrict__ block_offs,
@@ -222,93 +240,20 @@ __global__ __launch_bounds__(256) void k_mask_apply(int64_t nwords, const uint64
                                                     const double* __restrict__ wants, RowIndex ix,
                                                     const int32_t* __restrict__ s_sub, double* s_wants, ResAgg* agg,
                                                     uint32_t* flags, int64_t vlo, int64_t vhi) {
-  if (*flags & kUpdReject) return;  // uniform over the grid
-  const int lane = threadIdx.x & 63;
-  const int64_t w0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kMaskWords;
-  if (w0 >= nwords) return;  // whole waves
-  const int nw = nwords - w0 < kMaskWords ? (int)(nwords - w0) : kMaskWords;
-  uint64_t my_m = 0ull;
-  int64_t my_off = 0, my_end = 0;
-  if (lane < nw) {
-    const int64_t w = w0 + lane;
-    my_m = mask[w];
-    my_off = block_offs[w >> 8] + word_pre[w];
-  }
-  // only the values [vlo, vhi) have landed (dm_store_apply copies them in chunks): a
-  // wave whose words' values all lie outside is done
-  {
-    const int64_t first = readlane_any(my_off, 0);
-    const int64_t last = readlane_any(my_off, nw - 1) + __popcll(readlane_any(my_m, nw - 1));  // one past
-    if (last <= vlo || first >= vhi) return;
-  }
-  int my_seg = 0;
-  if (lane < nw) {
-    my_seg = seg_of_row(ix, first_row + 64 * (w0 + lane));
-    my_end = ix.seg_off[my_seg + 1];  // the word lies in one resource iff its last row < my_end
-  }
-  const uint64_t below = (1ull << lane) - 1ull;
-  uint32_t inr = 0;  // bit q: this lane's row of word q is set and its value in [vlo, vhi)
-  double v[kMaskWords], old[kMaskWords];
-  uint32_t freed = 0;  // bit q: this lane's row of word q is released (k_update_wants: left alone)
-#pragma unroll
-  for (int q = 0; q < kMaskWords; ++q) {  // every load in flight before the first use
-    v[q] = 0.0;
-    old[q] = 0.0;
-    if (q < nw) {
-      const uint64_t m = readlane_any(my_m, q);
-      const int64_t vi = readlane_any(my_off, q) + __popcll(m & below);
-      if (((m >> lane) & 1ull) && vi >= vlo && vi < vhi) {
-        inr |= 1u << q;
-        v[q] = wants[vi];
-        old[q] = s_wants[first_row + 64 * (w0 + q) + lane];
-        freed |= (sub_released(s_sub[first_row + 64 * (w0 + q) + lane]) ? 1u : 0u) << q;
-      }
-    }
-  }
-  int cur = -1;      // resource whose deltas `acc` holds (uniform)
-  double acc = 0.0;  // this lane's share of them
-  bool nan = false;
-#pragma unroll
-  for (int q = 0; q < kMaskWords; ++q) {
-    const uint64_t m = q < nw ? readlane_any(my_m, q) : 0ull;
-    if (m != 0ull) {  // uniform
-      const int64_t row0 = first_row + 64 * (w0 + q);
-      const bool act = (inr >> q & 1u) && !(freed >> q & 1u);
-      const int s0 = __builtin_amdgcn_readlane(my_seg, q);
-      const bool single = readlane_any(my_end, q) > row0 + 63 - __builtin_clzll(m);
-      double d = 0.0;
-      int seg = s0;
-      if (act) {
-        const int64_t r = row0 + lane;
-        nan |= __builtin_isnan(v[q]);
-        if (!single)
-          while (ix.seg_off[seg + 1] <= r) ++seg;
-        d = v[q] - old[q];
-        s_wants[r] = v[q];
-      }
-      if (single && s0 == cur) {
-        acc += d;
-      } else {
-        if (cur >= 0) {  // flush the previous resource
-          const double t = wave_reduce(acc, [](double a, double b) { return a + b; });
-          if (lane == 0) atomicAdd(&agg[cur].sum_wants, t);
-        }
-        if (single) {
-          cur = s0;
-          acc = d;
-        } else {
-          cur = -1;
-          acc = 0.0;
-          wave_seg_add(agg, act, seg, 0.0, d, 0, false, false);
-        }
-      }
-    }
-  }
-  if (cur >= 0) {
-    const double t = wave_reduce(acc, [](double a, double b) { return a + b; });
-    if (lane == 0) atomicAdd(&agg[cur].sum_wants, t);
-  }
-  if (__ballot(nan) && lane == 0) atomicOr(flags, kUpdNaN);
+  constexpr bool kKeys = false;
+  const KeyClear kc{};
+#include "dm_mask_apply.inc"
+}
+
+__global__ __launch_bounds__(256) void k_mask_apply_keys(int64_t nwords, const uint64_t* __restrict__ mask,
+                                                         int64_t first_row, const int64_t* __restrict__ block_offs,
+                                                         const int32_t* __restrict__ word_pre,
+                                                         const double* __restrict__ wants, RowIndex ix,
+                                                         const int32_t* __restrict__ s_sub, double* s_wants,
+                                                         ResAgg* agg, uint32_t* flags, int64_t vlo, int64_t vhi,
+                                                         KeyClear kc) {
+  constexpr bool kKeys = true;
+#include "dm_mask_apply.inc"
 }
 
 // dm_store_apply: a part is applied only if no earlier part was rejected.
@@ -369,9 +314,13 @@ hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, do
 
 hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
                                const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
-                               hipStream_t st) {
+                               const KeyClear* kc, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  k_update_wants<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, wants, ix, s_sub, s_wants, agg, flags);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (kc)
+    k_update_wants_keys<<<grid, 256, 0, st>>>(n, rows, wants, ix, s_sub, s_wants, agg, flags, *kc);
+  else
+    k_update_wants<<<grid, 256, 0, st>>>(n, rows, wants, ix, s_sub, s_wants, agg, flags);
   return hipGetLastError();
 }
 
@@ -406,7 +355,8 @@ hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t
 hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
                                     int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
                                     const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
-                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi) {
+                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi,
+                                    const KeyClear* kc) {
   if (nwords <= 0) return hipSuccess;
   const int64_t nb = (nwords + 255) / 256;
   if (phase != 1) {  // the mask's counts and value offsets (the mask alone)
@@ -415,8 +365,13 @@ hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_
   }
   if (phase != 0) {  // the rows whose values [vlo, vhi) have landed
     const int64_t waves = (nwords + kMaskWords - 1) / kMaskWords;
-    k_mask_apply<<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, ix,
-                                                              s_sub, s_wants, agg, flags, vlo, vhi);
+    const unsigned grid = (unsigned)((waves + 3) / 4);
+    if (kc)
+      k_mask_apply_keys<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, ix, s_sub, s_wants,
+                                              agg, flags, vlo, vhi, *kc);
+    else
+      k_mask_apply<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, ix, s_sub, s_wants, agg,
+                                         flags, vlo, vhi);
   }
   return hipGetLastError();
 }

@@ -26,20 +26,50 @@ __device__ __forceinline__ int seg_of_row(const RowIndex& ix, int64_t r) {
   return (int)lo;
 }
 
+// The key-clearing builds of the wants-refresh kernels (dm_update.hip, dm_device.h
+// KeyClear): resource seg's fixed-point key, if it has one, becomes invalid.  A plain
+// vector store of zeros: keys are cleared only by stores of this one value, so any number
+// of waves may clear the same key.  (The bin's array by selects, not by an index into the
+// kernel argument, which would put the four pointers into scratch.)
+__device__ __forceinline__ void clear_key(const KeyClear& kc, int seg) {
+  const int32_t io = kc.item_of[seg];
+  if (io < 0) return;
+  const int bin = io >> 24;
+  FixKey* k = bin == 3 ? kc.keys[0] : bin == 4 ? kc.keys[1] : bin == 5 ? kc.keys[2] : kc.keys[3];
+  if (k) k[io & 0xFFFFFF] = FixKey{0, 0, 0};
+}
+
 // Add per-row deltas to their resources' running sums: lanes of a wave that hit
 // the same resource are summed first (DPP) and add once; a wave whose rows spread
 // over many resources adds per lane.  Every lane of the wave must call this.
+// KEYS (the key-clearing builds): `changed` says that the lane's row changed its wants
+// bits; the lane that adds for a run of a resource also clears the resource's key when some
+// lane of the run changed -- one store per run at most, on the spread-out path too, where
+// the run is the consecutive active lanes of one resource behind a head.
+template <bool KEYS = false>
 __device__ __forceinline__ void wave_seg_add(ResAgg* agg, bool active, int seg, double dh, double dw, long long ds,
-                                             bool with_has, bool with_count) {
+                                             bool with_has, bool with_count, bool changed = false,
+                                             const KeyClear& kc = KeyClear{}) {
   const int lane = threadIdx.x & 63;
   const unsigned long long act = __ballot(active);
   const int prev = __shfl(seg, lane > 0 ? lane - 1 : 0, 64);
   const bool head = active && (lane == 0 || !((act >> (lane - 1)) & 1) || prev != seg);
-  if (__popcll(__ballot(head)) > 8) {
+  const unsigned long long heads = __ballot(head);
+  unsigned long long chg = 0ull;
+  if constexpr (KEYS) chg = __ballot(active && changed);
+  if (__popcll(heads) > 8) {
     if (active) {
       if (with_has) atomicAdd(&agg[seg].sum_has, dh);
       atomicAdd(&agg[seg].sum_wants, dw);
       if (with_count) atomicAdd((unsigned long long*)&agg[seg].count, (unsigned long long)ds);
+    }
+    if constexpr (KEYS) {
+      if (head) {  // the run: this lane up to the next head or inactive lane
+        const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
+        const unsigned long long stop = (heads | ~act) & above;
+        const unsigned long long upto = stop ? (1ull << __builtin_ctzll(stop)) - 1ull : ~0ull;
+        if (chg & upto & ~((1ull << lane) - 1ull)) clear_key(kc, seg);
+      }
     }
     return;
   }
@@ -55,6 +85,9 @@ __device__ __forceinline__ void wave_seg_add(ResAgg* agg, bool active, int seg, 
       if (with_has) atomicAdd(&agg[s0].sum_has, v.h);
       atomicAdd(&agg[s0].sum_wants, v.w);
       if (with_count) atomicAdd((unsigned long long*)&agg[s0].count, (unsigned long long)v.cnt);
+      if constexpr (KEYS) {
+        if (chg & m) clear_key(kc, s0);
+      }
     }
     rem &= ~m;
   }

@@ -18,7 +18,7 @@ from .workloads import CFG_FIELDS
 _BIN_NAMES = ("small_tiles", "sub16x4", "sub32x4", "wave64x4", "block128x4", "block128x8", "block256x8",
               "block2k4k", "sub8x2", "sub16x2", "large_resources", "large_chunks", "leases", "bin_shapes",
               "redo_resident_cap", "spec_fits", "aux_own_queues", "stream_parts", "queue_perm", "wb_inplace",
-              "steady_parts", "fixed_parts", "sweep_parts")
+              "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes")
 
 
 def _ptr(a):
@@ -329,6 +329,11 @@ class Engine:
     # -- profiling --
     def set_profiling(self, on: bool):
         self._chk(self._L.dm_set_profiling(self._ctx, 1 if on else 0))
+
+    def keep_keys(self, on: bool):
+        """dm_keep_keys: a wants refresh without NaN keeps the fixed-point keys of every resource
+        in which it changed no row's wants bits (off by default)."""
+        self._chk(self._L.dm_keep_keys(self._ctx, 1 if on else 0))
 
     def kernel_times(self) -> dict:
         cap = 64

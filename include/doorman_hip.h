@@ -57,7 +57,9 @@ extern "C" {
    the number of those parts whose last tick ran as the sweep (one lane per item finishes
    the items whose key holds and lists the others; the dense kernel runs over the list;
    DM_SWEEP=0 in the environment, read when the context is created, keeps the dense
-   kernel over every item), and the call returns 23;
+   kernel over every item), and the call returns 23; dm_keep_keys (a wants refresh keeps
+   the fixed-point keys of the resources it did not change), with slot 23, the refreshes
+   the context kept, and the call returns 24;
    dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
    are in use, and returns 5 (a caller that passes max = 4 gets the four it got).  (Added
    slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
@@ -510,6 +512,17 @@ int dm_hier_comm_info(dm_ctx* root, int* nranks, int* rank);
 
 /* ---- profiling ---- */
 int dm_set_profiling(dm_ctx* ctx, int on);
+/* on != 0: a wants refresh (dm_store_update_wants, dm_store_update_wants_mask) that carries no
+   NaN and is not rejected no longer starts a row epoch.  It invalidates, on the device, the
+   fixed-point keys of exactly the workgroup-bin resources in which it changed a row's wants
+   bits (a released row changes nothing; -0.0 against +0.0 is a change; a client re-sending
+   its stored value is none); every other key stays in use, the density verification stays
+   valid, and the next writeback tick stays in place.  What any reader sees of the store, the
+   leases and the sums is unchanged bit for bit.  A refresh with a NaN, a rejected one and
+   every other writer (the batches of dm_store_apply / dm_store_apply_async included) end the
+   keys' use as they always did.  Default off.  Returns DM_OK, or DM_E_INVAL for a NULL
+   context. */
+int dm_keep_keys(dm_ctx* ctx, int on);
 /* fills up to max entries; returns the number of kernel classes (>= 0) */
 int dm_kernel_times(dm_ctx* ctx, dm_kernel_time* out, int max);
 /* the names dm_kernel_times reports, in its order (static strings; no context or GPU
@@ -531,7 +544,9 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * forked writeback ticks, -1 until then), and the column the store's last writeback tick
  * wrote (1: the has column, in place; 0: the alternate column; -1: none yet), and the
  * workgroup-bin parts whose last tick ran the dense kernel's steady builds, and those of
- * them that ran with the fixed-point keys in use; returns 22 */
+ * them that ran with the fixed-point keys in use, and those of them that ran as the sweep,
+ * and (slot 23) the wants refreshes the context kept under dm_keep_keys since it was
+ * created; returns 24 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
