@@ -204,6 +204,25 @@ struct SplitSlot {
   Mapped<uint64_t> rec;
   Mapped<int32_t> guard;
   uint64_t ver_epoch = 0, ver_write = 0;  // the row and write epochs of the last check (check_dense)
+  // A kept update (dm_keep_keys' DM_KEEP_UPDATES, dm_ctx::update_kept) withdraws the record:
+  // the host zeroes the record's epoch word and keeps the counts it held, with their row
+  // epoch (0: none), as an estimate for the forms that the rest launch follows
+  // (FormInputs::rec_kept); upd_rows: the rows kept updates wrote since that count; recount:
+  // the next writeback tick's check_dense counts again.
+  uint64_t kept_counts = 0, kept_epoch = 0;
+  int64_t upd_rows = 0;
+  bool recount = false;
+  void withdraw_record(uint64_t row_epoch, int64_t rows) {
+    if (!rec.h) return;
+    if (__atomic_load_n(rec.h + 1, __ATOMIC_ACQUIRE) == row_epoch) {
+      kept_counts = __atomic_load_n(rec.h, __ATOMIC_RELAXED);
+      kept_epoch = row_epoch;
+      upd_rows = 0;
+      __atomic_store_n(rec.h + 1, 0, __ATOMIC_RELEASE);
+    }
+    upd_rows += rows;
+    recount = true;
+  }
   // The row epoch in which the part's last tick launched the FIXED build, which keeps a
   // key per item (0: it did not): keys are trusted only while this is the current epoch.
   // bin_part assigns it from choose_form's result (PartForm::fix_live has the rule and
@@ -223,9 +242,18 @@ struct SplitSlot {
   // Only the words the choice can use are read, as ever: the queued count for a part that
   // may split, the records for one that tries to, the sweep's where keys may be in use.
   int64_t read_queued() const { return __atomic_load_n(queued.h, __ATOMIC_RELAXED); }
-  void read_records(FormInputs& in) const {
+  void read_records(FormInputs& in) {
     in.rec_epoch = __atomic_load_n(rec.h + 1, __ATOMIC_ACQUIRE);
     in.rec_counts = __atomic_load_n(rec.h, __ATOMIC_RELAXED);
+    if (in.rec_epoch == in.row_epoch) {  // a count taken after every kept update: the copy has served
+      kept_epoch = 0;
+      upd_rows = 0;
+    } else if (kept_epoch == in.row_epoch) {
+      in.rec_epoch = kept_epoch;
+      in.rec_counts = kept_counts;
+      in.rec_kept = true;
+      in.upd_rows = upd_rows;
+    }
     if (in.fix_live != in.row_epoch) return;
     in.sw_epoch = __atomic_load_n(sweep.h + 1, __ATOMIC_ACQUIRE);
     in.sw_told = (int64_t)__atomic_load_n(sweep.h, __ATOMIC_RELAXED);
@@ -458,8 +486,9 @@ struct dm_ctx {
   // writeback tick leaves every dense workgroup-bin resource dense (dm_tick_group.hip),
   // so a bin verified all-dense once in the epoch (k_count_undense) can skip its
   // k_block_rest: nothing can be queued.
-  // One writer may leave it alone: a wants refresh under dm_keep_keys (dm_row_epoch.h has
-  // the rule and why it is safe), which ends as refresh_kept().  write_epoch moves with
+  // Some writers may leave it alone under dm_keep_keys (dm_row_epoch.h has the rule and why
+  // it is safe): a wants refresh, which ends as refresh_kept(), and with DM_KEEP_UPDATES a
+  // release, an upsert or a synchronous batch, which end as update_kept().  write_epoch moves with
   // every write, kept or not: what the large chain's light redo asks (redo_epoch).
   uint64_t row_epoch = 1, write_epoch = 1;
   void rows_changed() {
@@ -471,13 +500,28 @@ struct dm_ctx {
   // dm_keep_keys.  kept_refreshes: dm_plan_info slot 23.  kept_rows: values the kept
   // refreshes carried since the last tick, each of which may have cleared a key: the next
   // sweep's row kernel is sized for them (FormInputs::refreshed).
-  bool keep_keys = false;
+  // keep_mode: the call's bit set (DM_KEEP_REFRESH, DM_KEEP_UPDATES).  A kept release, upsert
+  // or synchronous batch ends as update_kept(): a kept refresh's effects, its own counter
+  // (dm_keep_stats), and every part's density record withdrawn as a proof (SplitSlot::
+  // withdraw_record).  The call has waited for the context stream behind DM_ENTER's join of
+  // the class streams, so no count is in flight: a record enqueued before the update is never
+  // read as one taken after it.  kept_upd_rows: the rows of kept updates since the last tick.
+  int keep_mode = 0;
   int64_t kept_refreshes = 0, kept_rows = 0;
+  int64_t kept_releases = 0, kept_upserts = 0, kept_batches = 0, kept_upd_rows = 0;
   void refresh_kept(int64_t n) {
     chain_live_ok = false;
     write_epoch += 1;
     kept_refreshes += 1;
     kept_rows += n;
+  }
+  void update_kept(RowWrite w, int64_t n) {
+    chain_live_ok = false;
+    write_epoch += 1;
+    (w == RowWrite::release ? kept_releases : w == RowWrite::upsert ? kept_upserts : kept_batches) += 1;
+    kept_rows += n;
+    kept_upd_rows += n;
+    for (SplitSlot& s : split) s.withdraw_record(row_epoch, n);
   }
   bool keys_in_use() const {
     for (const SplitSlot& s : split)
@@ -570,7 +614,7 @@ struct dm_ctx {
   int fixed_ok = 1;
   DBuf<FixKey> fix_keys[kSplitBins];
   DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
-  // the key-clearing refresh kernels' view of the keys (dm_device.h KeyClear)
+  // the key-clearing refresh and update kernels' view of the keys (dm_device.h KeyClear)
   KeyClear key_clear() const {
     KeyClear k{};
     k.item_of = item_of.p;

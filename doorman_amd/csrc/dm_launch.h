@@ -57,10 +57,11 @@ hipError_t launch_general(const DevParams& p, const int32_t* glist, const int32_
 hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
                          const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
                          const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
-                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st);
+                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st,
+                         const KeyClear* kc = nullptr);
 hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
                           int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du,
-                          hipStream_t st);
+                          hipStream_t st, const KeyClear* kc = nullptr);
 hipError_t launch_check_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, const double* wants,
                              const int64_t* sub, const int32_t* sub32, uint32_t* flags, hipStream_t st);
 hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, hipStream_t st);
@@ -69,8 +70,8 @@ hipError_t launch_resolve_rows(int64_t n, const int64_t* rows, int64_t off, cons
                                hipStream_t st);
 hipError_t launch_gather_leases(int64_t n, const int64_t* rows, const double* gets, const int64_t* expiry,
                                double* out_gets, int64_t* out_exp, hipStream_t st);
-// kc (both refresh launchers): null launches the plain kernel; else its key-clearing build
-// (dm_row_epoch.h row_write_start says when)
+// kc (the upsert, release and refresh launchers): null launches the plain kernel; else its
+// key-clearing build (dm_row_epoch.h row_write_start_mode says when)
 hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
                                const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
                                const KeyClear* kc, hipStream_t st);

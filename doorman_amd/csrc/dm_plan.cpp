@@ -220,6 +220,9 @@ int dm::SplitSlot::reset(dm_ctx* c, hipStream_t st) {
   __atomic_store_n(rec.h + 1, (uint64_t)0, __ATOMIC_RELAXED);
   __atomic_store_n(guard.h, 0, __ATOMIC_RELAXED);
   ver_epoch = 0;
+  kept_epoch = 0;
+  upd_rows = 0;
+  recount = false;
   fix_live = 0;
   __atomic_store_n(queued.h, 0, __ATOMIC_RELAXED);
   skip = 0;

@@ -23,6 +23,24 @@
 // call starts an epoch as it always did; so does a rejected one, which wrote nothing, and
 // every call the refresh's flags are not read in (the batches: the asynchronous one learns
 // of a NaN two batches later).
+//
+// dm_keep_keys' argument is a bit set.  Any non-zero value keeps refreshes, as above
+// (kKeepRefresh is the value 1).  kKeepUpdates (2) also keeps dm_store_release,
+// dm_store_upsert and the synchronous dm_store_apply, when no part was rejected and none was
+// flagged NaN.  Such a call does write subclients words, state bytes, masks and work items,
+// and what makes that safe is on the device: every tick kernel that may trust a key or skip a
+// pass tests the item first (a hint stale against the state byte, a released-row or arrival
+// bit, no hint word: the item's key is cleared and it goes to k_block_rest), and the update
+// kernels leave exactly those marks.  Two things follow on the host (dm_split_form.h): the
+// steady, FIXED and sweep forms are always followed by the rest launch, so for them the
+// density record is a cost estimate and may be a little out of date; the dense kernel that
+// runs alone (skip_rest) takes the record as a proof, and a kept update withdraws it until a
+// count taken after a later writeback tick (dm_ctx::update_kept, check_dense).  The
+// key-clearing builds of the update kernels (k_release_keys, k_upsert_keys) clear the key of
+// every workgroup-bin resource of which they write a row: redundant for correctness, it keeps
+// FixKey's stated meaning and dm_store_stats' count of valid keys exact right after the call.
+// kUpdNotOne does not end the mode: maybe_general / all_sub_one are set as ever and the
+// resource's state byte is 1 by then.  Every other writer starts an epoch under either bit.
 #pragma once
 #include <cstdint>
 
@@ -60,6 +78,25 @@ inline RowWriteStart row_write_start(RowWrite w, bool keep_keys, bool keys_in_us
   s.defer = keep_keys && is_refresh(w);
   s.clear_keys = s.defer && keys_in_use;
   return s;
+}
+
+// The same for dm_keep_keys' bit set (above): what the callers ask.  With mode 0 or 1 the
+// answers are those of the two functions around it.
+constexpr int kKeepRefresh = 1, kKeepUpdates = 2;
+constexpr bool is_update(RowWrite w) {
+  return w == RowWrite::release || w == RowWrite::upsert || w == RowWrite::apply;
+}
+constexpr bool mode_keeps(RowWrite w, int mode) {
+  return (mode != 0 && is_refresh(w)) || ((mode & kKeepUpdates) && is_update(w));
+}
+inline RowWriteStart row_write_start_mode(RowWrite w, int mode, bool keys_in_use) {
+  RowWriteStart s;
+  s.defer = mode_keeps(w, mode);
+  s.clear_keys = s.defer && keys_in_use;
+  return s;
+}
+inline bool row_write_kept_mode(RowWrite w, int mode, bool rejected, bool nan) {
+  return mode_keeps(w, mode) && !rejected && !nan;
 }
 
 // After the flags are back.  rejected: the call failed or its validation refused it (the

@@ -290,8 +290,16 @@ int dm_set_profiling(dm_ctx* c, int on) {
 
 int dm_keep_keys(dm_ctx* c, int on) {
   DM_CHECK_CTX(c);
-  c->keep_keys = on != 0;
+  c->keep_mode = on;  // a bit set (DM_KEEP_REFRESH, DM_KEEP_UPDATES); any non-zero value keeps refreshes
   return DM_OK;
+}
+
+int dm_keep_stats(dm_ctx* c, int64_t* out, int max) {
+  if (!c || !out) return DM_E_INVAL;
+  const int64_t v[6] = {c->keep_mode,    c->kept_refreshes, c->kept_releases,
+                        c->kept_upserts, c->kept_batches,   c->kept_upd_rows};
+  for (int i = 0; i < 6 && i < max; ++i) out[i] = v[i];
+  return 6;
 }
 
 int dm_kernel_class_names(const char** names, int max) {

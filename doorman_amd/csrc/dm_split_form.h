@@ -75,9 +75,13 @@ struct FormInputs {
   uint64_t fix_live = 0;     // the part's, before this tick
   uint64_t sw_epoch = 0;     // the sweep record: the epoch of the count the device last told ...
   int64_t sw_told = 0;       // ... and the count
-  int64_t refreshed = 0;     // values of kept wants refreshes since the last tick: each may have cleared a key
+  int64_t refreshed = 0;     // kept refreshes' values and kept updates' rows since the last tick: each may have cleared a key
   int n = 0;                 // the part's items
   int64_t queued = 0;        // items the last split tick the host has heard of queued
+  // dm_keep_keys' DM_KEEP_UPDATES (dm_row_epoch.h).  The defaults are every other context's.
+  bool keep_updates = false;  // the bit is set
+  bool rec_kept = false;      // the record is the host's copy from before a kept update: an estimate, no proof
+  int64_t upd_rows = 0;       // rows kept updates wrote since the record's count
 };
 
 // `tried`: try_split's answer (asked only of a part with hints in a bin that splits).
@@ -94,9 +98,23 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   // Not for a bin in stream parts: its ticks are short enough for the rest launch to
   // cost more than the pass saves (C1: kernel 33.7 -> 29.3 us, step 37.8 -> 39.6 us,
   // profiles/steady_ab.md).
-  const bool steady_form = in.steady_ok && in.nparts == 1 && verified && in.rec_counts == 0 && !in.recompute;
+  // With DM_KEEP_UPDATES the counts need not be zero for a tick that can run the FIXED
+  // build (writeback in place): the steady kernels test every item themselves and queue what
+  // is not dense or carries a mask bit, so a few such items cost a few items of the rest
+  // launch, not the part its keys.  A few: the items not dense, those with mask bits and the
+  // rows kept updates wrote since the count (each may have ended a dense state or set a bit)
+  // are together at most a quarter of the part's items, try_split's bound for "too many for
+  // the rest kernel".  Above it the part runs the forms it always ran.
+  const int64_t odd = (int64_t)(uint32_t)in.rec_counts + (int64_t)(in.rec_counts >> 32) + in.upd_rows;
+  const bool few = in.keep_updates && in.writeback && in.inplace && 4 * odd <= in.n;
+  const bool clean = in.rec_counts == 0 && !in.rec_kept;
+  const bool steady_form = in.steady_ok && in.nparts == 1 && verified && (clean || few) && !in.recompute;
   f.steady = steady_form && in.steady_ok != 2;
-  f.skip_rest = !steady_form && verified && (uint32_t)in.rec_counts == 0;
+  // The dense kernel alone takes the record as a proof that nothing can be queued, which a
+  // copy from before a kept update is not: k_count_undense counts hint words, and an update
+  // that ended a dense state left the hint word set and stale (the guard would mark the store
+  // lost).  Not before a count taken after a later writeback tick.
+  f.skip_rest = !steady_form && verified && !in.rec_kept && (uint32_t)in.rec_counts == 0;
   // The FIXED build: a steady build on a writeback tick in place.  It may trust the
   // items' keys when the part's last tick was one too, in this row epoch; otherwise it
   // rewrites every key and the next one may.
@@ -107,7 +125,7 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   // Grids are hints: both kernels stride over their lists, so correctness never depends
   // on them.  The rest kernel's is sized from the last split tick's queue (an empty queue
   // costs 16 workgroups that read one count); the row kernel's from the count the device
-  // last told in this row epoch (and the keys that kept refreshes may have cleared since),
+  // last told in this row epoch (and the keys that kept refreshes and updates may have cleared since),
   // plus an eighth and 64 (the part's items until then).
   f.rest_grid = (int)std::min<int64_t>(512, std::max<int64_t>(16, in.queued));
   f.list_grid = in.n;

@@ -71,6 +71,37 @@ static int finish_update(dm_ctx* c, int64_t n, uint32_t* flags_out) {
   return DM_OK;
 }
 
+// How a call that dm_keep_keys may keep ends (dm_row_epoch.h): a wants refresh, and with
+// DM_KEEP_UPDATES a release, an upsert or a synchronous batch.  Where the mode does not cover
+// the call it starts a row epoch before it launches, as every writer does; where it does,
+// once its flags are back -- kept (dm_ctx::refresh_kept, update_kept), or rows_changed() on
+// every other way out of the call (a rejection, a NaN, a failure on the way).
+namespace {
+struct WriteEnd {
+  dm_ctx* c;
+  RowWrite w;
+  RowWriteStart start;
+  KeyClear kc;
+  bool ended = false;
+  WriteEnd(dm_ctx* ctx, RowWrite kind)
+      : c(ctx), w(kind), start(row_write_start_mode(kind, ctx->keep_mode, ctx->keys_in_use())), kc(ctx->key_clear()) {
+    if (!start.defer) end(true, false, 0);
+  }
+  ~WriteEnd() { end(true, false, 0); }
+  const KeyClear* keys() const { return start.clear_keys ? &kc : nullptr; }  // the launchers' build
+  void end(bool rejected, bool nan, int64_t n) {
+    if (ended) return;
+    ended = true;
+    if (!row_write_kept_mode(w, c->keep_mode, rejected, nan))
+      c->rows_changed();
+    else if (is_refresh(w))
+      c->refresh_kept(n);
+    else
+      c->update_kept(w, n);
+  }
+};
+}  // namespace
+
 int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
                     const int64_t* sub, const int64_t* exp) {
   DM_ENTER(c);
@@ -78,8 +109,8 @@ int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has
   if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   if (n < 0 || (n > 0 && (!rows || !has || !wants || !sub || !exp))) return c->fail(DM_E_INVAL, "bad upsert");
   if (n == 0) return DM_OK;
-  c->expl_rows = true;
-  c->rows_changed();
+  c->expl_rows = true;  // (kept or not: the rows take explicit expiries)
+  WriteEnd we(c, RowWrite::upsert);
   DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
   DM_HIP(c, c->st_has.ensure((size_t)n), "stage has");
   DM_HIP(c, c->st_wants.ensure((size_t)n), "stage wants");
@@ -91,11 +122,12 @@ int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has
   if (rc) return rc;
   DM_HIP(c, launch_upsert(n, c->st_rows.p, c->st_has.p, c->st_wants.p, c->st_sub.p, nullptr, c->st_exp.p, c->cfg.p, 0,
                           c->row_index(), c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p, c->expl.p,
-                          c->upd_flags.p, c->dense_upd(), c->stream),
+                          c->upd_flags.p, c->dense_upd(), c->stream, we.keys()),
          "upsert");
   uint32_t f = 0;
   rc = finish_update(c, n, &f);
   if (rc) return rc;
+  we.end(false, f & kUpdNaN, n);
   // an upsert can make a resource's subclients heterogeneous: stay conservative
   if ((f & (kUpdNaN | kUpdNotOne)) || !c->all_sub_one) c->maybe_general = true;
   if (f & kUpdNotOne) c->all_sub_one = false;
@@ -103,41 +135,13 @@ int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has
   return DM_OK;
 }
 
-// How a wants refresh ends (dm_row_epoch.h): with dm_keep_keys off it starts a row epoch
-// before it launches, as every writer does; with it on, once its flags are back -- a kept
-// refresh, or rows_changed() on every other way out of the call (a rejection, a NaN, a
-// failure on the way).
-namespace {
-struct RefreshEnd {
-  dm_ctx* c;
-  RowWrite w;
-  RowWriteStart start;
-  KeyClear kc;
-  bool ended = false;
-  RefreshEnd(dm_ctx* ctx, RowWrite kind)
-      : c(ctx), w(kind), start(row_write_start(kind, ctx->keep_keys, ctx->keys_in_use())), kc(ctx->key_clear()) {
-    if (!start.defer) end(true, false, 0);
-  }
-  ~RefreshEnd() { end(true, false, 0); }
-  const KeyClear* keys() const { return start.clear_keys ? &kc : nullptr; }  // the launchers' build
-  void end(bool rejected, bool nan, int64_t n) {
-    if (ended) return;
-    ended = true;
-    if (row_write_kept(w, c->keep_keys, rejected, nan))
-      c->refresh_kept(n);
-    else
-      c->rows_changed();
-  }
-};
-}  // namespace
-
 int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
   DM_ENTER(c);
   DM_STORE_OK(c);
   if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   if (n < 0 || (n > 0 && (!rows || !wants))) return c->fail(DM_E_INVAL, "bad update");
   if (n == 0) return DM_OK;
-  RefreshEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
+  WriteEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
   DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
   DM_HIP(c, c->st_wants.ensure((size_t)n), "stage wants");
   const StageCol cols[] = {{c->st_rows.p, rows, 8}, {c->st_wants.p, wants, 8}};
@@ -167,7 +171,7 @@ int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, con
     return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
   if (nwords == 0) return n == 0 ? DM_OK : c->fail(DM_E_INVAL, "packed values without a mask");
   if (first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
-  RefreshEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
+  WriteEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
   const int64_t nb = (nwords + 255) / 256;
   DM_HIP(c, c->st_mask.ensure((size_t)nwords), "stage mask");
   DM_HIP(c, c->st_wants.ensure((size_t)std::max<int64_t>(n, 1)), "stage wants");
@@ -202,17 +206,18 @@ int dm_store_release(dm_ctx* c, int64_t n, const int64_t* rows) {
   if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad release");
   if (n == 0) return DM_OK;
-  c->rows_changed();
+  WriteEnd we(c, RowWrite::release);
   DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
   const StageCol cols[] = {{c->st_rows.p, rows, 8}};
   int rc = staged_check(c, n, cols, 1, false, false);
   if (rc) return rc;
   DM_HIP(c, launch_release(n, c->st_rows.p, c->row_index(), c->has.p, c->wants.p, c->sub.p, c->expiry.p,
-                           c->agg.p, c->expl.p, c->upd_flags.p, c->dense_upd(), c->stream),
+                           c->agg.p, c->expl.p, c->upd_flags.p, c->dense_upd(), c->stream, we.keys()),
          "release");
   uint32_t f = 0;
   rc = finish_update(c, n, &f);
   if (rc) return rc;
+  we.end(false, false, n);
   c->have_result = false;
   return DM_OK;
 }
@@ -247,13 +252,16 @@ static int batch_args(dm_ctx* c, const dm_store_batch* b) {
 }
 
 // The batch's copies (copy stream), its three parts' kernels (context stream) and the
-// flags' copy back into S.h_flags; nothing waits for them here.
-static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S) {
+// flags' copy back into S.h_flags; nothing waits for them here.  we: the synchronous call's
+// end (its key-clearing builds, and the row epoch it has started or will decide on); null:
+// an asynchronous batch, which starts a row epoch here.
+static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S, const WriteEnd* we) {
   const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
   const bool sub32 = b->upsert_subclients32 != nullptr;
   if (nu > 0) c->expl_rows = true;  // arrivals take explicit expiries
   if (nu > 0 || nr > 0) c->chain_live_ok = false;  // subclients words written, rows released
-  c->rows_changed();  // (wants refreshes too: a NaN wants ends a resource's dense state)
+  if (!we) c->rows_changed();  // (wants refreshes too: a NaN wants ends a resource's dense state)
+  const KeyClear* kc = we ? we->keys() : nullptr;
   S.nu = nu;
   hipStream_t st = c->stream, cp = c->cpy;
   if (!S.flags.p) {
@@ -323,7 +331,7 @@ static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S
       DM_HIP(c, hipStreamWaitEvent(st, S.ev_wchunk[k], 0), "stage");
       if (v1 > v0)
         DM_HIP(c, launch_update_wants_mask(nw, S.mask.p, b->wants_first_row, c->N, nm, S.mwants.p, S.blk.p, S.wpre.p,
-                                           c->row_index(), c->sub.p, c->wants.p, c->agg.p, F + 0, st, 1, v0, v1),
+                                           c->row_index(), c->sub.p, c->wants.p, c->agg.p, F + 0, st, 1, v0, v1, kc),
                "masked update");
     }
   }
@@ -333,7 +341,7 @@ static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S
     DM_HIP(c, launch_check_rows(nr, S.rel.p, c->N, c->row_bits.p, nullptr, nullptr, nullptr, F + 1, st), "check rows");
     DM_HIP(c, launch_carry_reject(F + 0, F + 1, st), "carry");
     DM_HIP(c, launch_release(nr, S.rel.p, c->row_index(), c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p,
-                             c->expl.p, F + 1, c->dense_upd(), st),
+                             c->expl.p, F + 1, c->dense_upd(), st, kc),
            "release");
     DM_HIP(c, launch_clear_rows(nr, S.rel.p, c->N, c->row_bits.p, st), "clear rows");
   } else {
@@ -348,7 +356,8 @@ static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S
     DM_HIP(c, launch_carry_reject(F + 1, F + 2, st), "carry");
     DM_HIP(c, launch_upsert(nu, S.rows.p, b->upsert_has ? S.has.p : nullptr, S.wants.p, s64, s32,
                             b->upsert_expiry_ns ? S.exp.p : nullptr, c->cfg.p, b->upsert_now_ns, c->row_index(),
-                            c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p, c->expl.p, F + 2, c->dense_upd(), st),
+                            c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p, c->expl.p, F + 2, c->dense_upd(), st,
+                            kc),
            "upsert");
     DM_HIP(c, launch_clear_rows(nu, S.rows.p, c->N, c->row_bits.p, st), "clear rows");
   }
@@ -386,9 +395,12 @@ int dm_store_apply(dm_ctx* c, const dm_store_batch* b) {
   if (int rc = batch_args(c, b)) return rc;
   if (b->wants_nwords == 0 && b->release_n == 0 && b->upsert_n == 0) return DM_OK;
   dm_ctx::ApplySet& S = c->aset[0];
-  if (int rc = apply_enqueue(c, b, S)) return rc;
+  WriteEnd we(c, RowWrite::apply);
+  if (int rc = apply_enqueue(c, b, S, &we)) return rc;
   if (int rs = c->synced("batch")) return rs;
-  return apply_check(c, S, false);
+  if (int rc = apply_check(c, S, false)) return rc;  // (a rejected part: a row epoch, ~WriteEnd)
+  we.end(false, (S.h_flags.p[0] | S.h_flags.p[2]) & kUpdNaN, b->wants_n + b->release_n + b->upsert_n);
+  return DM_OK;
 }
 
 // Retire asynchronous set S: wait for its batch, then its flags.
@@ -411,7 +423,7 @@ int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) {
   // batches ahead of the device at most)
   if (int rc = async_retire(c, S)) return rc;
   S.may_general = b->wants_nwords > 0 || b->upsert_n > 0;
-  if (int rc = apply_enqueue(c, b, S)) return rc;
+  if (int rc = apply_enqueue(c, b, S, nullptr)) return rc;
   DM_HIP(c, hipEventRecord(S.ev_done, c->stream), "batch done");
   S.pending = true;
   c->async_seq += 1;

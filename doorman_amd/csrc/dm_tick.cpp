@@ -129,13 +129,17 @@ static hipError_t check_dense(dm_ctx* c, SplitSlot& sl, hipStream_t s) {
   // found items that are not dense: the refresh may have repaired the NaN that ended a
   // resource's dense state, and nothing else would count the part again before the next epoch
   // (tests/test_keep_keys_gpu.py::test_nan_and_rejection: the keys come back after the repair).
-  bool again = false;
-  if (sl.ver_epoch == c->row_epoch && sl.ver_write != c->write_epoch)
+  // And again after the first writeback tick that follows a kept update (dm_ctx::update_kept),
+  // which withdrew the record: this count, behind that tick on the part's stream, is the
+  // first that may prove the part dense again.
+  bool again = sl.recount;
+  if (!again && sl.ver_epoch == c->row_epoch && sl.ver_write != c->write_epoch)
     again = __atomic_load_n(sl.rec.h + 1, __ATOMIC_ACQUIRE) == c->row_epoch &&
             (uint32_t)__atomic_load_n(sl.rec.h, __ATOMIC_RELAXED) != 0;
   if ((sl.ver_epoch == c->row_epoch && !again) || n <= 0) return hipSuccess;
   sl.ver_epoch = c->row_epoch;
   sl.ver_write = c->write_epoch;
+  sl.recount = false;
   return launch_count_undense(c->bins[sl.b].p + sl.lo[0], (int)n, (unsigned long long*)sl.rec.d,
                               (unsigned long long)c->row_epoch, s);
 }
@@ -423,6 +427,7 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   in.inplace = pt.p.out_gets == pt.p.has;
   in.fix_live = sl.fix_live;
   in.refreshed = c->kept_rows;
+  in.keep_updates = (c->keep_mode & kKeepUpdates) != 0;
   in.n = n;
   const bool may_split = in.hints && in.dense_split;
   if (may_split) in.queued = sl.read_queued();
@@ -496,7 +501,7 @@ int Tick::bins() {
     for (int j = 0; j < nparts; ++j)
       if (int rc = bin_part(b, lb, nparts, j)) return rc;
   }
-  c->kept_rows = 0;  // (every part's sweep is sized: FormInputs::refreshed)
+  c->kept_rows = c->kept_upd_rows = 0;  // (every part's sweep is sized: FormInputs::refreshed)
   return DM_OK;
 }
 

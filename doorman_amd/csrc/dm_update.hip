@@ -60,63 +60,47 @@ __global__ void k_clear_rows(int64_t n, const int64_t* __restrict__ rows, int64_
 // Narrow arrivals (dm_store_batch): has == nullptr -> 0; sub32 instead of sub;
 // expiry == nullptr -> the resource's now + lease length (the Assign's expiry,
 // store.go:161).
+// Two builds of one body each (dm_update_upsert.inc, dm_update_release.inc), as the refresh
+// kernels below, whose comment has the rule, the clearing store and its stream order.  The
+// key-clearing builds (k_upsert_keys, k_release_keys) run only under dm_keep_keys'
+// DM_KEEP_UPDATES while some part has keys in use (dm_row_epoch.h); they store an invalid key
+// for every workgroup-bin resource of which the call writes a row.  The tick kernels would
+// not trust such a resource's key anyway (the stale hint, the mask bit: group_segment STEADY,
+// k_fixed_sweep); cleared here, a valid key keeps meaning what dm_device.h FixKey says.
 __global__ void k_upsert(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ has,
                          const double* __restrict__ wants, const int64_t* __restrict__ sub,
                          const int32_t* __restrict__ sub32, const int64_t* __restrict__ expiry,
                          const ResCfg* __restrict__ cfg, int64_t now, RowIndex ix, double* s_has, double* s_wants,
                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
                          DenseUpd du) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (*flags & kUpdReject) return;  // uniform over the grid
-  const bool active = i < n;
-  int seg = 0;
-  double dh = 0.0, dw = 0.0;
-  long long ds = 0;
-  if (active) {
-    const int64_t r = rows[i];
-    seg = seg_of_row(ix, r);
-    const double hv = has ? has[i] : 0.0;
-    const int64_t sv = sub32 ? (int64_t)sub32[i] : sub[i];
-    dh = hv - s_has[r];
-    dw = wants[i] - s_wants[r];
-    ds = sv - sub_value(s_sub[r]);
-    s_has[r] = hv;
-    s_wants[r] = wants[i];
-    s_sub[r] = (int32_t)((uint32_t)sv | kSubExplicit);  // in [0, kSubMax] (k_check_rows); expiry explicit
-    const int64_t ex = expiry ? expiry[i] : now + (int64_t)cfg[seg].lease_len_s * kNs;
-    s_exp[r] = ex;
-    // an arrival with the dense resource's count and the Assign's expiry, not before the
-    // followers': the resource stays dense, the row goes into its arrival mask
-    MaskPos mp;
-    WorkItem* it;
-    const uint8_t st = expl[seg];
-    if (!expiry && dense_row(du, ix, seg, r, st, &mp, &it) && sv == (int64_t)st - 1 && ex >= agg[seg].follow_exp) {
-      mask_bit(du.rmask + rel_mask_offset(ix.seg_off[seg]), mp.roff, mp.rbit, false);
-      mask_bit(du.rmask + rel_mask_offset(ix.seg_off[seg]), mp.aoff, mp.abit, true);
-      atomicOr(&it->n, 1 << 25);
-    } else {
-      expl[seg] = 1;  // the tick reads this resource's expiry column again
-    }
-  }
-  wave_seg_add(agg, active, seg, dh, dw, ds, true, true);
+  constexpr bool kKeys = false;
+  const KeyClear kc{};
+#include "dm_update_upsert.inc"
+}
+
+__global__ void k_upsert_keys(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ has,
+                              const double* __restrict__ wants, const int64_t* __restrict__ sub,
+                              const int32_t* __restrict__ sub32, const int64_t* __restrict__ expiry,
+                              const ResCfg* __restrict__ cfg, int64_t now, RowIndex ix, double* s_has,
+                              double* s_wants, int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl,
+                              const uint32_t* flags, DenseUpd du, KeyClear kc) {
+  constexpr bool kKeys = true;
+#include "dm_update_upsert.inc"
 }
 
 __global__ void k_release(int64_t n, const int64_t* __restrict__ rows, RowIndex ix, double* s_has, double* s_wants,
                           int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
                           DenseUpd du) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (*flags & kUpdReject) return;  // uniform over the grid
-  const bool active = i < n;
-  int seg = 0;
-  double dh = 0.0, dw = 0.0;
-  long long ds = 0;
-  if (active) {
-    const int64_t r = rows[i];
-    seg = seg_of_row(ix, r);
-    (void)s_exp;
-    release_row(ix, seg, r, s_has, s_wants, s_sub, expl, du, &dh, &dw, &ds);
-  }
-  wave_seg_add(agg, active, seg, dh, dw, ds, true, true);
+  constexpr bool kKeys = false;
+  const KeyClear kc{};
+#include "dm_update_release.inc"
+}
+
+__global__ void k_release_keys(int64_t n, const int64_t* __restrict__ rows, RowIndex ix, double* s_has,
+                               double* s_wants, int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl,
+                               const uint32_t* flags, DenseUpd du, KeyClear kc) {
+  constexpr bool kKeys = true;
+#include "dm_update_release.inc"
 }
 
 // Narrow Assign for a refresh that only changes wants (store.go:157):
@@ -296,19 +280,28 @@ __global__ void k_gather_leases(int64_t n, const int64_t* __restrict__ rows, con
 hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
                          const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
                          const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
-                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st) {
+                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st,
+                         const KeyClear* kc) {
   if (n <= 0) return hipSuccess;
-  k_upsert<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, cfg, now, ix, s_has,
-                                                        s_wants, s_sub, s_exp, agg, expl, flags, du);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (kc)
+    k_upsert_keys<<<grid, 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, cfg, now, ix, s_has, s_wants, s_sub,
+                                        s_exp, agg, expl, flags, du, *kc);
+  else
+    k_upsert<<<grid, 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, cfg, now, ix, s_has, s_wants, s_sub, s_exp,
+                                   agg, expl, flags, du);
   return hipGetLastError();
 }
 
 hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
                           int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
-                          const DenseUpd& du, hipStream_t st) {
+                          const DenseUpd& du, hipStream_t st, const KeyClear* kc) {
   if (n <= 0) return hipSuccess;
-  k_release<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, rows, ix, s_has, s_wants, s_sub, s_exp, agg, expl, flags,
-                                                         du);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (kc)
+    k_release_keys<<<grid, 256, 0, st>>>(n, rows, ix, s_has, s_wants, s_sub, s_exp, agg, expl, flags, du, *kc);
+  else
+    k_release<<<grid, 256, 0, st>>>(n, rows, ix, s_has, s_wants, s_sub, s_exp, agg, expl, flags, du);
   return hipGetLastError();
 }
 

@@ -330,10 +330,19 @@ class Engine:
     def set_profiling(self, on: bool):
         self._chk(self._L.dm_set_profiling(self._ctx, 1 if on else 0))
 
-    def keep_keys(self, on: bool):
+    def keep_keys(self, on):
         """dm_keep_keys: a wants refresh without NaN keeps the fixed-point keys of every resource
-        in which it changed no row's wants bits (off by default)."""
-        self._chk(self._L.dm_keep_keys(self._ctx, 1 if on else 0))
+        in which it changed no row's wants bits (off by default).  `on` is a bit set: True or
+        _lib.DM_KEEP_REFRESH (1) is that mode; with _lib.DM_KEEP_UPDATES (2) release, upsert and
+        the synchronous apply keep the keys of the resources whose rows they did not write."""
+        self._chk(self._L.dm_keep_keys(self._ctx, int(on)))
+
+    def keep_stats(self) -> dict:
+        """dm_keep_stats: the mode and what the context kept under it."""
+        arr = (ctypes.c_int64 * 6)()
+        self._chk(self._L.dm_keep_stats(self._ctx, arr, 6))
+        names = ("mode", "kept_refreshes", "kept_releases", "kept_upserts", "kept_batches", "kept_update_rows")
+        return {k: int(arr[i]) for i, k in enumerate(names)}
 
     def kernel_times(self) -> dict:
         cap = 64

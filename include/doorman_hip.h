@@ -59,7 +59,9 @@ extern "C" {
    DM_SWEEP=0 in the environment, read when the context is created, keeps the dense
    kernel over every item), and the call returns 23; dm_keep_keys (a wants refresh keeps
    the fixed-point keys of the resources it did not change), with slot 23, the refreshes
-   the context kept, and the call returns 24;
+   the context kept, and the call returns 24; dm_keep_keys' argument as a bit set
+   (DM_KEEP_REFRESH, the mode it had, and DM_KEEP_UPDATES, which also keeps releases, upserts
+   and synchronous batches) with dm_keep_stats (its counters; dm_plan_info is not extended);
    dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
    are in use, and returns 5 (a caller that passes max = 4 gets the four it got).  (Added
    slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
@@ -521,8 +523,26 @@ int dm_set_profiling(dm_ctx* ctx, int on);
    leases and the sums is unchanged bit for bit.  A refresh with a NaN, a rejected one and
    every other writer (the batches of dm_store_apply / dm_store_apply_async included) end the
    keys' use as they always did.  Default off.  Returns DM_OK, or DM_E_INVAL for a NULL
-   context. */
+   context.
+   `on` is a bit set.  DM_KEEP_REFRESH (1) is the mode above, and any non-zero value turns it
+   on.  DM_KEEP_UPDATES (2) also keeps dm_store_release, dm_store_upsert and the synchronous
+   dm_store_apply: such a call, when no part of it was rejected and none carried a NaN wants,
+   starts no row epoch either.  On the device it clears the key of every workgroup-bin
+   resource of which it wrote a row; the tick kernels hand every item with a released row, a
+   pending arrival or an ended dense state to the general path themselves, so the other
+   resources' keys stay in use as long as such items are at most a quarter of their bin's
+   (above that the bin runs as with the bit clear).  Subclient counts other than one do not end
+   the mode.  Every other writer starts a row epoch as ever, under either bit:
+   dm_store_apply_async (its NaN flag arrives two batches late), dm_decide, dm_store_clean,
+   dm_store_relayout, dm_store_load, dm_config_load and dm_hier_root_tick. */
+#define DM_KEEP_REFRESH 1
+#define DM_KEEP_UPDATES 2
 int dm_keep_keys(dm_ctx* ctx, int on);
+/* dm_keep_keys' counters: the mode (the bit set last passed), then what the context kept since
+   it was created: wants refreshes, dm_store_release calls, dm_store_upsert calls, dm_store_apply
+   batches; then the rows the kept releases, upserts and batches wrote since the last tick.
+   Fills up to max entries; returns 6, or DM_E_INVAL for a NULL context or output. */
+int dm_keep_stats(dm_ctx* ctx, int64_t* out, int max);
 /* fills up to max entries; returns the number of kernel classes (>= 0) */
 int dm_kernel_times(dm_ctx* ctx, dm_kernel_time* out, int max);
 /* the names dm_kernel_times reports, in its order (static strings; no context or GPU

@@ -19,6 +19,23 @@ on and keys in use launches the key-clearing build, the other the plain one; the
 the stored ones, so no key is cleared and no tick is needed between the calls.  The call's
 host time (its copies included) per build.
 
+--writer release,arrival,batch (DM_KEEP_UPDATES; --out profiles/keep_updates_ab.md): the two
+engines run dm_keep_keys modes 1 and 3, so the first behaves as the commit before the bit did.
+Per k, on the same store: "release" frees one row in each of k resources (dm_store_release),
+"arrival" refills them (a narrow arrival through dm_store_apply: no expiry, the resource's
+count), each followed by a synchronous writeback tick and timed with it, a release round and
+an arrival round taking turns; "batch" is one dm_store_apply that frees one row in each of
+the k resources and refills the row the batch before freed, then the tick.  Guidance: mode 3
+pays for a tick that stays FIXED with a rest launch over the items that hold a released row
+or an arrival, so it gains while those are few (at most a quarter of a bin's resources: above
+that the tick runs as in mode 1, and the call has cleared keys for nothing).  Measured on the
+100,000 x 1,000 store (profiles/keep_updates_ab.md): mode 3 takes a fifth to a quarter of mode
+1's time at k = 100 and 1,000, four fifths at 10,000 for releases and arrivals; for a batch of
+both at 10,000, and for every writer at 100,000, the two modes lie within each other's ranges
+(mode 3's median 7 us above mode 1's for the batch at 100,000, 805 against 812 us): nothing
+gained there, so a store whose every round writes a tenth of its resources or more can leave
+the bit clear.
+
 Prints one JSON line; --out also writes the tables as Markdown.
 """
 import argparse
@@ -40,11 +57,12 @@ NOW = W.NOW_NS
 STEP = 1.0 / 1024
 
 
-def engines(snap):
+def engines(snap, modes=(0, 1)):
     """(mode off, mode on), both at the store's fixed point with keys in use."""
     from doorman_amd.engine import Engine
     pair = (Engine(0), Engine(0))
-    pair[1].keep_keys(True)
+    for e, m in zip(pair, modes):
+        e.keep_keys(m)
     R = len(snap["seg_off"]) - 1
     for e in pair:
         e.load(snap)
@@ -100,6 +118,91 @@ def ab_rounds(pair, snap, k, changed, runs, rng):
         for _ in range(3):
             e.apportion(NOW, writeback=True)
     return out
+
+
+def update_rounds(pair, snap, k, runs, rng, writers):
+    """Modes 1 and 3 (pair[0], pair[1]): releases, arrivals and batches of both in k resources."""
+    R = len(snap["seg_off"]) - 1
+    clients = len(snap["wants"]) // R
+    res = rng.choice(R, k, replace=False).astype(np.int64)
+    first = rng.integers(0, clients - 1, k)
+    X, Y = res * clients + first, res * clients + first + 1  # two rows of each resource
+    one = np.ones(k, np.int32)
+    tick = lambda e: e.apportion(NOW, writeback=True)  # noqa: E731
+    arrive = lambda e, rows: e.apply(upsert=(rows, None, snap["wants"][rows], one, None), now_ns=NOW)  # noqa: E731
+
+    def timed(e, call):
+        t0 = time.perf_counter()
+        call(e)
+        tick(e)
+        return 1e6 * (time.perf_counter() - t0)
+
+    def state(e):
+        info, ks = e.plan_info(), e.keep_stats()
+        return {"fixed_parts": info["fixed_parts"], "sweep_parts": info["sweep_parts"],
+                "wb_inplace": info["wb_inplace"], "fixed_items": e.store_stats()["fixed_items"],
+                "kept": [ks["kept_releases"], ks["kept_batches"]]}
+
+    out = {}
+    if "release" in writers or "arrival" in writers:
+        t_rel, t_arr, st_rel, st_arr = ([], []), ([], []), [None, None], [None, None]
+        for r in range(runs + 2):
+            for i in (1, 0):
+                a = timed(pair[i], lambda e: e.release(X))
+                st_rel[i] = state(pair[i])
+                b = timed(pair[i], lambda e: arrive(e, X))
+                st_arr[i] = state(pair[i])
+                if r >= 2:
+                    t_rel[i].append(a)
+                    t_arr[i].append(b)
+        for name, t, st in (("release", t_rel, st_rel), ("arrival", t_arr, st_arr)):
+            out[name] = {m: {"round_us": spread(t[i]), "runs": [round(x, 1) for x in t[i]], **st[i]}
+                         for i, m in ((0, "mode1"), (1, "mode3"))}
+        for e in pair:
+            for _ in range(3):
+                tick(e)
+    if "batch" in writers:
+        for e in pair:  # one row of each resource free, as between two batches
+            e.release(Y)
+            tick(e)
+        t, st = ([], []), [None, None]
+        for r in range(runs + 2):
+            free, take = (X, Y) if r % 2 == 0 else (Y, X)
+            for i in (1, 0):
+                cols = (take, None, snap["wants"][take], one, None)
+                a = timed(pair[i], lambda e: e.apply(release_rows=free, upsert=cols, now_ns=NOW))
+                st[i] = state(pair[i])
+                if r >= 2:
+                    t[i].append(a)
+        out["batch"] = {m: {"round_us": spread(t[i]), "runs": [round(x, 1) for x in t[i]], **st[i]}
+                        for i, m in ((0, "mode1"), (1, "mode3"))}
+        last = Y if (runs + 2) % 2 == 0 else X  # the rows the last batch left free
+        for e in pair:
+            arrive(e, last)
+            for _ in range(3):
+                tick(e)
+    return out
+
+
+def updates_markdown(out):
+    L = ["# dm_keep_keys modes 1 and 3: releases, arrivals and batches in k resources, then a writeback tick", "",
+         "`python tools/keep_keys_ab.py --writer release,arrival,batch` on one MI355X: %d resources x 1,000 rows, "
+         "FairShare, at its fixed point; two engines in one process, mode 1 (which treats these calls as the commit "
+         "before DM_KEEP_UPDATES did) and mode 3, taking turns run by run; %d timed rounds each; host time of the "
+         "call and the synchronous tick together, in us (median, min - max).  After the round: the parts whose tick "
+         "ran with keys in use, and the valid keys." % (out["resources"], out["runs"]), "",
+         "| writer | k | mode 1 | mode 3 | mode 3: parts with keys, keys | every mode-3 run below every mode-1 run |",
+         "|---|---|---|---|---|---|"]
+    for c in out["cases"]:
+        for w in ("release", "arrival", "batch"):
+            if w not in c:
+                continue
+            a, b = c[w]["mode1"]["round_us"], c[w]["mode3"]["round_us"]
+            L.append("| %s | %d | %.1f (%.1f - %.1f) | %.1f (%.1f - %.1f) | %d, %d | %s |"
+                     % (w, c["k"], a["median"], a["min"], a["max"], b["median"], b["min"], b["max"],
+                        c[w]["mode3"]["fixed_parts"], c[w]["mode3"]["fixed_items"],
+                        "yes" if b["max"] < a["min"] else "no"))
+    return "\n".join(L) + "\n"
 
 
 def refresh_calls(R, runs, rng):
@@ -163,13 +266,30 @@ if __name__ == "__main__":
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--ks", default="100,1000,10000,100000")
     ap.add_argument("--refresh-resources", type=int, default=125_000, help="0: skip the refresh calls' part")
+    ap.add_argument("--writer", default="refresh",
+                    help="refresh (modes 0 and 1), or a list of release, arrival, batch (modes 1 and 3)")
     ap.add_argument("--out")
     a = ap.parse_args()
     rng = np.random.default_rng(3)
     t0 = time.perf_counter()
     snap = all_fixed_store(a.resources)
-    pair = engines(snap)
     out = {"resources": a.resources, "rows": int(len(snap["wants"])), "runs": a.runs, "cases": []}
+    if a.writer != "refresh":
+        pair = engines(snap, (1, 3))
+        try:
+            for k in (int(x) for x in a.ks.split(",") if x):
+                k = min(k, a.resources)
+                out["cases"].append({"k": k, **update_rounds(pair, snap, k, a.runs, rng, a.writer.split(","))})
+        finally:
+            for e in pair:
+                e.close()
+        out["seconds"] = round(time.perf_counter() - t0, 1)
+        print(json.dumps(out))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(updates_markdown(out))
+        sys.exit(0)
+    pair = engines(snap)
     try:
         for k in (int(x) for x in a.ks.split(",") if x):  # (--ks "": the refresh calls' part alone)
             for changed in (True, False):
