@@ -2,8 +2,8 @@
 // device-resident columnar lease store, its dispatch plan, streams and policy state), the
 // types that own its device memory, pinned host memory and events, the four owners of its
 // cross-stream order (StreamOrder, TickDone, TemplatePipe, QueueCalibration: they carry out
-// what dm_tick_order.h decides), the entry macros of the C-ABI calls, and the functions
-// that cross a unit boundary.  The only definition of
+// what dm_tick_order.h decides), the large-resource chain's owner (dm_large_chain.h), the
+// entry macros of the C-ABI calls, and the functions that cross a unit boundary.  The only definition of
 // dm_ctx; the units around it are dm_runtime.cpp (context life, streams, profiling),
 // dm_plan.cpp, dm_tick.cpp, dm_decide.cpp, dm_store.cpp, dm_store_update.cpp and
 // dm_hier_host.cpp.  See DESIGN.md §3-§5.
@@ -23,6 +23,7 @@
 
 #include "../../include/doorman_hip.h"
 #include "dm_device.h"
+#include "dm_large_form.h"
 #include "dm_launch.h"
 #include "dm_row_epoch.h"
 #include "dm_split_form.h"
@@ -432,6 +433,8 @@ struct QueueCalibration {
 
 }  // namespace dm
 
+#include "dm_large_chain.h"
+
 using namespace dm;
 
 struct dm_ctx {
@@ -477,10 +480,6 @@ struct dm_ctx {
   // turns every live explicit row into a follower).  Without them pass A's
   // speculative round 1 is exact and pass B runs one workgroup per large resource.
   bool expl_rows = true;
-  // the last call that changed the store was a writeback tick through the chain
-  // (Partials::s_live): cleared at the start of every tick and by every call that
-  // writes a subclients word or releases a row
-  bool chain_live_ok = false;
   // Row epoch: bumped by every call that writes rows (loads, plans, upserts, releases,
   // wants refreshes, decide, the root's tick) -- never by a tick.  Within one epoch a
   // writeback tick leaves every dense workgroup-bin resource dense (dm_tick_group.hip),
@@ -489,10 +488,10 @@ struct dm_ctx {
   // Some writers may leave it alone under dm_keep_keys (dm_row_epoch.h has the rule and why
   // it is safe): a wants refresh, which ends as refresh_kept(), and with DM_KEEP_UPDATES a
   // release, an upsert or a synchronous batch, which end as update_kept().  write_epoch moves with
-  // every write, kept or not: what the large chain's light redo asks (redo_epoch).
+  // every write, kept or not: what the large chain's light redo asks (LargeChain::redo_epoch).
   uint64_t row_epoch = 1, write_epoch = 1;
   void rows_changed() {
-    chain_live_ok = false;
+    chain.rows_written();
     row_epoch += 1;
     write_epoch += 1;
     for (SplitSlot& s : split) s.fix_live = 0;  // no fixed-point key is trusted across a write (SplitSlot)
@@ -510,13 +509,13 @@ struct dm_ctx {
   int64_t kept_refreshes = 0, kept_rows = 0;
   int64_t kept_releases = 0, kept_upserts = 0, kept_batches = 0, kept_upd_rows = 0;
   void refresh_kept(int64_t n) {
-    chain_live_ok = false;
+    chain.rows_written();
     write_epoch += 1;
     kept_refreshes += 1;
     kept_rows += n;
   }
   void update_kept(RowWrite w, int64_t n) {
-    chain_live_ok = false;
+    chain.rows_written();
     write_epoch += 1;
     (w == RowWrite::release ? kept_releases : w == RowWrite::upsert ? kept_upserts : kept_batches) += 1;
     kept_rows += n;
@@ -654,39 +653,9 @@ struct dm_ctx {
       s.rec = {h_rec.p + 2 * i, h_rec.d + 2 * i}, s.sweep = {h_sw.p + 2 * i, h_sw.d + 2 * i};
     }
   }
-  // large-path partials
-  DBuf<int64_t> pa_cnt, pa_cnt_all, pa_smin, pa_smax, pb_w, pc_sgt;
-  DBuf<double> pa_has, pa_wants, pa_has_all, pa_wants_all, pb_x, pb_y, pc_ee, pd_delta;
-  DBuf<int32_t> pa_nan;
-  DBuf<uint32_t> pa_live;
-  DBuf<uint8_t> p_tot;
-  // the speculative chain (k_large_spec + k_large_redo; DM_SPEC_CHAIN=0: the chain):
-  // per large resource its SpecTot, the redo's launch count, the host-mapped give-up flag
-  bool spec_chain = true;
-  DBuf<SpecTot> p_spec;
-  DBuf<uint32_t> p_spec_ring;  // SpecArgs::ring
-  // 3/4 of the redo workgroups (full build) the GPU holds at once: the full build's
-  // grid when the store has that many team slots
-  int64_t redo_cap = 0;
-  // the redo by teams (k_large_redo_team): team slots and the two builds' grids.  (The
-  // per-chunk redo of round 4, bounded by redo_cap chunks per resource, was retired in
-  // round 5: the teams need only kTeamMax co-resident workgroups for any resource.)
-  DBuf<int32_t> p_team;
-  int nslots = 0, team_grid_full = 1, team_grid_light = 1;
-  uint64_t spec_seq = 0;
-  HBuf<int32_t> h_serr;  // [0] the give-up flag, [1] SpecArgs::seen
-  // k_large_redo's light build (dm_tick_large.hip) while the last redo the host saw found
-  // nothing marked and no row changed since (DM_REDO_LIGHT: 0 never, 1 so, 2 always)
-  int redo_light = 1;
-  uint64_t redo_epoch = 0;  // write_epoch at the last speculative tick
-  DBuf<int32_t> p_uni;
-  // heterogeneous FairShare on the chain (allocated on the first tick that may need it)
-  DBuf<uint32_t> ph_set;  // per large resource: distinct subclient counts (all ones between ticks)
-  DBuf<int32_t> ph_n, ph_bkc;
-  size_t ph_set_ready = 0;  // large resources whose set slots are initialised
-  DBuf<uint8_t> ph_het;
-  DBuf<double> ph_bkw;
-  DBuf<int64_t> ph_bks;
+  // the large-resource chain: its partials, the speculative form's state, the
+  // heterogeneous form's buffers (dm_large_chain.h)
+  LargeChain chain;
   // worklist of resources for k_general (heterogeneous-subclient FairShare)
   DBuf<int32_t> glist, gcount;
   // Some non-small resource may need k_general.  A store update can make a store "maybe
@@ -824,7 +793,7 @@ struct dm_ctx {
           store_lost = true;
           lost_msg = "a dense kernel queued an item on a tick that skipped its rest kernel";
         }
-      if (!store_lost && h_serr.p && __atomic_load_n(h_serr.p, __ATOMIC_RELAXED)) {
+      if (!store_lost && chain.gave_up()) {
         store_lost = true;
         lost_msg = "a redo workgroup of the speculative chain gave up waiting for its resource";
       }

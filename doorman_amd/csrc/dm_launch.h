@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_device.h"
+#include "dm_large_form.h"
 
 namespace dm {
 // dm_tick_group.hip
@@ -45,11 +46,18 @@ hipError_t launch_bin_rest(const BinItems& w, const DevParams& p, const SplitArg
                            int rest_grid, hipEvent_t done, hipStream_t st);
 // dm_tick_large.hip
 int redo_blocks_per_cu();
-hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls,
-                             const Partials& P, const SpecArgs& S, int redo_grid, int32_t* glist, int32_t* gcount,
-                             hipStream_t st);
-hipError_t launch_large(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls, int nls,
-                        const Partials& P, int32_t* glist, int32_t* gcount, hipStream_t st);
+// The chain's one launcher takes the phase (dm_large_form.h LargePhase: each names its
+// kernel) and what the chain's kernels share as one argument.  Host-side only: the launcher
+// unpacks it into the kernel's own arguments.  The grid is the phase's (dm_large_chain.h
+// LargeChain::grid), and S is read by the speculative form's phases alone.
+struct LargeArgs {
+  const Chunk* chunks;
+  const LargeSeg* ls;
+  Partials P;
+  SpecArgs S;
+  int32_t *glist, *gcount;  // k_general's worklist and its count
+};
+hipError_t launch_large(LargePhase ph, dim3 grid, const DevParams& p, const LargeArgs& a, hipStream_t st);
 // dm_tick_general.hip
 hipError_t launch_general(const DevParams& p, const int32_t* glist, const int32_t* gcount, int blocks,
                           hipStream_t st);

@@ -297,50 +297,7 @@ int dm::upload_plan(dm_ctx* c) {
   }
   if (int rc = init_split_slots(c, st)) return rc;
   if (int rc = update_bin4_shape(c, st)) return rc;
-  const size_t nc = std::max<size_t>(c->h_chunks.size(), 1);
-  DM_HIP(c, c->pa_cnt.ensure(nc), "partials");
-  DM_HIP(c, c->pa_cnt_all.ensure(nc), "partials");
-  DM_HIP(c, c->pa_has_all.ensure(nc), "partials");
-  DM_HIP(c, c->pa_wants_all.ensure(nc), "partials");
-  DM_HIP(c, c->pa_smin.ensure(nc), "partials");
-  DM_HIP(c, c->pa_smax.ensure(nc), "partials");
-  DM_HIP(c, c->pb_w.ensure(nc), "partials");
-  DM_HIP(c, c->pc_sgt.ensure(nc), "partials");
-  DM_HIP(c, c->pa_has.ensure(nc), "partials");
-  DM_HIP(c, c->pa_wants.ensure(nc), "partials");
-  DM_HIP(c, c->pb_x.ensure(nc), "partials");
-  DM_HIP(c, c->pb_y.ensure(nc), "partials");
-  DM_HIP(c, c->pc_ee.ensure(nc), "partials");
-  DM_HIP(c, c->pd_delta.ensure(nc), "partials");
-  DM_HIP(c, c->pa_nan.ensure(nc), "partials");
-  DM_HIP(c, c->pa_live.ensure(nc * 256), "partials");
-  DM_HIP(c, c->p_uni.ensure(nc), "partials");
-  DM_HIP(c, c->p_tot.ensure(std::max<size_t>(c->h_large.size(), 1) * kSegTotBytes), "partials");
-  {  // no resource has totals to speculate on yet (valid 0)
-    const size_t nl = std::max<size_t>(c->h_large.size(), 1);
-    DM_HIP(c, c->p_spec.ensure(nl), "speculative chain");
-    DM_HIP(c, hipMemsetAsync(c->p_spec.p, 0, nl * sizeof(SpecTot), st), "speculative chain");
-    DM_HIP(c, c->p_spec_ring.ensure(4), "speculative chain");
-    DM_HIP(c, hipMemsetAsync(c->p_spec_ring.p, 0, 4 * sizeof(uint32_t), st), "speculative chain");
-    std::vector<int32_t> team;
-    for (size_t l = 0; l < c->h_large.size(); ++l) {
-      const int nch_l = c->h_large[l].chunk_end - c->h_large[l].chunk_begin;
-      for (int m = 0; m < std::min(nch_l, kTeamMax); ++m) team.push_back((int32_t)(l << 8 | (size_t)m));
-    }
-    c->nslots = (int)team.size();
-    DM_HIP(c, upload(c->p_team, team.data(), team.size(), st), "redo teams");
-    // every team's members can be resident at once: >= kTeamMax workgroups (the full
-    // build: up to what the GPU holds; the light one: a steady tick's launch is all it costs)
-    c->team_grid_full = std::max(1, (int)std::min<int64_t>(c->nslots, std::max<int64_t>(kTeamMax, c->redo_cap)));
-    c->team_grid_light = std::max(1, std::min(c->nslots, kTeamMax));
-    c->spec_seq = 0;
-    if (!c->h_serr.p)
-      DM_HIP(c, c->h_serr.alloc(2, hipHostMallocMapped | hipHostMallocCoherent), "speculative chain");
-    __atomic_store_n(c->h_serr.p, 0, __ATOMIC_RELAXED);
-    __atomic_store_n(c->h_serr.p + 1, 1, __ATOMIC_RELAXED);  // no redo seen yet: the full build first
-  }
-  DM_HIP(c, hipMemsetAsync(c->p_tot.p, 0, std::max<size_t>(c->h_large.size(), 1) * kSegTotBytes, st),
-         "partials");  // SegTot::rel starts clear
+  DM_HIP(c, c->chain.plan(c->h_large, c->h_chunks, st), "large-resource chain");
   c->n_nonsmall = 0;
   for (int64_t r = 0; r < c->R; ++r)
     if (c->h_seg_off[r + 1] - c->h_seg_off[r] > kSmallMax) ++c->n_nonsmall;

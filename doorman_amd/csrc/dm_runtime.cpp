@@ -159,8 +159,8 @@ int dm_create(int device, dm_ctx** out) {
   // library chooses between by itself, so that a test can compare the two on the same
   // ticks.  No other environment switch exists (round 5 retired the A/B probes).
   if (const char* df = getenv("DM_DECIDE_FAST")) c->decide_fast = atoi(df) != 0;
-  if (const char* sc = getenv("DM_SPEC_CHAIN")) c->spec_chain = atoi(sc) != 0;
-  if (const char* rl = getenv("DM_REDO_LIGHT")) c->redo_light = atoi(rl);
+  if (const char* sc = getenv("DM_SPEC_CHAIN")) c->chain.spec_chain = atoi(sc) != 0;
+  if (const char* rl = getenv("DM_REDO_LIGHT")) c->chain.redo_light = atoi(rl);
   if (const char* qc = getenv("DM_QUEUE_CALIB")) {  // 0: keep the creation-order queue assignment; 2: log
     if (atoi(qc) == 0) c->qcal.cal.phase = QueueCalib::Phase::Done;
     c->qcal.cal.log = atoi(qc) == 2;
@@ -185,7 +185,7 @@ int dm_create(int device, dm_ctx** out) {
   (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
   // a quarter of headroom: the other classes' streams hold slots too, and run ahead
   // (DM_DEFER_JOIN)
-  c->redo_cap = (int64_t)std::max(ncu, 1) * redo_blocks_per_cu() * 3 / 4;
+  c->chain.redo_cap = (int64_t)std::max(ncu, 1) * redo_blocks_per_cu() * 3 / 4;
   if (e == hipSuccess) e = take_aux(c, ncu);
   c->stream = c->own_stream;
   for (int i = 0; i < 2 && e == hipSuccess; ++i) e = c->ev_stage[i].create(hipEventDisableTiming);
@@ -340,7 +340,7 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   v[2 + kNumBins] = (int64_t)c->h_chunks.size();
   v[3 + kNumBins] = c->N;
   v[4 + kNumBins] = (c->bin6_wide ? 1 : 0) | (c->bin4_wave ? 2 : 0);  // bit 0: bin 6 on 512 x 8 (else 256 x 16); bit 1: bin 4 on 64 x 16
-  v[5 + kNumBins] = c->redo_cap;  // 3/4 of the redo's full-build workgroups the GPU holds at once
+  v[5 + kNumBins] = c->chain.redo_cap;  // 3/4 of the redo's full-build workgroups the GPU holds at once
   v[6 + kNumBins] = 1;            // every store may speculate (the redo by teams has no bound)
   v[7 + kNumBins] = c->order.aux_own_queue ? 1 : 0;  // the work classes' streams each have a hardware queue
   int64_t parts = 1;  // the stream parts of the store's one workgroup bin (dm_ctx::kParts), else 1

@@ -259,7 +259,7 @@ static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S
   const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
   const bool sub32 = b->upsert_subclients32 != nullptr;
   if (nu > 0) c->expl_rows = true;  // arrivals take explicit expiries
-  if (nu > 0 || nr > 0) c->chain_live_ok = false;  // subclients words written, rows released
+  if (nu > 0 || nr > 0) c->chain.rows_written();  // subclients words written, rows released
   if (!we) c->rows_changed();  // (wants refreshes too: a NaN wants ends a resource's dense state)
   const KeyClear* kc = we ? we->keys() : nullptr;
   S.nu = nu;

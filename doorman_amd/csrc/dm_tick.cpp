@@ -7,6 +7,9 @@
 // SplitSlot): it reads the slot's host-mapped words, asks dm_split_form.h for the form of
 // this tick's launches (try_split, choose_form: the one place the forms and the key rule
 // are written), and hands the form to launch_dense_form, launch_rest or launch_mixed.
+// The large-resource chain (Tick::large_chain) works on its owner (dm_large_chain.h
+// LargeChain): Tick::outputs asks dm_large_form.h once for the tick's output column and the
+// chain's form (choose_large), and large_chain launches the form's phases in order.
 #include <ctime>
 
 #include "dm_ctx.h"
@@ -153,13 +156,11 @@ struct Tick {
   uint32_t flags;
   bool wb = false, pingpong = false;
   DevParams p{};
-  Partials P{};
+  LargeForm lf;  // the output column and the chain's form (dm_large_form.h), chosen in outputs()
   hipStream_t st = nullptr, s_large = nullptr, s_small = nullptr;
   int nch = 0;
   int32_t *gl = nullptr, *gc = nullptr;  // k_general's worklist and its count
   bool general = false, fork = false, one_class = false;
-  bool live_ok = false;
-  bool chain_live = false;  // this tick ran the (non-heterogeneous) chain
 
   template <typename F>
   hipError_t timed(int cls, hipStream_t s, F&& fn) {
@@ -204,7 +205,7 @@ int Tick::outputs() {
   // gets store of every 64-row run the tick leaves unchanged (dm_tick_group.hip
   // group_segment: a third of a quiescent resource's bytes).  It writes the alternate
   // column, which becomes the store's has after the tick, when the caller asks for it,
-  // when it may take the speculative large chain (below), and on a store beyond the
+  // when it may take the speculative large chain (dm_large_form.h), and on a store beyond the
   // Infinity Cache whose rows a call has written since the last writeback tick (the row
   // epoch): such a tick has little to skip, and separate columns stream ~2 % faster than
   // reading and writing the same lines (C3 without the skip 427 against 435 us, C4's
@@ -213,14 +214,27 @@ int Tick::outputs() {
   // c->has is complete.
   if ((flags & DM_WB_INPLACE) && (flags & DM_WB_ALTERNATE))
     return c->fail(DM_E_INVAL, "DM_WB_INPLACE and DM_WB_ALTERNATE are exclusive");
-  // The speculative large chain (below) writes its gets before they are verified, so a
-  // tick that may take it writes the alternate column whatever the store's size.
-  const bool spec_eligible = c->spec_chain && wb && !(flags & DM_AGG_RECOMPUTE) && !c->expl_rows &&
-                             !((c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0) &&
-                             !c->h_chunks.empty();
-  const bool stream_written = c->N * 48 > kStreamBytes && c->wb_epoch != c->row_epoch;
-  pingpong = wb && !(flags & DM_WB_INPLACE) &&
-             ((flags & DM_WB_ALTERNATE) || spec_eligible || stream_written);
+  // (an asynchronous store batch still in flight may bring NaN wants or other subclient
+  // counts: the tick is ready for k_general until the batch is retired)
+  general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
+  nch = (int)c->h_chunks.size();
+  LargeChain& lc = c->chain;
+  LargeInputs in;
+  in.spec_chain = lc.spec_chain;
+  in.writeback = wb;
+  in.recompute = (flags & DM_AGG_RECOMPUTE) != 0;
+  in.inplace = (flags & DM_WB_INPLACE) != 0;
+  in.alternate = (flags & DM_WB_ALTERNATE) != 0;
+  in.expl_rows = c->expl_rows;
+  in.may_general = general;
+  in.nchunks = nch;
+  in.live_ok = lc.live_ok;
+  in.stream_written = c->N * 48 > kStreamBytes && c->wb_epoch != c->row_epoch;
+  in.redo_light = lc.redo_light;
+  in.same_write_epoch = lc.redo_epoch == c->write_epoch;
+  lf = choose_large(in);
+  lc.live_ok = false;
+  pingpong = lf.pingpong;
   if (wb) {
     c->wb_inplace = pingpong ? 0 : 1;  // dm_plan_info slot 19
     c->wb_epoch = c->row_epoch;
@@ -253,8 +267,6 @@ int Tick::outputs() {
   }
   p.now = now_ns;
   p.recompute = (flags & DM_AGG_RECOMPUTE) ? 1 : 0;
-  live_ok = c->chain_live_ok;
-  c->chain_live_ok = false;
   if (wb && !c->pub_ring.empty()) {
     const int64_t n = (int64_t)c->pub_ring.size();
     p.pub = c->pub_ring[(size_t)(c->pub_k % n)];
@@ -267,17 +279,9 @@ int Tick::outputs() {
 }
 
 int Tick::streams() {
-  P = Partials{c->pa_cnt.p, c->pa_has.p, c->pa_wants.p, c->pa_cnt_all.p, c->pa_has_all.p, c->pa_wants_all.p,
-               c->pa_smin.p, c->pa_smax.p, c->pa_nan.p,
-               c->pb_x.p,   c->pb_y.p,   c->pb_w.p,     c->pc_ee.p,   c->pc_sgt.p,  c->pd_delta.p,
-               c->pa_live.p, c->p_tot.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   st = c->stream;
-  nch = (int)c->h_chunks.size();
   gl = c->glist.p;
   gc = c->gcount.p;
-  // (an asynchronous store batch still in flight may bring NaN wants or other subclient
-  // counts: the tick is ready for k_general until the batch is retired)
-  general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
   if (general) {  // only non-small resources are ever appended to the worklist
     DM_HIP(c, hipMemsetAsync(gc, 0, sizeof(int32_t), st), "worklist reset");
     c->order.main_has_work();
@@ -314,67 +318,28 @@ int Tick::streams() {
 }
 
 int Tick::large_chain() {
+  if (lf.n == 0) return DM_OK;
+  LargeChain& lc = c->chain;
   const int nls = (int)c->h_large.size();
+  LargeArgs a{c->chunks.p, c->large.p, lc.partials(), SpecArgs{}, gl, gc};
   // heterogeneous-subclient FairShare is decided on the chain when the store may
   // hold it (k_large_t, k_large_c_het, k_large_e, k_large_map_het)
-  const bool het = general && nch > 0;
-  if (het) {
-    const size_t nc = (size_t)nch, nl = (size_t)std::max(nls, 1);
-    if (c->ph_set_ready < nl || c->ph_set.n < nl * 2 * kHetMaxS) {
-      DM_HIP(c, c->ph_set.ensure(nl * 2 * kHetMaxS), "heterogeneous partials");
-      DM_HIP(c, c->ph_n.ensure(nl), "heterogeneous partials");
-      DM_HIP(c, hipMemsetAsync(c->ph_set.p, 0xFF, nl * 2 * kHetMaxS * sizeof(uint32_t), s_large), "heterogeneous sets");
-      DM_HIP(c, hipMemsetAsync(c->ph_n.p, 0, nl * sizeof(int32_t), s_large), "heterogeneous sets");
-      c->ph_set_ready = nl;
-    }
-    DM_HIP(c, c->ph_het.ensure(nl * sizeof(HetRes)), "heterogeneous partials");
-    DM_HIP(c, c->ph_bkw.ensure(nc * kHetBuckets), "heterogeneous partials");
-    DM_HIP(c, c->ph_bks.ensure(nc * kHetBuckets), "heterogeneous partials");
-    DM_HIP(c, c->ph_bkc.ensure(nc * kHetBuckets), "heterogeneous partials");
-    P.s_set = c->ph_set.p;
-    P.s_n = c->ph_n.p;
-    P.het = c->ph_het.p;
-    P.bk_w = c->ph_bkw.p;
-    P.bk_s = c->ph_bks.p;
-    P.bk_c = c->ph_bkc.p;
-  }
-  P.b_first = (!het && !p.recompute && !c->expl_rows) ? 1 : 0;
-  P.s_live = (!het && live_ok && !c->expl_rows) ? 1 : 0;
-  P.uni = c->p_uni.p;
-  // A, B, [T], C, [C_het, E], map, [map_het], fin
-  static constexpr int kSeq[9] = {0, 1, 5, 2, 6, 7, 3, 8, 4};
-  static constexpr int kCls[9] = {KC_LARGE_A, KC_LARGE_B,   KC_LARGE_T,  KC_LARGE_C,  KC_LARGE_CH,
-                                  KC_LARGE_E, KC_LARGE_MAP, KC_LARGE_MH, KC_LARGE_FIN};
+  if (lf.het) DM_HIP(c, lc.with_het(a.P, nls, nch, s_large), "heterogeneous partials");
+  a.P.b_first = lf.b_first ? 1 : 0;
+  a.P.s_live = lf.s_live ? 1 : 0;
   // the steady state: one speculative launch, verified per resource, and a redo launch
-  // that only the resources whose totals moved use (the store's rows must not be
-  // overwritten by the speculative gets: alternate output columns)
-  const bool spec = c->spec_chain && !het && P.b_first && wb && p.out_gets != p.has && nch > 0;
-  if (spec) {
-    const SpecArgs S{c->p_spec.p, c->spec_seq, c->h_serr.d, c->p_spec_ring.p, (int)(c->spec_seq & 1), nch,
-                     reinterpret_cast<uint32_t*>(c->h_serr.d + 1), c->p_team.p, c->nslots};
-    c->spec_seq += 1;
-    const bool light = c->redo_light == 2 || (c->redo_light == 1 && c->redo_epoch == c->write_epoch &&
-                                              __atomic_exchange_n(c->h_serr.p + 1, 0, __ATOMIC_RELAXED) == 0);
-    c->redo_epoch = c->write_epoch;
-    const int redo_phase = light ? 2 : 1;
-    const int redo_grid = light ? c->team_grid_light : c->team_grid_full;
-    for (int ph = 0; ph < 2; ++ph)
-      DM_HIP(c, timed(ph == 0 ? KC_LARGE_SPEC : KC_LARGE_REDO, s_large,
-                      [&] {
-                        return launch_large_spec(ph == 0 ? 0 : redo_phase, p, c->chunks.p, nch, c->large.p, P, S,
-                                                 redo_grid, gl, gc, s_large);
-                      }),
-             "large-resource kernels");
+  // that only the resources whose totals moved use
+  if (lf.spec) {
+    a.S = lc.spec_args(nch);
+    if (lf.ask_seen && lc.take_seen()) lf.seen();
+    lc.redo_epoch = c->write_epoch;
   }
-  for (int i = 0; i < 9 && nch > 0 && !spec; ++i) {
-    const int ph = kSeq[i];
-    if (ph >= 5 && !het) continue;
-    if (ph == 4 && !het) continue;  // the map's last-arriving chunks did fin's work
-    DM_HIP(c, timed(kCls[i], s_large,
-                    [&] { return launch_large(ph, p, c->chunks.p, nch, c->large.p, nls, P, gl, gc, s_large); }),
+  for (int i = 0; i < lf.n; ++i) {
+    const LargePhase ph = lf.seq[i];
+    DM_HIP(c, timed(kLargePhaseRows[(int)ph].cls, s_large,
+                    [&] { return launch_large(ph, lc.grid(ph, nch, nls, lf.b_first), p, a, s_large); }),
            "large-resource kernels");
   }
-  chain_live = nch > 0 && !het;
   return DM_OK;
 }
 
@@ -525,7 +490,7 @@ int Tick::finish() {
   c->have_result = true;
   if (wb) c->hints_set = true;
   if (wb) c->expl_rows = false;
-  c->chain_live_ok = wb && chain_live;
+  c->chain.live_ok = lf.leaves_live;
   if (!(flags & DM_ASYNC)) {
     const int rc = c->synced("tick");
     c->collect_profile();

@@ -262,6 +262,66 @@ __device__ void chunk_s_insert(const Partials& P, int lseg, const ChunkRows& rw,
     if (set[i] != kHetEmpty) het_insert_global(gset, gn, set[i]);
 }
 
+// A chunk's sums over its rows in registers, stated once for the chain (k_large_a/b/c), the
+// speculative launch and the redo (k ascending in every thread: one order, the same bits).
+// Pass A (Clean sums of the rows it releases, the live rows' count range, NaN wants) and
+// round 1 with equalShare eq
+__device__ __forceinline__ AggA chunk_a(const ChunkRows& rw) {
+  AggA a = zeroA();
+#pragma unroll
+  for (int k = 0; k < kLR; ++k) {
+    if (!(rw.valid >> k & 1)) continue;
+    if (!(rw.live >> k & 1)) {
+      a.cnt += rw.s[k];
+      a.h += rw.h[k];
+      a.w += rw.w[k];
+    } else {
+      a.smin = rw.s[k] < a.smin ? rw.s[k] : a.smin;
+      a.smax = rw.s[k] > a.smax ? rw.s[k] : a.smax;
+      a.nan |= __builtin_isnan(rw.w[k]) ? 1 : 0;
+    }
+  }
+  return a;
+}
+__device__ __forceinline__ AggB chunk_b(const ChunkRows& rw, int kind, double eq) {
+  AggB b{0.0, 0.0, 0};
+#pragma unroll
+  for (int k = 0; k < kLR; ++k) {
+    if (!(rw.live >> k & 1)) continue;
+    const double w = rw.w[k];
+    const int sk = rw.s[k];
+    if (kind == 2) {
+      const double e = eq * (double)sk;  // algorithm.go:273
+      if (w < e)
+        b.x += e - w;
+      else
+        b.y += w - e;
+    } else {
+      const double d = (double)sk * eq;  // algorithm.go:160
+      if (w < d)
+        b.x += d - w;
+      else if (w > d)
+        b.i += sk;
+    }
+  }
+  return b;
+}
+// round 2 at threshold Tu over the live rows, every one holding s0 (k_large_c)
+__device__ __forceinline__ AggC chunk_c(const ChunkRows& rw, int s0, double eq, double Tu) {
+  AggC x{0.0, 0};
+#pragma unroll
+  for (int k = 0; k < kLR; ++k) {
+    if (!(rw.live >> k & 1)) continue;
+    const double w = rw.w[k];
+    if (!(w > (double)s0 * eq)) continue;
+    if (w < Tu)
+      x.ee += Tu - w;
+    else if (w > Tu)
+      x.sgt += s0;
+  }
+  return x;
+}
+
 __global__ __launch_bounds__(256) void k_large_a(DevParams p, const Chunk* __restrict__ chunks, Partials P) {
   __shared__ Lds<256> lds;
   const Chunk ch = chunks[blockIdx.x];
@@ -272,25 +332,14 @@ __global__ __launch_bounds__(256) void k_large_a(DevParams p, const Chunk* __res
     const uint32_t prev_live = P.s_live ? P.live[(size_t)blockIdx.x * 256 + threadIdx.x] : 0u;
     load_chunk(p, ch, rw, rs, uni, prev_live);
   }
-  AggA a = zeroA();
+  AggA a = chunk_a(rw);
+  if (p.recompute) {  // every row's sums
 #pragma unroll
-  for (int k = 0; k < kLR; ++k) {
-    if (!(rw.valid >> k & 1)) continue;
-    const bool lv = rw.live >> k & 1;
-    if (!lv) {
-      a.cnt += rw.s[k];
-      a.h += rw.h[k];
-      a.w += rw.w[k];
-    }
-    if (p.recompute) {
+    for (int k = 0; k < kLR; ++k) {
+      if (!(rw.valid >> k & 1)) continue;
       a.all.cnt += rw.s[k];
       a.all.h += rw.h[k];
       a.all.w += rw.w[k];
-    }
-    if (lv) {
-      a.smin = rw.s[k] < a.smin ? rw.s[k] : a.smin;
-      a.smax = rw.s[k] > a.smax ? rw.s[k] : a.smax;
-      a.nan |= __builtin_isnan(rw.w[k]) ? 1 : 0;
     }
   }
   P.live[(size_t)blockIdx.x * 256 + threadIdx.x] = rw.live | rw.expl << 8 | rw.rel << 16;
@@ -301,28 +350,7 @@ __global__ __launch_bounds__(256) void k_large_a(DevParams p, const Chunk* __res
   // otherwise.  Saves pass B's row reads (12 B per lease) in the steady state.
   const bool spec = !p.recompute && !rs.learning && rs.kind >= 2;
   AggB b{0.0, 0.0, 0};
-  if (spec) {
-    const double eq = rs.C / (double)rs.agg_count;
-#pragma unroll
-    for (int k = 0; k < kLR; ++k) {
-      if (!(rw.live >> k & 1)) continue;
-      const double w = rw.w[k];
-      const int sk = rw.s[k];
-      if (rs.kind == 2) {
-        const double e = eq * (double)sk;  // algorithm.go:273
-        if (w < e)
-          b.x += e - w;
-        else
-          b.y += w - e;
-      } else {
-        const double d = (double)sk * eq;  // algorithm.go:160
-        if (w < d)
-          b.x += d - w;
-        else if (w > d)
-          b.i += sk;
-      }
-    }
-  }
+  if (spec) b = chunk_b(rw, rs.kind, rs.C / (double)rs.agg_count);
   {
     const AggR all_part = a.all;
     if (P.s_set)  // every thread reads the chunk's count range (chunk_s_insert)
@@ -390,27 +418,7 @@ __global__ __launch_bounds__(256) void k_large_b(DevParams p, const Chunk* __res
 #pragma unroll
     for (int k = 0; k < kLR; ++k) rw.s[k] = st.a.smin;
   }
-  AggB b{0.0, 0.0, 0};
-#pragma unroll
-  for (int k = 0; k < kLR; ++k) {
-    if (!(rw.live >> k & 1)) continue;
-    const double w = rw.w[k];
-    const int s = rw.s[k];
-    if (st.rs.kind == 2) {
-      const double e = eq * (double)s;
-      if (w < e)
-        b.x += e - w;
-      else
-        b.y += w - e;
-    } else {
-      const double d = (double)s * eq;
-      if (w < d)
-        b.x += d - w;
-      else if (w > d)
-        b.i += s;
-    }
-  }
-  b = group_reduce_t0<256>(b, OpB(), lds.b);
+  const AggB b = group_reduce_t0<256>(chunk_b(rw, st.rs.kind, eq), OpB(), lds.b);
   if (threadIdx.x == 0) {
     P.b_x[blockIdx.x] = b.x;
     P.b_y[blockIdx.x] = b.y;
@@ -431,27 +439,13 @@ __global__ __launch_bounds__(256) void k_large_c(DevParams p, const Chunk* __res
   const LargeSeg L = ls[ch.lseg];
   const SegState st = seg_state_of(p, L.seg, seg_tot(P, ch.lseg)->a);  // left by pass B
   if (st.general || st.rs.learning || st.rs.kind != 3) return;
-#pragma unroll
-  for (int k = 0; k < kLR; ++k) rw.s[k] = st.a.smin;  // uniform subclients here
   const bool spec_ok = !p.recompute && seg_tot(P, ch.lseg)->rel == 0;  // pass B's first chunk left b
   const AggB b = spec_ok ? seg_tot(P, ch.lseg)->b : seg_b<256>(P, L, lds);
   if (threadIdx.x == 0 && !spec_ok && (int)blockIdx.x == L.chunk_begin) seg_tot(P, ch.lseg)->b = b;
   const double eq = st.rs.C / (double)st.cl.count;
-  const double s0 = (double)st.a.smin;
+  const double s0 = (double)st.a.smin;  // uniform subclients here
   const double Tu = (b.x / (double)b.i) * s0 + eq * s0;
-  AggC c{0.0, 0};
-#pragma unroll
-  for (int k = 0; k < kLR; ++k) {
-    if (!(rw.live >> k & 1)) continue;
-    const double w = rw.w[k];
-    const int s = rw.s[k];
-    if (!(w > (double)s * eq)) continue;
-    if (w < Tu)
-      c.ee += Tu - w;
-    else if (w > Tu)
-      c.sgt += s;
-  }
-  c = group_reduce_t0<256>(c, OpC(), lds.c);
+  const AggC c = group_reduce_t0<256>(chunk_c(rw, st.a.smin, eq, Tu), OpC(), lds.c);
   if (threadIdx.x == 0) {
     P.c_ee[blockIdx.x] = c.ee;
     P.c_sgt[blockIdx.x] = c.sgt;
@@ -619,18 +613,6 @@ __device__ __forceinline__ T canon_reduce(int begin, int end, T v, Op op, Ld ld)
   for (int q = begin + (int)(threadIdx.x & 63); q < end; q += 64) v = op(v, ld(q));
   return wave_reduce(v, op);
 }
-__device__ __forceinline__ AggA canon_a(const Partials& P, const LargeSeg& L) {
-  return canon_reduce(L.chunk_begin, L.chunk_end, zeroA(), OpA(), [&](int q) {
-    AggA x = zeroA();
-    x.cnt = ld_wt(P.a_cnt + q);
-    x.h = ld_wt(P.a_has + q);
-    x.w = ld_wt(P.a_wants + q);
-    x.smin = (int)ld_wt(P.a_smin + q);
-    x.smax = (int)ld_wt(P.a_smax + q);
-    x.nan = ld_wt(P.a_nan + q);
-    return x;
-  });
-}
 __device__ __forceinline__ AggB canon_b(const Partials& P, const LargeSeg& L) {
   return canon_reduce(L.chunk_begin, L.chunk_end, AggB{0.0, 0.0, 0}, OpB(),
                       [&](int q) { return AggB{ld_wt(P.b_x + q), ld_wt(P.b_y + q), ld_wt(P.b_w + q)}; });
@@ -643,7 +625,7 @@ __device__ __forceinline__ double canon_d(const Partials& P, const LargeSeg& L) 
   return canon_reduce(L.chunk_begin, L.chunk_end, SumD{0.0}, OpSumD(),
                       [&](int q) { return SumD{ld_wt(P.d_delta + q)}; }).v;
 }
-// canon_a, canon_b, canon_c and canon_d in one pass over the chunks (k_large_spec's
+// pass A's totals, canon_b, canon_c and canon_d in one pass over the chunks (k_large_spec's
 // verifier): every partial of a 64-chunk stripe loaded at once, one round trip per
 // stripe instead of four; each quantity keeps its own order and tree (the same bits)
 struct CanonAll {
@@ -674,64 +656,6 @@ __device__ __forceinline__ CanonAll canon_all(const Partials& P, const LargeSeg&
     d = OpSumD()(d, u);
   }
   return CanonAll{wave_reduce(a, OpA()), wave_reduce(b, OpB()), wave_reduce(c, OpC()), wave_reduce(d, OpSumD()).v};
-}
-
-// pass A (Clean sums of the rows it releases, the live rows' count range, NaN wants)
-// and round 1 with equalShare eq over the chunk's rows in registers (as k_large_a)
-__device__ __forceinline__ AggA chunk_a(const ChunkRows& rw) {
-  AggA a = zeroA();
-#pragma unroll
-  for (int k = 0; k < kLR; ++k) {
-    if (!(rw.valid >> k & 1)) continue;
-    if (!(rw.live >> k & 1)) {
-      a.cnt += rw.s[k];
-      a.h += rw.h[k];
-      a.w += rw.w[k];
-    } else {
-      a.smin = rw.s[k] < a.smin ? rw.s[k] : a.smin;
-      a.smax = rw.s[k] > a.smax ? rw.s[k] : a.smax;
-      a.nan |= __builtin_isnan(rw.w[k]) ? 1 : 0;
-    }
-  }
-  return a;
-}
-__device__ __forceinline__ AggB chunk_b(const ChunkRows& rw, int kind, double eq) {
-  AggB b{0.0, 0.0, 0};
-#pragma unroll
-  for (int k = 0; k < kLR; ++k) {
-    if (!(rw.live >> k & 1)) continue;
-    const double w = rw.w[k];
-    const int sk = rw.s[k];
-    if (kind == 2) {
-      const double e = eq * (double)sk;  // algorithm.go:273
-      if (w < e)
-        b.x += e - w;
-      else
-        b.y += w - e;
-    } else {
-      const double d = (double)sk * eq;  // algorithm.go:160
-      if (w < d)
-        b.x += d - w;
-      else if (w > d)
-        b.i += sk;
-    }
-  }
-  return b;
-}
-// round 2 at threshold Tu over the live rows, every one holding s0 (k_large_c)
-__device__ __forceinline__ AggC chunk_c(const ChunkRows& rw, int s0, double eq, double Tu) {
-  AggC x{0.0, 0};
-#pragma unroll
-  for (int k = 0; k < kLR; ++k) {
-    if (!(rw.live >> k & 1)) continue;
-    const double w = rw.w[k];
-    if (!(w > (double)s0 * eq)) continue;
-    if (w < Tu)
-      x.ee += Tu - w;
-    else if (w > Tu)
-      x.sgt += s0;
-  }
-  return x;
 }
 
 // (at 5 waves per SIMD -- amdgpu_waves_per_eu(5): 96 VGPRs, 2 spilled -- C2 lost 105.2 ->
@@ -1317,34 +1241,28 @@ __global__ __launch_bounds__(256) void k_large_map_het(DevParams p, const Chunk*
 // --------------------------------------------------------------------------
 // host-side launchers (called by dm_tick.cpp)
 // --------------------------------------------------------------------------
-hipError_t launch_large(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls, int nls,
-                        const Partials& P, int32_t* glist, int32_t* gcount, hipStream_t st) {
-  if (nchunks <= 0) return hipSuccess;
-  switch (phase) {
-    case 5: k_large_t<<<nls, 256, 0, st>>>(p, ls, P, glist, gcount); break;
-    case 6: k_large_c_het<<<nchunks, 256, 0, st>>>(p, chunks, ls, P); break;
-    case 7: k_large_e<<<dim3(nls, (kHetBuckets + 3) / 4), 256, 0, st>>>(p, ls, P); break;
-    case 8: k_large_map_het<<<nchunks, 256, 0, st>>>(p, chunks, ls, P); break;
-    case 0: k_large_a<<<nchunks, 256, 0, st>>>(p, chunks, P); break;
-    case 1: k_large_b<<<P.b_first ? nls : nchunks, 256, 0, st>>>(p, chunks, ls, P); break;
-    case 2: k_large_c<<<nchunks, 256, 0, st>>>(p, chunks, ls, P); break;
-    case 3: k_large_map<<<nchunks, 256, 0, st>>>(p, chunks, ls, P, glist, gcount); break;
-    case 4: k_large_fin<<<nls, 256, 0, st>>>(p, ls, P, glist, gcount); break;
-    default: return hipErrorInvalidValue;
+hipError_t launch_large(LargePhase ph, dim3 grid, const DevParams& p, const LargeArgs& a, hipStream_t st) {
+  if (grid.x == 0 || grid.y == 0) return hipSuccess;
+  const Chunk* chunks = a.chunks;
+  const LargeSeg* ls = a.ls;
+  switch (ph) {
+    case LargePhase::A: k_large_a<<<grid, 256, 0, st>>>(p, chunks, a.P); break;
+    case LargePhase::B: k_large_b<<<grid, 256, 0, st>>>(p, chunks, ls, a.P); break;
+    case LargePhase::T: k_large_t<<<grid, 256, 0, st>>>(p, ls, a.P, a.glist, a.gcount); break;
+    case LargePhase::C: k_large_c<<<grid, 256, 0, st>>>(p, chunks, ls, a.P); break;
+    case LargePhase::C_HET: k_large_c_het<<<grid, 256, 0, st>>>(p, chunks, ls, a.P); break;
+    case LargePhase::E: k_large_e<<<grid, 256, 0, st>>>(p, ls, a.P); break;
+    case LargePhase::MAP: k_large_map<<<grid, 256, 0, st>>>(p, chunks, ls, a.P, a.glist, a.gcount); break;
+    case LargePhase::MAP_HET: k_large_map_het<<<grid, 256, 0, st>>>(p, chunks, ls, a.P); break;
+    case LargePhase::FIN: k_large_fin<<<grid, 256, 0, st>>>(p, ls, a.P, a.glist, a.gcount); break;
+    case LargePhase::SPEC: k_large_spec<<<grid, 256, 0, st>>>(p, chunks, ls, a.P, a.S); break;
+    case LargePhase::REDO_FULL:
+      k_large_redo_team<false><<<grid, 256, 0, st>>>(p, chunks, ls, a.P, a.S, a.glist, a.gcount);
+      break;
+    case LargePhase::REDO_LIGHT:
+      k_large_redo_team<true><<<grid, 256, 0, st>>>(p, chunks, ls, a.P, a.S, a.glist, a.gcount);
+      break;
   }
-  return hipGetLastError();
-}
-
-hipError_t launch_large_spec(int phase, const DevParams& p, const Chunk* chunks, int nchunks, const LargeSeg* ls,
-                             const Partials& P, const SpecArgs& S, int redo_grid, int32_t* glist, int32_t* gcount,
-                             hipStream_t st) {
-  if (nchunks <= 0) return hipSuccess;
-  if (phase == 0)
-    k_large_spec<<<nchunks, 256, 0, st>>>(p, chunks, ls, P, S);
-  else if (phase == 1)
-    k_large_redo_team<false><<<redo_grid, 256, 0, st>>>(p, chunks, ls, P, S, glist, gcount);
-  else
-    k_large_redo_team<true><<<redo_grid, 256, 0, st>>>(p, chunks, ls, P, S, glist, gcount);
   return hipGetLastError();
 }
 

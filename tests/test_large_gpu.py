@@ -349,6 +349,51 @@ def test_speculative_chain_against_the_chain_and_the_oracle(monkeypatch, redo):
         spec.close()
 
 
+def test_inplace_tick_runs_the_chain_and_the_next_tick_speculates():
+    """The output column and the chain's form are one decision (dm_large_form.h): a writeback
+    tick told to write in place runs the four-launch chain and never the speculative launch,
+    whose unverified gets would land on the store's has column; the next tick, left to choose,
+    writes the alternate column and speculates.  Two large resources (4097 and 6144 rows: a
+    1-row tail chunk, an exact multiple), ProportionalShare and FairShare, no explicit expiry
+    left after the first writeback tick; every tick against the oracle on the store as it
+    stood before it."""
+    rng = np.random.default_rng(7171)
+    sizes = np.asarray([4097, 6144], dtype=np.int64)
+    snap = snapshot_with_sizes(rng, sizes, kinds=(2, 3), expired_frac=0.01, learning_frac=0.0,
+                               parent_expired_frac=0.0)
+    snap["kind"][:] = [W.PROPORTIONAL_SHARE, W.FAIR_SHARE]
+    snap["learning_end_ns"][:] = W.INT64_MIN
+    snap["lease_length_s"][:] = 600
+    chain = ("large_a", "large_b", "large_c", "large_map")
+    eng = _engine()
+    try:
+        eng.load(snap)
+        eng.set_profiling(True)
+        now = NOW
+        for cols, inplace in (("auto", None), ("inplace", 1), ("auto", 0)):
+            now += W.NS
+            cur = _store_as_snapshot(snap, eng)
+            ref = O.apportion(cur, now)
+            eng.reset_kernel_times()
+            eng.apportion(now, writeback=True, wb_columns=cols)
+            launches = {k: v[0] for k, v in eng.kernel_times().items() if v[0]}
+            if inplace is None:  # the loaded rows carry explicit expiries: the chain, whatever the column
+                assert all(launches.get(k) == 1 for k in chain) and "large_spec" not in launches, launches
+            elif inplace:
+                assert all(launches.get(k) == 1 for k in chain), launches
+                assert "large_spec" not in launches and "large_redo" not in launches, launches
+            else:
+                assert launches.get("large_spec") == 1 and launches.get("large_redo") == 1, launches
+                assert "large_a" not in launches, launches
+            if inplace is not None:
+                assert eng.plan_info()["wb_inplace"] == inplace
+            gets, exp = eng.leases()
+            assert_leases_match(cur, gets, exp, ref, f"{cols} tick")
+            assert_resources_match(cur, eng.resources(), ref, f"{cols} tick")
+    finally:
+        eng.close()
+
+
 def test_resource_beyond_the_co_resident_redo_workgroups():
     """A resource with more chunks than 3/4 of the redo workgroups the GPU holds at once
     (plan_info redo_resident_cap: the bound round 4's per-chunk redo had, every chunk of a
