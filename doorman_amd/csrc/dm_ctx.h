@@ -3,7 +3,9 @@
 // types that own its device memory, pinned host memory and events, the four owners of its
 // cross-stream order (StreamOrder, TickDone, TemplatePipe, QueueCalibration: they carry out
 // what dm_tick_order.h decides), the large-resource chain's owner (dm_large_chain.h), the
-// entry macros of the C-ABI calls, and the functions that cross a unit boundary.  The only definition of
+// store updates' staging (dm_update_stage.h: UpdateStage, RowBitmap; what their flags mean:
+// dm_update_outcome.h), the entry macros of the C-ABI calls, and the functions that cross a
+// unit boundary.  The only definition of
 // dm_ctx; the units around it are dm_runtime.cpp (context life, streams, profiling),
 // dm_plan.cpp, dm_tick.cpp, dm_decide.cpp, dm_store.cpp, dm_store_update.cpp and
 // dm_hier_host.cpp.  See DESIGN.md §3-§5.
@@ -434,6 +436,7 @@ struct QueueCalibration {
 }  // namespace dm
 
 #include "dm_large_chain.h"
+#include "dm_update_stage.h"
 
 using namespace dm;
 
@@ -463,7 +466,6 @@ struct dm_ctx {
   int class_stream[kNumBins + 2] = {2, 2, 2, 2, 1, 1, 1, 2, 2, 3, 0};
   int64_t h_shape_lo[kSubShapes] = {}, h_shape_n[kSubShapes] = {};  // sub-wave shapes' items within their bins
   hipStream_t cpy = nullptr;  // store-update column copies (overlap a running tick)
-  Event ev_stage[2];  // staged update copies -> per-chunk validation
   std::string err;
 
   int64_t R = 0, N = 0;
@@ -613,6 +615,8 @@ struct dm_ctx {
   int fixed_ok = 1;
   DBuf<FixKey> fix_keys[kSplitBins];
   DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
+  // the update launchers' view of the store's columns (dm_launch.h StoreCols)
+  StoreCols store_cols() const { return {row_index(), has.p, wants.p, sub.p, expiry.p, agg.p, expl.p, cfg.p}; }
   // the key-clearing refresh and update kernels' view of the keys (dm_device.h KeyClear)
   KeyClear key_clear() const {
     KeyClear k{};
@@ -668,40 +672,15 @@ struct dm_ctx {
   bool maybe_general = false;
   bool all_sub_one = true;  // every loaded row had subclients == 1
   int64_t n_nonsmall = 0;
-  // staging for upsert / release
-  DBuf<int64_t> st_rows, st_sub, st_exp;
-  DBuf<double> st_has, st_wants;
-  DBuf<uint64_t> st_mask;  // dm_store_update_wants_mask
-  DBuf<int64_t> st_blk;
-  DBuf<int32_t> st_wpre;
-  static constexpr int kWChunks = 4;  // dm_store_apply: the refresh values' copy chunks
-  // One round's staging (dm_store_apply): set 0 for the synchronous call, sets 1..
-  // kAsyncSets for dm_store_apply_async, whose batch k uses set 1 + k % kAsyncSets and is
-  // retired (its flags read) before batch k + kAsyncSets reuses the set.
-  struct ApplySet {
-    DBuf<uint64_t> mask;
-    DBuf<double> mwants;  // the refresh part's values
-    DBuf<int64_t> blk;
-    DBuf<int32_t> wpre;
-    DBuf<int64_t> rel;  // the departures' rows
-    DBuf<int64_t> rows, sub, exp;
-    DBuf<double> has, wants;
-    DBuf<uint32_t> flags;  // one flags word per part
-    HBuf<uint32_t> h_flags;  // its pinned host mirror
-    Event ev_bat[3];
-    Event ev_wchunk[kWChunks];
-    Event ev_done;  // (asynchronous sets) the batch's last kernel and flags copy
-    bool pending = false;      // enqueued, not yet retired
-    bool may_general = false;  // its refresh or arrivals may bring NaN wants / other subclient counts
-    int64_t nu = 0;
-  };
-  static constexpr int kAsyncSets = 2;
-  ApplySet aset[1 + kAsyncSets];
+  // the staging of the store updates and the device-resolving reads (dm_update_stage.h):
+  // set 0 for every call that is synchronous on return, the rest for dm_store_apply_async
+  UpdateStage stage[1 + kAsyncSets];
+  RowBitmap row_bits;
   int64_t async_seq = 0;  // asynchronous batches enqueued
   // a tick enqueued while an asynchronous batch that may make the store general is in flight
   bool async_may_general() const {
     for (int i = 1; i <= kAsyncSets; ++i)
-      if (aset[i].pending && aset[i].may_general) return true;
+      if (stage[i].pending && stage[i].may_general) return true;
     return false;
   }
   // dm_store_relayout: the rejection flags and the first rejected resource, compact mode's
@@ -716,8 +695,6 @@ struct dm_ctx {
   DBuf<int64_t> cl_blk_pre, cl_blk_min, cl_list;
   bool cl_valid = false;
   int64_t cl_n = 0;
-  DBuf<uint32_t> row_bits;    // device row bitmap for the uniqueness check, all-zero between calls
-  DBuf<uint32_t> upd_flags;    // k_check_rows result (device)
   // dm_decide: a round's requests (grouped by resource), per-resource work items, results
   DBuf<int64_t> rq_rows, rq_sub, rq_exp;
   DBuf<double> rq_has, rq_wants, rq_gets;
@@ -767,7 +744,6 @@ struct dm_ctx {
     if (j == 0) return class_stream[b];
     return class_stream[b] != 2 ? 2 : 0;
   }
-  HBuf<uint32_t> h_flags;  // pinned host mirror of upd_flags
   // profiling
   bool profiling = false;
   std::vector<ProfEvent> pending;

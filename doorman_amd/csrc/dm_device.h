@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "dm_update_outcome.h"
+
 namespace dm {
 
 constexpr int64_t kReleased = INT64_MIN;
@@ -257,14 +259,7 @@ struct RowIndex {
   int64_t R;
 };
 
-// store-update validation flags (k_check_rows)
-constexpr uint32_t kUpdRange = 1u;   // row outside [0, N)
-constexpr uint32_t kUpdDup = 2u;     // row twice in one call
-constexpr uint32_t kUpdSub = 4u;     // subclients outside [0, kSubMax]
-constexpr uint32_t kUpdNaN = 8u;     // NaN wants (FairShare then needs k_general)
-constexpr uint32_t kUpdNotOne = 16u; // subclients != 1 (may make a resource heterogeneous)
-constexpr uint32_t kUpdCount = 32u;  // packed values != set bits of the row mask
-constexpr uint32_t kUpdReject = kUpdRange | kUpdDup | kUpdSub | kUpdCount;
+// (the store-update validation flags, kUpd*: dm_update_outcome.h)
 
 // Per-resource configuration, AoS (one scalar burst per resource).
 struct ResCfg {  // what every tick reads: 32 B

@@ -62,14 +62,24 @@ hipError_t launch_large(LargePhase ph, dim3 grid, const DevParams& p, const Larg
 hipError_t launch_general(const DevParams& p, const int32_t* glist, const int32_t* gcount, int blocks,
                           hipStream_t st);
 // dm_update.hip
+// The store's columns as the update launchers take them (dm_ctx::store_cols builds it).
+// Host-side only: each launcher unpacks it into its kernel's own arguments.
+struct StoreCols {
+  RowIndex ix;
+  double *has, *wants;
+  int32_t* sub;
+  int64_t* expiry;
+  ResAgg* agg;
+  uint8_t* expl;
+  const ResCfg* cfg;
+};
+// kc (the upsert, release and refresh launchers): null launches the plain kernel; else its
+// key-clearing build (dm_row_epoch.h row_write_start_mode says when)
 hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
-                         const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
-                         const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
-                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st,
-                         const KeyClear* kc = nullptr);
-hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
-                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du,
-                          hipStream_t st, const KeyClear* kc = nullptr);
+                         const int32_t* sub32, const int64_t* expiry, int64_t now, const StoreCols& s,
+                         const uint32_t* flags, const DenseUpd& du, const KeyClear* kc, hipStream_t st);
+hipError_t launch_release(int64_t n, const int64_t* rows, const StoreCols& s, const uint32_t* flags,
+                          const DenseUpd& du, const KeyClear* kc, hipStream_t st);
 hipError_t launch_check_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, const double* wants,
                              const int64_t* sub, const int32_t* sub32, uint32_t* flags, hipStream_t st);
 hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t* bitmap, hipStream_t st);
@@ -78,16 +88,13 @@ hipError_t launch_resolve_rows(int64_t n, const int64_t* rows, int64_t off, cons
                                hipStream_t st);
 hipError_t launch_gather_leases(int64_t n, const int64_t* rows, const double* gets, const int64_t* expiry,
                                double* out_gets, int64_t* out_exp, hipStream_t st);
-// kc (the upsert, release and refresh launchers): null launches the plain kernel; else its
-// key-clearing build (dm_row_epoch.h row_write_start_mode says when)
-hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
-                               const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
-                               const KeyClear* kc, hipStream_t st);
+hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const StoreCols& s,
+                               const uint32_t* flags, const KeyClear* kc, hipStream_t st);
+// phase 0: the mask's count and scan; 1: the apply of the values [vlo, vhi); 2: both
 hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
                                     int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
-                                    const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
-                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi,
-                                    const KeyClear* kc = nullptr);
+                                    const StoreCols& s, uint32_t* flags, int phase, int64_t vlo, int64_t vhi,
+                                    const KeyClear* kc, hipStream_t st);
 hipError_t launch_carry_reject(const uint32_t* from, uint32_t* to, hipStream_t st);
 // dm_hier.hip
 hipError_t launch_publish(int64_t R, const ResAgg* agg, void* dst, uint32_t* sync, hipStream_t st);

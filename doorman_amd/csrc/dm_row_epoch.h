@@ -65,7 +65,7 @@ enum class RowWrite {
 constexpr bool is_refresh(RowWrite w) { return w == RowWrite::refresh || w == RowWrite::refresh_mask; }
 
 // Before the launch.  defer: the call decides how it ends once its flags are back
-// (row_write_end); otherwise it calls rows_changed() at once, as every writer did.
+// (row_write_kept_mode); otherwise it calls rows_changed() at once, as every writer did.
 // clear_keys: launch the key-clearing build of the refresh kernel.  Only where keys are in
 // use (some part's fix_live is the row epoch): keys out of use are rewritten by the next
 // FIXED launch before any is read, so every other launch runs the plain kernels.
@@ -73,15 +73,8 @@ struct RowWriteStart {
   bool defer = false;
   bool clear_keys = false;
 };
-inline RowWriteStart row_write_start(RowWrite w, bool keep_keys, bool keys_in_use) {
-  RowWriteStart s;
-  s.defer = keep_keys && is_refresh(w);
-  s.clear_keys = s.defer && keys_in_use;
-  return s;
-}
 
-// The same for dm_keep_keys' bit set (above): what the callers ask.  With mode 0 or 1 the
-// answers are those of the two functions around it.
+// dm_keep_keys' bit set (above).
 constexpr int kKeepRefresh = 1, kKeepUpdates = 2;
 constexpr bool is_update(RowWrite w) {
   return w == RowWrite::release || w == RowWrite::upsert || w == RowWrite::apply;
@@ -95,15 +88,12 @@ inline RowWriteStart row_write_start_mode(RowWrite w, int mode, bool keys_in_use
   s.clear_keys = s.defer && keys_in_use;
   return s;
 }
-inline bool row_write_kept_mode(RowWrite w, int mode, bool rejected, bool nan) {
-  return mode_keeps(w, mode) && !rejected && !nan;
-}
 
 // After the flags are back.  rejected: the call failed or its validation refused it (the
-// apply kernel did not run); nan: kUpdNaN.  true: a kept refresh (dm_ctx::refresh_kept);
+// apply kernel did not run); nan: kUpdNaN.  true: kept (dm_ctx::refresh_kept, update_kept);
 // false: rows_changed().
-inline bool row_write_kept(RowWrite w, bool keep_keys, bool rejected, bool nan) {
-  return keep_keys && is_refresh(w) && !rejected && !nan;
+inline bool row_write_kept_mode(RowWrite w, int mode, bool rejected, bool nan) {
+  return mode_keeps(w, mode) && !rejected && !nan;
 }
 
 }  // namespace dm

@@ -188,13 +188,9 @@ int dm_create(int device, dm_ctx** out) {
   c->chain.redo_cap = (int64_t)std::max(ncu, 1) * redo_blocks_per_cu() * 3 / 4;
   if (e == hipSuccess) e = take_aux(c, ncu);
   c->stream = c->own_stream;
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = c->ev_stage[i].create(hipEventDisableTiming);
   if (e == hipSuccess) e = xs_setup(c);
-  for (auto& a : c->aset) {
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = a.ev_bat[i].create(hipEventDisableTiming);
-    for (int i = 0; i < dm_ctx::kWChunks && e == hipSuccess; ++i) e = a.ev_wchunk[i].create(hipEventDisableTiming);
-    if (e == hipSuccess) e = a.ev_done.create(hipEventDisableTiming);
-  }
+  for (UpdateStage& s : c->stage)
+    if (e == hipSuccess) e = s.create_events();
   for (int j = 0; j < dm_ctx::kParts; ++j)
     for (int i = 0; i < kTickEv && e == hipSuccess; ++i) e = c->done.ev[j][i].create(hipEventDefault);
   if (e != hipSuccess) {

@@ -162,17 +162,18 @@ int dm_config_load(dm_ctx* c, int64_t R, const dm_resource_cfg* cfg) {
 
 int dm_read_leases(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
   DM_ENTER(c);
+  UpdateStage& S = c->stage[0];  // synchronous on return: set 0 (dm_update_stage.h)
   DM_STORE_READABLE(c);
   if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
   int rc = check_range(c, off, n, c->N);
   if (rc) return rc;
   DM_HIP(c, download(gets, c->last_writeback ? c->has.p : c->out_gets.p, off, n, c->stream), "read gets");
   if (expiry_ns && c->last_writeback) {  // the store's encoding, resolved on the device
-    DM_HIP(c, c->st_exp.ensure((size_t)std::max<int64_t>(n, 1)), "stage expiry");
-    DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, c->st_exp.p,
+    DM_HIP(c, S.exp.ensure((size_t)std::max<int64_t>(n, 1)), "stage expiry");
+    DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, S.exp.p,
                                   nullptr, c->stream),
            "resolve expiry");
-    DM_HIP(c, download(expiry_ns, (const int64_t*)c->st_exp.p, 0, n, c->stream), "read expiry");
+    DM_HIP(c, download(expiry_ns, (const int64_t*)S.exp.p, 0, n, c->stream), "read expiry");
   } else {
     DM_HIP(c, download(expiry_ns, (const int64_t*)c->out_expiry.p, off, n, c->stream), "read expiry");
   }
@@ -181,6 +182,7 @@ int dm_read_leases(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* exp
 
 int dm_read_leases_rows(dm_ctx* c, int64_t n, const int64_t* rows, double* gets, int64_t* expiry_ns) {
   DM_ENTER(c);
+  UpdateStage& S = c->stage[0];  // synchronous on return: set 0 (dm_update_stage.h)
   DM_STORE_READABLE(c);
   if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
   if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad rows");
@@ -189,17 +191,17 @@ int dm_read_leases_rows(dm_ctx* c, int64_t n, const int64_t* rows, double* gets,
     if (rows[i] < 0 || rows[i] >= c->N) return c->fail(DM_E_RANGE, "row out of range");
   const double* g = c->last_writeback ? c->has.p : c->out_gets.p;
   const int64_t* e = c->last_writeback ? nullptr : c->out_expiry.p;  // the store's encoding: resolved below
-  DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
-  DM_HIP(c, c->st_has.ensure((size_t)n), "stage gets");
-  DM_HIP(c, c->st_exp.ensure((size_t)n), "stage expiry");
-  DM_HIP(c, hipMemcpyAsync(c->st_rows.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, c->stream), "stage rows");
-  DM_HIP(c, launch_gather_leases(n, c->st_rows.p, g, e, c->st_has.p, c->st_exp.p, c->stream), "gather leases");
+  DM_HIP(c, S.rows.ensure((size_t)n), "stage rows");
+  DM_HIP(c, S.has.ensure((size_t)n), "stage gets");
+  DM_HIP(c, S.exp.ensure((size_t)n), "stage expiry");
+  DM_HIP(c, hipMemcpyAsync(S.rows.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, c->stream), "stage rows");
+  DM_HIP(c, launch_gather_leases(n, S.rows.p, g, e, S.has.p, S.exp.p, c->stream), "gather leases");
   if (!e)
-    DM_HIP(c, launch_resolve_rows(n, c->st_rows.p, 0, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, c->st_exp.p,
+    DM_HIP(c, launch_resolve_rows(n, S.rows.p, 0, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, S.exp.p,
                                   nullptr, c->stream),
            "resolve expiry");
-  DM_HIP(c, download(gets, (const double*)c->st_has.p, 0, n, c->stream), "read gets");
-  DM_HIP(c, download(expiry_ns, (const int64_t*)c->st_exp.p, 0, n, c->stream), "read expiry");
+  DM_HIP(c, download(gets, (const double*)S.has.p, 0, n, c->stream), "read gets");
+  DM_HIP(c, download(expiry_ns, (const int64_t*)S.exp.p, 0, n, c->stream), "read expiry");
   return c->synced("read leases");
 }
 
@@ -290,6 +292,7 @@ int dm_read_config(dm_ctx* c, int64_t r0, int64_t n, int32_t* kind, double* capa
 
 int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
   DM_ENTER(c);
+  UpdateStage& S = c->stage[0];  // synchronous on return: set 0 (dm_update_stage.h)
   DM_STORE_READABLE(c);
   if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   int rc = check_range(c, off, n, c->N);
@@ -297,13 +300,13 @@ int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants,
   DM_HIP(c, download(has, (const double*)c->has.p, off, n, c->stream), "read has");
   DM_HIP(c, download(wants, (const double*)c->wants.p, off, n, c->stream), "read wants");
   if ((sub || exp) && n > 0) {  // subclients and expiry from the column encoding (dm_device.h)
-    DM_HIP(c, c->st_exp.ensure((size_t)n), "stage expiry");
-    DM_HIP(c, c->st_sub.ensure((size_t)n), "stage subclients");
+    DM_HIP(c, S.exp.ensure((size_t)n), "stage expiry");
+    DM_HIP(c, S.sub.ensure((size_t)n), "stage subclients");
     DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p,
-                                  exp ? c->st_exp.p : nullptr, sub ? c->st_sub.p : nullptr, c->stream),
+                                  exp ? S.exp.p : nullptr, sub ? S.sub.p : nullptr, c->stream),
            "resolve rows");
-    DM_HIP(c, download(exp, (const int64_t*)c->st_exp.p, 0, n, c->stream), "read expiry");
-    DM_HIP(c, download(sub, (const int64_t*)c->st_sub.p, 0, n, c->stream), "read subclients");
+    DM_HIP(c, download(exp, (const int64_t*)S.exp.p, 0, n, c->stream), "read expiry");
+    DM_HIP(c, download(sub, (const int64_t*)S.sub.p, 0, n, c->stream), "read subclients");
   }
   return c->synced("read store");
 }

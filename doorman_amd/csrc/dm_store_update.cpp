@@ -3,79 +3,30 @@
 // asynchronous), the re-layout and Clean on the device.
 #include "dm_ctx.h"
 
-// Rows of one upsert/release call: in range and unique (a bitmap over the table,
-// O(n + N/64)); the resource of each row is found on the device.
-// The call's columns cross PCIe in chunks on an auxiliary stream while the
-// context stream validates the chunks already there (k_check_rows: no O(n) host
-// pass, so pinned buffers from dm_host_alloc go at full DMA rate).  The apply
-// kernel then runs on the context stream; finish_update() maps the flags.
+// An update's columns are staged in an UpdateStage (dm_update_stage.h: set 0 for every call
+// that waits before it returns), validated on the device and applied on the context stream;
+// what the flags its kernels leave mean is dm_update_outcome.h's to say.  Two copy schedules:
+//   - a single call's columns cross PCIe in chunks on the copy stream while the context
+//     stream validates the chunks already there (k_check_rows: no O(n) host pass, so pinned
+//     buffers from dm_host_alloc go at full DMA rate);
+//   - a batch's parts cross back to back, each validated and applied once it has landed.
+// Neither copy waits for the context stream: the call (or, for an asynchronous batch, the
+// set's retirement) waits for its kernels before the staging is used again, so the copies
+// overlap whatever still runs there (e.g. an asynchronous tick), and each validation is
+// ordered after that work and its copy.
 struct StageCol {
   void* dst;
   const void* src;
   size_t elem;
 };
-static constexpr int64_t kStageChunk = 1 << 22;  // rows per copy/validate step
-
-// The update calls' flags word, cleared on the context stream (the first call allocates it
-// and its pinned host mirror).
-static int reset_upd_flags(dm_ctx* c) {
-  if (!c->upd_flags.p) {
-    DM_HIP(c, c->upd_flags.ensure(1), "update flags");
-    DM_HIP(c, c->h_flags.alloc(1, hipHostMallocDefault), "update flags");
-  }
-  DM_HIP(c, hipMemsetAsync(c->upd_flags.p, 0, sizeof(uint32_t), c->stream), "update flags");
-  return DM_OK;
-}
-
-static int staged_check(dm_ctx* c, int64_t n, const StageCol* cols, int ncols, bool check_wants, bool check_sub) {
-  if (!c->row_bits.p || c->row_bits.n < (size_t)(c->N / 32 + 1)) {
-    DM_HIP(c, c->row_bits.ensure((size_t)(c->N / 32 + 1)), "row bitmap");
-    DM_HIP(c, hipMemsetAsync(c->row_bits.p, 0, c->row_bits.n * sizeof(uint32_t), c->stream), "row bitmap");
-  }
-  if (int rc = reset_upd_flags(c)) return rc;
-  // Every call that reads the staging buffers (updates, dm_read_leases_rows) waits
-  // for its kernels before it returns, so the copies need not wait for the context
-  // stream: they overlap whatever is still running there (e.g. an asynchronous
-  // tick), and each chunk's validation is ordered after that work and its copy.
-  hipStream_t cp = c->cpy;
-  int k = 0;
-  for (int64_t off = 0; off < n; off += kStageChunk, ++k) {
-    const int64_t m = std::min(kStageChunk, n - off);
-    for (int j = 0; j < ncols; ++j)
-      DM_HIP(c,
-             hipMemcpyAsync((char*)cols[j].dst + off * cols[j].elem, (const char*)cols[j].src + off * cols[j].elem,
-                            (size_t)m * cols[j].elem, hipMemcpyHostToDevice, cp),
-             "stage update");
-    hipEvent_t ev = c->ev_stage[k & 1];
-    DM_HIP(c, hipEventRecord(ev, cp), "stage update");
-    DM_HIP(c, hipStreamWaitEvent(c->stream, ev, 0), "stage update");
-    DM_HIP(c, launch_check_rows(m, c->st_rows.p + off, c->N, c->row_bits.p, check_wants ? c->st_wants.p + off : nullptr,
-                                check_sub ? c->st_sub.p + off : nullptr, nullptr, c->upd_flags.p, c->stream),
-           "check rows");
-  }
-  return DM_OK;
-}
-
-// After the apply kernel: clear the bitmap, fetch the flags, wait (the call is
-// synchronous on return, so the caller may free its buffers), map errors.
-static int finish_update(dm_ctx* c, int64_t n, uint32_t* flags_out) {
-  DM_HIP(c, launch_clear_rows(n, c->st_rows.p, c->N, c->row_bits.p, c->stream), "clear rows");
-  DM_HIP(c, hipMemcpyAsync(c->h_flags.p, c->upd_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream),
-         "update flags");
-  if (int rs = c->synced("update")) return rs;
-  const uint32_t f = *c->h_flags.p;
-  *flags_out = f;
-  if (f & kUpdRange) return c->fail(DM_E_RANGE, "row out of range");
-  if (f & kUpdDup) return c->fail(DM_E_INVAL, "rows must be unique within one call");
-  if (f & kUpdSub) return c->fail(DM_E_INVAL, "subclients must be in [0, 2^31-2]");
-  return DM_OK;
-}
+static constexpr int64_t kStageChunk = 1 << 22;  // rows per copy/validate step of a single call
 
 // How a call that dm_keep_keys may keep ends (dm_row_epoch.h): a wants refresh, and with
 // DM_KEEP_UPDATES a release, an upsert or a synchronous batch.  Where the mode does not cover
-// the call it starts a row epoch before it launches, as every writer does; where it does,
-// once its flags are back -- kept (dm_ctx::refresh_kept, update_kept), or rows_changed() on
-// every other way out of the call (a rejection, a NaN, a failure on the way).
+// the call (an asynchronous batch never is) it starts a row epoch before it launches, as every
+// writer does; where it does, once its flags are back -- kept (dm_ctx::refresh_kept,
+// update_kept), or rows_changed() on every other way out of the call (a rejection, a NaN, a
+// failure on the way).  Every one of these ends tells the large chain that rows were written.
 namespace {
 struct WriteEnd {
   dm_ctx* c;
@@ -100,7 +51,122 @@ struct WriteEnd {
       c->update_kept(w, n);
   }
 };
+
 }  // namespace
+
+// Host columns' rows [off, off + m) onto the copy stream (a column without a source: none).
+static int copy_cols(dm_ctx* c, const StageCol* cols, int ncols, int64_t off, int64_t m) {
+  for (const StageCol* k = cols; k < cols + ncols; ++k)
+    if (k->src && m > 0)
+      DM_HIP(c, hipMemcpyAsync((char*)k->dst + off * k->elem, (const char*)k->src + off * k->elem, (size_t)m * k->elem,
+                               hipMemcpyHostToDevice, c->cpy),
+             "stage update");
+  return DM_OK;
+}
+
+// A part that names rows (an upsert, a row refresh, a release; alone or in a batch), its
+// columns staged in S: the device sequence on the context stream.  Its rows in range and unique
+// (a bitmap over the table, O(n + N/64)) once they have landed, the rejection of the part
+// before carried into its word, the apply kernel (which finds each row's resource, and returns
+// at once from a rejected word), the bitmap cleared again.  cols: a single call's host columns,
+// copied here chunk by chunk; b: a batch, whose part is already on its way and whose arrivals
+// may be narrow (subclients of 4 B, no has: 0, no expiry: now + the resource's lease length).
+static int row_part(dm_ctx* c, UpdateStage& S, const WriteEnd& we, UpdPart part, int64_t n, const StageCol* cols,
+                    int ncols, const dm_store_batch* b) {
+  hipStream_t st = c->stream;
+  const int word = flags_word(part);
+  uint32_t* F = S.flag(word);
+  const int64_t* rows = part == UpdPart::batch_release ? S.rel.p : S.rows.p;
+  const double* wants = writes_wants(part) ? S.wants.p : nullptr;
+  const bool sub32 = b && b->upsert_subclients32;
+  const int64_t* sub = writes_subclients(part) && !sub32 ? S.sub.p : nullptr;
+  const int32_t* s32 = writes_subclients(part) && sub32 ? (const int32_t*)S.sub.p : nullptr;
+  const int64_t step = b ? n : kStageChunk;
+  int k = 0;
+  for (int64_t off = 0; off < n; off += step, ++k) {
+    const int64_t m = std::min(step, n - off);
+    hipEvent_t ev = S.ev_bat[b ? word : k & 1];
+    if (!b) {
+      if (int rc = copy_cols(c, cols, ncols, off, m)) return rc;
+      DM_HIP(c, hipEventRecord(ev, c->cpy), "stage update");
+    }
+    DM_HIP(c, hipStreamWaitEvent(st, ev, 0), "stage update");
+    DM_HIP(c, launch_check_rows(m, rows + off, c->N, c->row_bits.bits.p, wants ? wants + off : nullptr,
+                                sub ? sub + off : nullptr, s32 ? s32 + off : nullptr, F, st),
+           "check rows");
+  }
+  if (b) DM_HIP(c, launch_carry_reject(F - 1, F, st), "carry");
+  const StoreCols sc = c->store_cols();
+  if (!wants)
+    DM_HIP(c, launch_release(n, rows, sc, F, c->dense_upd(), we.keys(), st), "release");
+  else if (!writes_subclients(part))
+    DM_HIP(c, launch_update_wants(n, rows, wants, sc, F, we.keys(), st), "update wants");
+  else
+    DM_HIP(c, launch_upsert(n, rows, !b || b->upsert_has ? S.has.p : nullptr, wants, sub, s32,
+                            !b || b->upsert_expiry_ns ? S.exp.p : nullptr, b ? b->upsert_now_ns : 0, sc, F, c->dense_upd(),
+                            we.keys(), st),
+           "upsert");
+  DM_HIP(c, launch_clear_rows(n, rows, c->N, c->row_bits.bits.p, st), "clear rows");
+  return DM_OK;
+}
+
+// A masked refresh's copies (copy stream) and kernels (context stream).  nchunk 0, the single
+// call: mask and values land behind one event, and one launch counts, scans and applies.
+// Else, a batch: the count and scan run once the mask is there, and the n packed values cross
+// in nchunk chunks, each applied as soon as it has landed (the apply of one chunk overlaps the
+// next one's copy: C4 3.2 -> ~3.0 ms per step).
+static int mask_copies(dm_ctx* c, UpdateStage& S, int64_t nwords, const uint64_t* mask, int64_t n, const double* wants,
+                       int nchunk) {
+  const StageCol cm{S.mask.p, mask, 8}, cv{S.mwants.p, wants, 8};
+  if (int rc = copy_cols(c, &cm, 1, 0, nwords)) return rc;
+  if (!nchunk)
+    if (int rc = copy_cols(c, &cv, 1, 0, n)) return rc;
+  DM_HIP(c, hipEventRecord(S.ev_bat[0], c->cpy), "stage update");
+  for (int k = 0; k < nchunk; ++k) {
+    if (int rc = copy_cols(c, &cv, 1, n * k / nchunk, n * (k + 1) / nchunk - n * k / nchunk)) return rc;
+    DM_HIP(c, hipEventRecord(S.ev_wchunk[k], c->cpy), "stage update");
+  }
+  return DM_OK;
+}
+
+static int mask_kernels(dm_ctx* c, UpdateStage& S, int64_t first_row, int64_t nwords, int64_t n, uint32_t* flags,
+                        int nchunk, const KeyClear* kc) {
+  hipStream_t st = c->stream;
+  auto launch = [&](int phase, int64_t v0, int64_t v1) {
+    return launch_update_wants_mask(nwords, S.mask.p, first_row, c->N, n, S.mwants.p, S.blk.p, S.wpre.p, c->store_cols(),
+                                    flags, phase, v0, v1, kc, st);
+  };
+  DM_HIP(c, hipStreamWaitEvent(st, S.ev_bat[0], 0), "stage update");
+  DM_HIP(c, launch(nchunk ? 0 : 2, 0, INT64_MAX), "masked update");
+  for (int k = 0; k < nchunk; ++k) {
+    const int64_t v0 = n * k / nchunk, v1 = n * (k + 1) / nchunk;
+    DM_HIP(c, hipStreamWaitEvent(st, S.ev_wchunk[k], 0), "stage update");
+    if (v1 > v0) DM_HIP(c, launch(1, v0, v1), "masked update");
+  }
+  return DM_OK;
+}
+
+// A single call's end: its flags word back and the wait (the call is synchronous on return, so
+// the caller may free its buffers and set 0 is idle again), then what the word says.
+static int single_end(dm_ctx* c, UpdateStage& S, UpdPart part, WriteEnd& we, int64_t n) {
+  DM_HIP(c, S.fetch_flags(1, c->stream), "update flags");
+  if (int rs = c->synced("update")) return rs;
+  const uint32_t f = S.h_flags.p[0];
+  const UpdOutcome o = update_outcome(part, f, false);
+  if (o.code != DM_OK) return c->fail(o.code, o.msg);
+  update_values(part, f, c->maybe_general, c->all_sub_one);
+  we.end(false, f & kUpdNaN, n);
+  c->have_result = false;
+  return DM_OK;
+}
+
+// A single call that names rows: bitmap and flags word ready, the part, the end.
+static int single_rows(dm_ctx* c, UpdateStage& S, WriteEnd& we, UpdPart part, int64_t n, const StageCol* cols, int ncols) {
+  DM_HIP(c, c->row_bits.ensure(c->N, c->stream), "row bitmap");
+  DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
+  if (int rc = row_part(c, S, we, part, n, cols, ncols, nullptr)) return rc;
+  return single_end(c, S, part, we, n);
+}
 
 int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
                     const int64_t* sub, const int64_t* exp) {
@@ -111,28 +177,10 @@ int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has
   if (n == 0) return DM_OK;
   c->expl_rows = true;  // (kept or not: the rows take explicit expiries)
   WriteEnd we(c, RowWrite::upsert);
-  DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
-  DM_HIP(c, c->st_has.ensure((size_t)n), "stage has");
-  DM_HIP(c, c->st_wants.ensure((size_t)n), "stage wants");
-  DM_HIP(c, c->st_sub.ensure((size_t)n), "stage sub");
-  DM_HIP(c, c->st_exp.ensure((size_t)n), "stage expiry");
-  const StageCol cols[] = {{c->st_rows.p, rows, 8}, {c->st_wants.p, wants, 8}, {c->st_sub.p, sub, 8},
-                           {c->st_has.p, has, 8}, {c->st_exp.p, exp, 8}};
-  int rc = staged_check(c, n, cols, 5, true, true);
-  if (rc) return rc;
-  DM_HIP(c, launch_upsert(n, c->st_rows.p, c->st_has.p, c->st_wants.p, c->st_sub.p, nullptr, c->st_exp.p, c->cfg.p, 0,
-                          c->row_index(), c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p, c->expl.p,
-                          c->upd_flags.p, c->dense_upd(), c->stream, we.keys()),
-         "upsert");
-  uint32_t f = 0;
-  rc = finish_update(c, n, &f);
-  if (rc) return rc;
-  we.end(false, f & kUpdNaN, n);
-  // an upsert can make a resource's subclients heterogeneous: stay conservative
-  if ((f & (kUpdNaN | kUpdNotOne)) || !c->all_sub_one) c->maybe_general = true;
-  if (f & kUpdNotOne) c->all_sub_one = false;
-  c->have_result = false;
-  return DM_OK;
+  UpdateStage& S = c->stage[0];
+  DM_HIP(c, S.ensure_upsert(n), "stage upsert");
+  const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}, {S.sub.p, sub, 8}, {S.has.p, has, 8}, {S.exp.p, exp, 8}};
+  return single_rows(c, S, we, UpdPart::upsert, n, cols, 5);
 }
 
 int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
@@ -142,21 +190,10 @@ int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const doubl
   if (n < 0 || (n > 0 && (!rows || !wants))) return c->fail(DM_E_INVAL, "bad update");
   if (n == 0) return DM_OK;
   WriteEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
-  DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
-  DM_HIP(c, c->st_wants.ensure((size_t)n), "stage wants");
-  const StageCol cols[] = {{c->st_rows.p, rows, 8}, {c->st_wants.p, wants, 8}};
-  int rc = staged_check(c, n, cols, 2, true, false);
-  if (rc) return rc;
-  DM_HIP(c, launch_update_wants(n, c->st_rows.p, c->st_wants.p, c->row_index(), c->sub.p, c->wants.p, c->agg.p,
-                                c->upd_flags.p, re.keys(), c->stream),
-         "update wants");
-  uint32_t f = 0;
-  rc = finish_update(c, n, &f);
-  if (rc) return rc;
-  re.end(false, f & kUpdNaN, n);
-  if (f & kUpdNaN) c->maybe_general = true;
-  c->have_result = false;
-  return DM_OK;
+  UpdateStage& S = c->stage[0];
+  DM_HIP(c, S.ensure_each(n, S.rows, S.wants), "stage refresh");
+  const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}};
+  return single_rows(c, S, re, UpdPart::refresh, n, cols, 2);
 }
 
 // The same narrow Assign with the rows as a bit mask (one bit per row of
@@ -172,32 +209,12 @@ int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, con
   if (nwords == 0) return n == 0 ? DM_OK : c->fail(DM_E_INVAL, "packed values without a mask");
   if (first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
   WriteEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
-  const int64_t nb = (nwords + 255) / 256;
-  DM_HIP(c, c->st_mask.ensure((size_t)nwords), "stage mask");
-  DM_HIP(c, c->st_wants.ensure((size_t)std::max<int64_t>(n, 1)), "stage wants");
-  DM_HIP(c, c->st_blk.ensure((size_t)nb), "stage block sums");
-  DM_HIP(c, c->st_wpre.ensure((size_t)nwords), "stage word offsets");
-  if (int rc = reset_upd_flags(c)) return rc;
-  // the copies overlap whatever still runs on the context's streams (staged_check)
-  DM_HIP(c, hipMemcpyAsync(c->st_mask.p, mask, (size_t)nwords * 8, hipMemcpyHostToDevice, c->cpy), "stage mask");
-  if (n > 0)
-    DM_HIP(c, hipMemcpyAsync(c->st_wants.p, wants, (size_t)n * 8, hipMemcpyHostToDevice, c->cpy), "stage wants");
-  DM_HIP(c, hipEventRecord(c->ev_stage[0], c->cpy), "stage update");
-  DM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_stage[0], 0), "stage update");
-  DM_HIP(c, launch_update_wants_mask(nwords, c->st_mask.p, first_row, c->N, n, c->st_wants.p, c->st_blk.p,
-                                     c->st_wpre.p, c->row_index(), c->sub.p, c->wants.p, c->agg.p, c->upd_flags.p,
-                                     c->stream, 2, 0, INT64_MAX, re.keys()),
-         "masked update");
-  DM_HIP(c, hipMemcpyAsync(c->h_flags.p, c->upd_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream),
-         "update flags");
-  if (int rs = c->synced("update")) return rs;
-  const uint32_t f = *c->h_flags.p;
-  if (f & kUpdRange) return c->fail(DM_E_RANGE, "mask bit past the store's end");
-  if (f & kUpdCount) return c->fail(DM_E_INVAL, "packed values must match the mask's set bits");
-  re.end(false, f & kUpdNaN, n);
-  if (f & kUpdNaN) c->maybe_general = true;
-  c->have_result = false;
-  return DM_OK;
+  UpdateStage& S = c->stage[0];
+  DM_HIP(c, S.ensure_mask(nwords, n), "stage mask");
+  DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
+  if (int rc = mask_copies(c, S, nwords, mask, n, wants, 0)) return rc;
+  if (int rc = mask_kernels(c, S, first_row, nwords, n, S.flag(0), 0, re.keys())) return rc;
+  return single_end(c, S, UpdPart::refresh_mask, re, n);
 }
 
 int dm_store_release(dm_ctx* c, int64_t n, const int64_t* rows) {
@@ -207,19 +224,10 @@ int dm_store_release(dm_ctx* c, int64_t n, const int64_t* rows) {
   if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad release");
   if (n == 0) return DM_OK;
   WriteEnd we(c, RowWrite::release);
-  DM_HIP(c, c->st_rows.ensure((size_t)n), "stage rows");
-  const StageCol cols[] = {{c->st_rows.p, rows, 8}};
-  int rc = staged_check(c, n, cols, 1, false, false);
-  if (rc) return rc;
-  DM_HIP(c, launch_release(n, c->st_rows.p, c->row_index(), c->has.p, c->wants.p, c->sub.p, c->expiry.p,
-                           c->agg.p, c->expl.p, c->upd_flags.p, c->dense_upd(), c->stream, we.keys()),
-         "release");
-  uint32_t f = 0;
-  rc = finish_update(c, n, &f);
-  if (rc) return rc;
-  we.end(false, false, n);
-  c->have_result = false;
-  return DM_OK;
+  UpdateStage& S = c->stage[0];
+  DM_HIP(c, S.rows.ensure((size_t)n), "stage rows");
+  const StageCol cols[] = {{S.rows.p, rows, 8}};
+  return single_rows(c, S, we, UpdPart::release, n, cols, 1);
 }
 
 // One round of updates: every part's columns cross PCIe back to back on the copy
@@ -252,141 +260,64 @@ static int batch_args(dm_ctx* c, const dm_store_batch* b) {
 }
 
 // The batch's copies (copy stream), its three parts' kernels (context stream) and the
-// flags' copy back into S.h_flags; nothing waits for them here.  we: the synchronous call's
-// end (its key-clearing builds, and the row epoch it has started or will decide on); null:
-// an asynchronous batch, which starts a row epoch here.
-static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, dm_ctx::ApplySet& S, const WriteEnd* we) {
+// flags' copy back into S.h_flags; nothing waits for them here.  we: the call's end (its
+// key-clearing builds, and the row epoch it has started or will decide on).
+static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, UpdateStage& S, const WriteEnd& we) {
   const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
   const bool sub32 = b->upsert_subclients32 != nullptr;
   if (nu > 0) c->expl_rows = true;  // arrivals take explicit expiries
-  if (nu > 0 || nr > 0) c->chain.rows_written();  // subclients words written, rows released
-  if (!we) c->rows_changed();  // (wants refreshes too: a NaN wants ends a resource's dense state)
-  const KeyClear* kc = we ? we->keys() : nullptr;
   S.nu = nu;
-  hipStream_t st = c->stream, cp = c->cpy;
-  if (!S.flags.p) {
-    DM_HIP(c, S.flags.ensure(3), "batch flags");
-    DM_HIP(c, S.h_flags.alloc(3, hipHostMallocDefault), "batch flags");
-  }
-  if (!c->row_bits.p || c->row_bits.n < (size_t)(c->N / 32 + 1)) {
-    DM_HIP(c, c->row_bits.ensure((size_t)(c->N / 32 + 1)), "row bitmap");
-    DM_HIP(c, hipMemsetAsync(c->row_bits.p, 0, c->row_bits.n * sizeof(uint32_t), st), "row bitmap");
-  }
-  DM_HIP(c, hipMemsetAsync(S.flags.p, 0, 3 * sizeof(uint32_t), st), "batch flags");
-  uint32_t* F = S.flags.p;
+  hipStream_t st = c->stream;
+  DM_HIP(c, c->row_bits.ensure(c->N, st), "row bitmap");
+  DM_HIP(c, S.reset_flags(3, st), "batch flags");
   // the refresh's packed values cross in up to kWChunks chunks of >= 2^21 values, so
   // that the synchronous call's apply overlaps its own copies; an asynchronous batch's
   // apply overlaps the next batch's copies anyway, and one copy costs less than four
   // (C4 2.95 -> 2.91 ms per step, alternated: tools/archive/gpu_r6_c4chunk.sh)
-  const bool sync_set = &S == &c->aset[0];
-  const int nchunk = nw == 0 ? 0 : !sync_set ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(dm_ctx::kWChunks, nm >> 21));
+  const int nchunk = we.w == RowWrite::apply_async ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(kWChunks, nm >> 21));
   // copies, back to back
   if (nw > 0) {
-    DM_HIP(c, S.mask.ensure((size_t)nw), "stage mask");
-    DM_HIP(c, S.mwants.ensure((size_t)std::max<int64_t>(nm, 1)), "stage wants");
-    DM_HIP(c, S.blk.ensure((size_t)((nw + 255) / 256)), "stage block sums");
-    DM_HIP(c, S.wpre.ensure((size_t)nw), "stage word offsets");
-    DM_HIP(c, hipMemcpyAsync(S.mask.p, b->wants_mask, (size_t)nw * 8, hipMemcpyHostToDevice, cp), "stage mask");
-    DM_HIP(c, hipEventRecord(S.ev_bat[0], cp), "stage");
-    // the packed values in chunks, each applied as soon as it has landed (the apply
-    // of one chunk overlaps the next one's copy): C4 3.2 -> ~3.0 ms per step
-    for (int k = 0; k < nchunk; ++k) {
-      const int64_t v0 = nm * k / nchunk, v1 = nm * (k + 1) / nchunk;
-      if (v1 > v0)
-        DM_HIP(c, hipMemcpyAsync(S.mwants.p + v0, b->wants + v0, (size_t)(v1 - v0) * 8, hipMemcpyHostToDevice, cp),
-               "stage wants");
-      DM_HIP(c, hipEventRecord(S.ev_wchunk[k], cp), "stage");
-    }
+    DM_HIP(c, S.ensure_mask(nw, nm), "stage mask");
+    if (int rc = mask_copies(c, S, nw, b->wants_mask, nm, b->wants, nchunk)) return rc;
   }
   if (nr > 0) {
     DM_HIP(c, S.rel.ensure((size_t)nr), "stage release rows");
-    DM_HIP(c, hipMemcpyAsync(S.rel.p, b->release_rows, (size_t)nr * 8, hipMemcpyHostToDevice, cp), "stage rows");
-    DM_HIP(c, hipEventRecord(S.ev_bat[1], cp), "stage");
+    const StageCol col{S.rel.p, b->release_rows, 8};
+    if (int rc = copy_cols(c, &col, 1, 0, nr)) return rc;
+    DM_HIP(c, hipEventRecord(S.ev_bat[1], c->cpy), "stage update");
   }
   if (nu > 0) {
-    DM_HIP(c, S.rows.ensure((size_t)nu), "stage rows");
-    DM_HIP(c, S.has.ensure((size_t)nu), "stage has");
-    DM_HIP(c, S.wants.ensure((size_t)nu), "stage wants");
-    DM_HIP(c, S.sub.ensure((size_t)nu), "stage sub");
-    DM_HIP(c, S.exp.ensure((size_t)nu), "stage expiry");
+    DM_HIP(c, S.ensure_upsert(nu), "stage upsert");
     const StageCol cols[] = {{S.rows.p, b->upsert_rows, 8},
                              {S.wants.p, b->upsert_wants, 8},
                              {S.sub.p, sub32 ? (const void*)b->upsert_subclients32 : b->upsert_subclients, sub32 ? 4u : 8u},
                              {S.has.p, b->upsert_has, 8},
                              {S.exp.p, b->upsert_expiry_ns, 8}};
-    for (const auto& col : cols)
-      if (col.src)
-        DM_HIP(c, hipMemcpyAsync(col.dst, col.src, (size_t)nu * col.elem, hipMemcpyHostToDevice, cp), "stage upsert");
-    DM_HIP(c, hipEventRecord(S.ev_bat[2], cp), "stage");
+    if (int rc = copy_cols(c, cols, 5, 0, nu)) return rc;
+    DM_HIP(c, hipEventRecord(S.ev_bat[2], c->cpy), "stage update");
   }
-  // part 1: wants refresh (validated by its count/scan passes over the mask, then
-  // applied chunk by chunk as the values land)
-  if (nw > 0) {
-    DM_HIP(c, hipStreamWaitEvent(st, S.ev_bat[0], 0), "stage");
-    DM_HIP(c, launch_update_wants_mask(nw, S.mask.p, b->wants_first_row, c->N, nm, S.mwants.p, S.blk.p, S.wpre.p,
-                                       c->row_index(), c->sub.p, c->wants.p, c->agg.p, F + 0, st, 0, 0, 0),
-           "masked update");
-    for (int k = 0; k < nchunk; ++k) {
-      const int64_t v0 = nm * k / nchunk, v1 = nm * (k + 1) / nchunk;
-      DM_HIP(c, hipStreamWaitEvent(st, S.ev_wchunk[k], 0), "stage");
-      if (v1 > v0)
-        DM_HIP(c, launch_update_wants_mask(nw, S.mask.p, b->wants_first_row, c->N, nm, S.mwants.p, S.blk.p, S.wpre.p,
-                                           c->row_index(), c->sub.p, c->wants.p, c->agg.p, F + 0, st, 1, v0, v1, kc),
-               "masked update");
-    }
-  }
+  // part 1: wants refresh (validated by its count/scan passes over the mask)
+  if (nw > 0)
+    if (int rc = mask_kernels(c, S, b->wants_first_row, nw, nm, S.flag(0), nchunk, we.keys())) return rc;
   // part 2: departures
   if (nr > 0) {
-    DM_HIP(c, hipStreamWaitEvent(st, S.ev_bat[1], 0), "stage");
-    DM_HIP(c, launch_check_rows(nr, S.rel.p, c->N, c->row_bits.p, nullptr, nullptr, nullptr, F + 1, st), "check rows");
-    DM_HIP(c, launch_carry_reject(F + 0, F + 1, st), "carry");
-    DM_HIP(c, launch_release(nr, S.rel.p, c->row_index(), c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p,
-                             c->expl.p, F + 1, c->dense_upd(), st, kc),
-           "release");
-    DM_HIP(c, launch_clear_rows(nr, S.rel.p, c->N, c->row_bits.p, st), "clear rows");
+    if (int rc = row_part(c, S, we, UpdPart::batch_release, nr, nullptr, 0, b)) return rc;
   } else {
-    DM_HIP(c, launch_carry_reject(F + 0, F + 1, st), "carry");
+    DM_HIP(c, launch_carry_reject(S.flag(0), S.flag(1), st), "carry");
   }
   // part 3: arrivals / full refreshes
-  if (nu > 0) {
-    DM_HIP(c, hipStreamWaitEvent(st, S.ev_bat[2], 0), "stage");
-    const int64_t* s64 = sub32 ? nullptr : S.sub.p;
-    const int32_t* s32 = sub32 ? (const int32_t*)S.sub.p : nullptr;
-    DM_HIP(c, launch_check_rows(nu, S.rows.p, c->N, c->row_bits.p, S.wants.p, s64, s32, F + 2, st), "check rows");
-    DM_HIP(c, launch_carry_reject(F + 1, F + 2, st), "carry");
-    DM_HIP(c, launch_upsert(nu, S.rows.p, b->upsert_has ? S.has.p : nullptr, S.wants.p, s64, s32,
-                            b->upsert_expiry_ns ? S.exp.p : nullptr, c->cfg.p, b->upsert_now_ns, c->row_index(),
-                            c->has.p, c->wants.p, c->sub.p, c->expiry.p, c->agg.p, c->expl.p, F + 2, c->dense_upd(), st,
-                            kc),
-           "upsert");
-    DM_HIP(c, launch_clear_rows(nu, S.rows.p, c->N, c->row_bits.p, st), "clear rows");
-  }
-  DM_HIP(c, hipMemcpyAsync(S.h_flags.p, F, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "batch flags");
+  if (nu > 0)
+    if (int rc = row_part(c, S, we, UpdPart::batch_upsert, nu, nullptr, 0, b)) return rc;
+  DM_HIP(c, S.fetch_flags(3, st), "batch flags");
   c->have_result = false;
   return DM_OK;
 }
 
-// A landed batch's flags: the first rejected part fails the call (its message names the
-// part; `late` marks an asynchronous batch reported by a later call), NaN wants or
-// other subclient counts make the store maybe-general.
-static int apply_check(dm_ctx* c, const dm_ctx::ApplySet& S, bool late) {
-  const uint32_t f0 = S.h_flags.p[0], f1 = S.h_flags.p[1], f2 = S.h_flags.p[2];
-  auto reject = [&](uint32_t f, const char* part) -> int {
-    const std::string p = std::string(late ? "an earlier asynchronous batch's " : "") + part;
-    if (f & kUpdRange) return c->fail(DM_E_RANGE, p + ": row out of range");
-    if (f & kUpdCount) return c->fail(DM_E_INVAL, p + ": packed values must match the mask's set bits");
-    if (f & kUpdDup) return c->fail(DM_E_INVAL, p + ": rows must be unique within one part");
-    return c->fail(DM_E_INVAL, p + ": subclients must be in [0, 2^31-2]");
-  };
-  if (f0 & kUpdReject) return reject(f0, "wants refresh");
-  if (f0 & kUpdNaN) c->maybe_general = true;
-  if (f1 & kUpdReject) return reject(f1, "release");
-  if (f2 & kUpdReject) return reject(f2, "upsert");
-  if (S.nu > 0) {
-    if ((f2 & (kUpdNaN | kUpdNotOne)) || !c->all_sub_one) c->maybe_general = true;
-    if (f2 & kUpdNotOne) c->all_sub_one = false;
-  }
-  return DM_OK;
+// A landed batch's flags (dm_update_outcome.h batch_outcome; `late` marks an asynchronous
+// batch reported by a later call).
+static int apply_check(dm_ctx* c, const UpdateStage& S, bool late) {
+  const UpdOutcome o = batch_outcome(S.h_flags.p, S.nu > 0, late, c->maybe_general, c->all_sub_one);
+  return o.code != DM_OK ? c->fail(o.code, o.msg) : DM_OK;
 }
 
 int dm_store_apply(dm_ctx* c, const dm_store_batch* b) {
@@ -394,9 +325,9 @@ int dm_store_apply(dm_ctx* c, const dm_store_batch* b) {
   DM_STORE_OK(c);
   if (int rc = batch_args(c, b)) return rc;
   if (b->wants_nwords == 0 && b->release_n == 0 && b->upsert_n == 0) return DM_OK;
-  dm_ctx::ApplySet& S = c->aset[0];
+  UpdateStage& S = c->stage[0];
   WriteEnd we(c, RowWrite::apply);
-  if (int rc = apply_enqueue(c, b, S, &we)) return rc;
+  if (int rc = apply_enqueue(c, b, S, we)) return rc;
   if (int rs = c->synced("batch")) return rs;
   if (int rc = apply_check(c, S, false)) return rc;  // (a rejected part: a row epoch, ~WriteEnd)
   we.end(false, (S.h_flags.p[0] | S.h_flags.p[2]) & kUpdNaN, b->wants_n + b->release_n + b->upsert_n);
@@ -404,7 +335,7 @@ int dm_store_apply(dm_ctx* c, const dm_store_batch* b) {
 }
 
 // Retire asynchronous set S: wait for its batch, then its flags.
-static int async_retire(dm_ctx* c, dm_ctx::ApplySet& S) {
+static int async_retire(dm_ctx* c, UpdateStage& S) {
   if (!S.pending) return DM_OK;
   const hipError_t e = hipEventSynchronize(S.ev_done);
   S.pending = false;
@@ -417,13 +348,16 @@ int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) {
   DM_STORE_OK(c);
   if (int rc = batch_args(c, b)) return rc;
   if (b->wants_nwords == 0 && b->release_n == 0 && b->upsert_n == 0) return DM_OK;
-  dm_ctx::ApplySet& S = c->aset[1 + (int)(c->async_seq % dm_ctx::kAsyncSets)];
+  UpdateStage& S = c->stage[1 + (int)(c->async_seq % kAsyncSets)];
   // the set's previous batch (kAsyncSets batches back) first: its flags, and its
   // staging free for these copies (this wait is what keeps the host kAsyncSets
   // batches ahead of the device at most)
   if (int rc = async_retire(c, S)) return rc;
   S.may_general = b->wants_nwords > 0 || b->upsert_n > 0;
-  if (int rc = apply_enqueue(c, b, S, nullptr)) return rc;
+  // (wants refreshes too start a row epoch: a NaN wants ends a resource's dense state, and
+  // the batch's flags are read two batches later)
+  WriteEnd we(c, RowWrite::apply_async);
+  if (int rc = apply_enqueue(c, b, S, we)) return rc;
   DM_HIP(c, hipEventRecord(S.ev_done, c->stream), "batch done");
   S.pending = true;
   c->async_seq += 1;
@@ -435,9 +369,9 @@ int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) {
 int dm::async_retire_all(dm_ctx* c) {
   int first = DM_OK;
   std::string msg;
-  for (int64_t k = c->async_seq - dm_ctx::kAsyncSets; k < c->async_seq; ++k) {  // oldest first
+  for (int64_t k = c->async_seq - kAsyncSets; k < c->async_seq; ++k) {  // oldest first
     if (k < 0) continue;
-    const int rc = async_retire(c, c->aset[1 + (int)(k % dm_ctx::kAsyncSets)]);
+    const int rc = async_retire(c, c->stage[1 + (int)(k % kAsyncSets)]);
     if (rc && first == DM_OK) {
       first = rc;
       msg = c->err;
@@ -451,10 +385,10 @@ int dm::async_retire_all(dm_ctx* c) {
 // outcome is dropped with the store they updated: a rejected batch's error is lost here
 // on purpose, and the load's own scan sets maybe_general / all_sub_one anew.
 void dm::async_drain(dm_ctx* c) {
-  for (int i = 1; i <= dm_ctx::kAsyncSets; ++i)
-    if (c->aset[i].pending) {
-      (void)hipEventSynchronize(c->aset[i].ev_done);
-      c->aset[i].pending = false;
+  for (int i = 1; i <= kAsyncSets; ++i)
+    if (c->stage[i].pending) {
+      (void)hipEventSynchronize(c->stage[i].ev_done);
+      c->stage[i].pending = false;
     }
 }
 

@@ -278,42 +278,38 @@ __global__ void k_gather_leases(int64_t n, const int64_t* __restrict__ rows, con
 // host-side launchers (called by dm_store.cpp and dm_store_update.cpp)
 // --------------------------------------------------------------------------
 hipError_t launch_upsert(int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
-                         const int32_t* sub32, const int64_t* expiry, const ResCfg* cfg, int64_t now,
-                         const RowIndex& ix, double* s_has, double* s_wants, int32_t* s_sub, int64_t* s_exp,
-                         ResAgg* agg, uint8_t* expl, const uint32_t* flags, const DenseUpd& du, hipStream_t st,
-                         const KeyClear* kc) {
+                         const int32_t* sub32, const int64_t* expiry, int64_t now, const StoreCols& s,
+                         const uint32_t* flags, const DenseUpd& du, const KeyClear* kc, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const unsigned grid = (unsigned)((n + 255) / 256);
   if (kc)
-    k_upsert_keys<<<grid, 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, cfg, now, ix, s_has, s_wants, s_sub,
-                                        s_exp, agg, expl, flags, du, *kc);
+    k_upsert_keys<<<grid, 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, s.cfg, now, s.ix, s.has, s.wants, s.sub,
+                                        s.expiry, s.agg, s.expl, flags, du, *kc);
   else
-    k_upsert<<<grid, 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, cfg, now, ix, s_has, s_wants, s_sub, s_exp,
-                                   agg, expl, flags, du);
+    k_upsert<<<grid, 256, 0, st>>>(n, rows, has, wants, sub, sub32, expiry, s.cfg, now, s.ix, s.has, s.wants, s.sub,
+                                   s.expiry, s.agg, s.expl, flags, du);
   return hipGetLastError();
 }
 
-hipError_t launch_release(int64_t n, const int64_t* rows, const RowIndex& ix, double* s_has, double* s_wants,
-                          int32_t* s_sub, int64_t* s_exp, ResAgg* agg, uint8_t* expl, const uint32_t* flags,
-                          const DenseUpd& du, hipStream_t st, const KeyClear* kc) {
+hipError_t launch_release(int64_t n, const int64_t* rows, const StoreCols& s, const uint32_t* flags,
+                          const DenseUpd& du, const KeyClear* kc, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const unsigned grid = (unsigned)((n + 255) / 256);
   if (kc)
-    k_release_keys<<<grid, 256, 0, st>>>(n, rows, ix, s_has, s_wants, s_sub, s_exp, agg, expl, flags, du, *kc);
+    k_release_keys<<<grid, 256, 0, st>>>(n, rows, s.ix, s.has, s.wants, s.sub, s.expiry, s.agg, s.expl, flags, du, *kc);
   else
-    k_release<<<grid, 256, 0, st>>>(n, rows, ix, s_has, s_wants, s_sub, s_exp, agg, expl, flags, du);
+    k_release<<<grid, 256, 0, st>>>(n, rows, s.ix, s.has, s.wants, s.sub, s.expiry, s.agg, s.expl, flags, du);
   return hipGetLastError();
 }
 
-hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const RowIndex& ix,
-                               const int32_t* s_sub, double* s_wants, ResAgg* agg, const uint32_t* flags,
-                               const KeyClear* kc, hipStream_t st) {
+hipError_t launch_update_wants(int64_t n, const int64_t* rows, const double* wants, const StoreCols& s,
+                               const uint32_t* flags, const KeyClear* kc, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const unsigned grid = (unsigned)((n + 255) / 256);
   if (kc)
-    k_update_wants_keys<<<grid, 256, 0, st>>>(n, rows, wants, ix, s_sub, s_wants, agg, flags, *kc);
+    k_update_wants_keys<<<grid, 256, 0, st>>>(n, rows, wants, s.ix, s.sub, s.wants, s.agg, flags, *kc);
   else
-    k_update_wants<<<grid, 256, 0, st>>>(n, rows, wants, ix, s_sub, s_wants, agg, flags);
+    k_update_wants<<<grid, 256, 0, st>>>(n, rows, wants, s.ix, s.sub, s.wants, s.agg, flags);
   return hipGetLastError();
 }
 
@@ -347,9 +343,8 @@ hipError_t launch_clear_rows(int64_t n, const int64_t* rows, int64_t N, uint32_t
 
 hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_t first_row, int64_t N,
                                     int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
-                                    const RowIndex& ix, const int32_t* s_sub, double* s_wants, ResAgg* agg,
-                                    uint32_t* flags, hipStream_t st, int phase, int64_t vlo, int64_t vhi,
-                                    const KeyClear* kc) {
+                                    const StoreCols& s, uint32_t* flags, int phase, int64_t vlo, int64_t vhi,
+                                    const KeyClear* kc, hipStream_t st) {
   if (nwords <= 0) return hipSuccess;
   const int64_t nb = (nwords + 255) / 256;
   if (phase != 1) {  // the mask's counts and value offsets (the mask alone)
@@ -360,10 +355,10 @@ hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_
     const int64_t waves = (nwords + kMaskWords - 1) / kMaskWords;
     const unsigned grid = (unsigned)((waves + 3) / 4);
     if (kc)
-      k_mask_apply_keys<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, ix, s_sub, s_wants,
-                                              agg, flags, vlo, vhi, *kc);
+      k_mask_apply_keys<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, s.ix, s.sub, s.wants,
+                                              s.agg, flags, vlo, vhi, *kc);
     else
-      k_mask_apply<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, ix, s_sub, s_wants, agg,
+      k_mask_apply<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, s.ix, s.sub, s.wants, s.agg,
                                          flags, vlo, vhi);
   }
   return hipGetLastError();

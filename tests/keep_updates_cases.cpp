@@ -2,7 +2,8 @@
 // First one line per writer, dm_keep_keys mode (0-3) and keys in use, from the functions that
 // take the mode's bits, in the format of tests/row_epoch_cases.cpp:
 //   <writer> mode=<0-3> keys=<0|1> -> defer=<0|1> build=<plain|keys> | ok=<end> nan=<end> rejected=<end> nan+rejected=<end>
-// then `legacy_same=<0|1>`: for modes 0 and 1 the two earlier functions answer the same;
+// then `legacy_same=<0|1>`: for modes 0 and 1 the rule the header held before dm_keep_keys took
+// a bit set (legacy_start, legacy_kept below: a transcription) answers the same;
 // then the form's choice with DM_KEEP_UPDATES, in the format of tests/split_form_cases.cpp:
 //   <case> <split><steady><skip_rest><fixed><use_keys><sweep> rest=<grid> list=<grid> live=<fix_live>
 #include <cstdio>
@@ -11,6 +12,17 @@
 #include "dm_split_form.h"
 
 using namespace dm;
+
+// dm_row_epoch.h's rule when dm_keep_keys was a boolean, as the header then held it
+static RowWriteStart legacy_start(RowWrite w, bool keep_keys, bool keys_in_use) {
+  RowWriteStart s;
+  s.defer = keep_keys && is_refresh(w);
+  s.clear_keys = s.defer && keys_in_use;
+  return s;
+}
+static bool legacy_kept(RowWrite w, bool keep_keys, bool rejected, bool nan) {
+  return keep_keys && is_refresh(w) && !rejected && !nan;
+}
 
 static FormInputs base() {  // split_form_cases.cpp's: 1000 items at their fixed point in row epoch 7, keys in use
   FormInputs in;
@@ -61,12 +73,12 @@ int main() {
         printf("%s mode=%d keys=%d -> defer=%d build=%s |", wr.name, mode, keys, s.defer, s.clear_keys ? "keys" : "plain");
         static const char* const outcome[4] = {"ok", "nan", "rejected", "nan+rejected"};
         if (mode < 2) {
-          const RowWriteStart l = row_write_start(wr.w, mode != 0, keys != 0);
+          const RowWriteStart l = legacy_start(wr.w, mode != 0, keys != 0);
           legacy_same &= l.defer == s.defer && l.clear_keys == s.clear_keys;
         }
         for (int o = 0; o < 4; ++o) {
           const bool kept = row_write_kept_mode(wr.w, mode, (o & 2) != 0, (o & 1) != 0);
-          if (mode < 2) legacy_same &= kept == row_write_kept(wr.w, mode != 0, (o & 2) != 0, (o & 1) != 0);
+          if (mode < 2) legacy_same &= kept == legacy_kept(wr.w, mode != 0, (o & 2) != 0, (o & 1) != 0);
           printf(" %s=%s", outcome[o], kept ? "kept" : "epoch");
         }
         printf("\n");

@@ -24,11 +24,11 @@ int main() {
   for (int mode = 0; mode < 2; ++mode)
     for (const auto& wr : writers)
       for (int keys = 0; keys < 2; ++keys) {
-        const RowWriteStart s = row_write_start(wr.w, mode != 0, keys != 0);
+        const RowWriteStart s = row_write_start_mode(wr.w, mode, keys != 0);
         printf("%s mode=%d keys=%d -> defer=%d build=%s |", wr.name, mode, keys, s.defer, s.clear_keys ? "keys" : "plain");
         static const char* const outcome[4] = {"ok", "nan", "rejected", "nan+rejected"};
         for (int o = 0; o < 4; ++o)
-          printf(" %s=%s", outcome[o], row_write_kept(wr.w, mode != 0, (o & 2) != 0, (o & 1) != 0) ? "kept" : "epoch");
+          printf(" %s=%s", outcome[o], row_write_kept_mode(wr.w, mode, (o & 2) != 0, (o & 1) != 0) ? "kept" : "epoch");
         printf("\n");
       }
   // a part of 100,000 items with keys in use, whose sweep record is of this row epoch

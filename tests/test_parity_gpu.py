@@ -936,6 +936,121 @@ def test_store_apply_async_between_synchronous_calls_and_a_reload(eng):
         other.close()
 
 
+def test_sync_calls_share_one_staging_set(eng):
+    """Every call that is synchronous on return stages through the same device buffers: the
+    single updates, the synchronous dm_store_apply and the reads that resolve rows on the
+    device.  A mixed sequence of them, with sizes that go up and down (a buffer grown by one
+    route is then used, smaller and larger, by the other), asynchronous batches in between
+    (three: more than the sets they rotate through) and rejected calls, leaves after every
+    step the store of the same changes made through single calls on another context: the
+    four columns and Count bit for bit, the sums within 1e-12 of capacity (atomic adds).  The
+    final writeback tick matches the oracle.  5, 70, 300 and 1,500 rows: a tile, a sub-wave
+    bin and two workgroup bins."""
+    from doorman_amd._lib import DM_E_INVAL, DmError
+    from doorman_amd.engine import Engine
+    rng = np.random.default_rng(46)
+    snap = snapshot_with_sizes(rng, np.array([5, 70, 300, 1500]), expired_frac=0.0)
+    N = len(snap["wants"])
+    cap = np.maximum(snap["capacity"], 1.0)
+    perm = rng.permutation(N)
+    taken = [0]
+
+    def take(k):  # k rows no other step names, ascending
+        taken[0] += k
+        return np.sort(perm[taken[0] - k:taken[0]])
+
+    def values(k):
+        return rng.uniform(0.5, 1.5, k)
+
+    def arrivals(rows):
+        k = len(rows)
+        return rows, rng.uniform(0, 2, k), values(k), np.ones(k, np.int64), np.full(k, NOW + 900 * W.NS)
+
+    other = Engine(0)
+
+    def same(label):
+        s1, s2 = eng.read_store(), other.read_store()
+        for k in ("has", "wants", "subclients", "expiry_ns"):
+            assert s1[k].tobytes() == s2[k].tobytes(), (label, k)
+        r1, r2 = eng.resources(safe=False), other.resources(safe=False)
+        np.testing.assert_array_equal(r1["count"], r2["count"], err_msg=label)
+        for k in ("sum_has", "sum_wants"):
+            assert float_close(r1[k], r2[k], cap, 1e-12).all(), (label, k)
+        return s1, r1
+
+    def batch(upd, w, gone, ups, **kw):  # on eng as one batch, on other as single calls
+        eng.apply(W.rows_to_mask(upd, N) if len(upd) else None, w if len(upd) else None,
+                  gone if len(gone) else None, ups, **kw)
+        if len(upd):
+            other.update_wants(upd, w)
+        if len(gone):
+            other.release(gone)
+        if ups is not None:
+            other.upsert(*ups)
+
+    try:
+        eng.load(snap)
+        other.load(snap)
+        eng.apportion(NOW)
+        other.apportion(NOW)
+        rows = take(3)  # 1: a read that gathers on the device
+        g1, e1 = eng.leases_rows(rows)
+        g2, e2 = other.leases()
+        assert g1.tobytes() == g2[rows].tobytes() and e1.tobytes() == e2[rows].tobytes()
+        ups = arrivals(take(40))  # 2
+        eng.upsert(*ups)
+        other.upsert(*ups)
+        same("upsert of 40")
+        upd = take(200)  # 3: a synchronous batch, smaller row parts than the upsert before
+        batch(upd, values(200), take(2), arrivals(take(1)))
+        same("synchronous apply")
+        gone = take(100)  # 4
+        eng.release(gone)
+        other.release(gone)
+        same("release of 100")
+        upd = take(260)  # 5
+        w = values(260)
+        eng.update_wants_mask(W.rows_to_mask(upd, N), w)
+        other.update_wants(upd, w)
+        same("masked refresh")  # 6: read_store of the whole store, larger than anything staged so far
+        # 7: three asynchronous batches (the third reuses the first's set), a single call in between
+        batch(take(150), values(150), take(5), arrivals(take(5)), asynchronous=True)
+        same("asynchronous batch 1")
+        batch(take(20), values(20), np.array([], np.int64), arrivals(take(60)), asynchronous=True)
+        same("asynchronous batch 2")
+        upd = take(300)
+        w = values(300)
+        eng.update_wants(upd, w)
+        other.update_wants(upd, w)
+        same("single refresh between asynchronous batches")
+        batch(np.array([], np.int64), None, take(30), arrivals(take(2)), asynchronous=True)
+        same("asynchronous batch 3")
+        eng.apply_wait()  # 8
+        same("apply_wait")
+        dup = take(10)  # 9: a rejected single call writes nothing
+        with pytest.raises(DmError) as e:
+            eng.release(np.concatenate([dup, dup[:1]]))
+        assert e.value.code == DM_E_INVAL
+        same("rejected release")
+        upd, w, ups = take(90), values(90), arrivals(take(4))  # 10: the refresh before the rejected part stays
+        with pytest.raises(DmError) as e:
+            eng.apply(W.rows_to_mask(upd, N), w, np.concatenate([dup, dup[:1]]), ups)
+        assert e.value.code == DM_E_INVAL and "release" in str(e.value)
+        other.update_wants(upd, w)
+        same("rejected batch")
+        batch(upd, w, dup, ups)  # 11: the same rows, accepted
+        s1, r1 = same("accepted batch")
+        assert taken[0] <= N
+        ref_snap = dict(snap)
+        ref_snap.update(has=s1["has"], wants=s1["wants"], subclients=s1["subclients"], expiry_ns=s1["expiry_ns"],
+                        agg_count=r1["count"], agg_sum_has=r1["sum_has"], agg_sum_wants=r1["sum_wants"])
+        eng.apportion(NOW, writeback=True)
+        gets, exp = eng.leases()
+        assert_leases_match(ref_snap, gets, exp, O.apportion(ref_snap, NOW), "after the mixed sequence")
+    finally:
+        other.close()
+
+
 def test_store_apply_async_reports_a_rejected_batch_later(eng):
     """dm_store_apply_async: a batch with a rejected part (duplicate departure rows) is
     enqueued without an error; the call that retires it (apply_wait) raises, naming the
