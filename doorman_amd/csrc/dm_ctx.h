@@ -193,6 +193,8 @@ struct SplitSlot {
   int64_t items() const { return lo[1] - lo[0]; }
   const DBuf<FixKey>* bin_keys = nullptr;  // ... and its keys that range of dm_ctx::fix_keys[b - 3]
   FixKey* keys() const { return bin_keys->p + lo[0]; }
+  const DBuf<CycAux>* bin_aux = nullptr;  // ... and the cycle form's half of them (dm_ctx::cyc_aux)
+  CycAux* aux() const { return bin_aux->p + lo[0]; }
   // The rest queue (k_block_dense appends, k_block_rest decides), one entry per item at
   // most; qcnt: its two-slot count ring and the last count told the host; qpar: the ring
   // slot of the next split tick.  queued (host-mapped): items the last split tick queued,
@@ -231,6 +233,10 @@ struct SplitSlot {
   // bin_part assigns it from choose_form's result (PartForm::fix_live has the rule and
   // why the host keeps it); rows_changed() and dm_ctx::reset_keys clear it.
   uint64_t fix_live = 0;
+  // The same for the cycle form (PartForm::cyc_live), and when the part asks for the
+  // alternate column by itself (dm_split_form.h CycleAuto).
+  uint64_t cyc_live = 0;
+  CycleAuto cyc;
   // The sweep (k_fixed_sweep) lists the items whose key does not hold in sw_list, one
   // entry per item at most.  sw_cnt: the list's two-slot count ring and the last {count,
   // epoch} told the host; lpar: the ring slot of the next sweep; sweep (host-mapped):
@@ -257,9 +263,11 @@ struct SplitSlot {
       in.rec_kept = true;
       in.upd_rows = upd_rows;
     }
-    if (in.fix_live != in.row_epoch) return;
+    if (in.fix_live != in.row_epoch && in.cyc_live != in.row_epoch) return;
     in.sw_epoch = __atomic_load_n(sweep.h + 1, __ATOMIC_ACQUIRE);
-    in.sw_told = (int64_t)__atomic_load_n(sweep.h, __ATOMIC_RELAXED);
+    const uint64_t told = __atomic_load_n(sweep.h, __ATOMIC_RELAXED);
+    in.sw_told = (int64_t)(uint32_t)told;  // (the high half: the cycle form's stamp of the launch that told it)
+    in.sw_stamp = (uint32_t)(told >> 32);
   }
   int reset(dm_ctx* c, hipStream_t st);  // a new plan, or parts turned on or off (dm_plan.cpp)
 };
@@ -496,7 +504,7 @@ struct dm_ctx {
     chain.rows_written();
     row_epoch += 1;
     write_epoch += 1;
-    for (SplitSlot& s : split) s.fix_live = 0;  // no fixed-point key is trusted across a write (SplitSlot)
+    for (SplitSlot& s : split) s.fix_live = s.cyc_live = 0;  // no fixed-point key is trusted across a write (SplitSlot)
   }
   // dm_keep_keys.  kept_refreshes: dm_plan_info slot 23.  kept_rows: values the kept
   // refreshes carried since the last tick, each of which may have cleared a key: the next
@@ -526,7 +534,7 @@ struct dm_ctx {
   }
   bool keys_in_use() const {
     for (const SplitSlot& s : split)
-      if (s.fix_live == row_epoch) return true;
+      if (s.fix_live == row_epoch || s.cyc_live == row_epoch) return true;
     return false;
   }
   std::vector<int64_t> h_seg_off;
@@ -614,7 +622,19 @@ struct dm_ctx {
   // keys of bin b's items, parallel to bins[b]; each slot sees its part's (SplitSlot::keys).
   int fixed_ok = 1;
   DBuf<FixKey> fix_keys[kSplitBins];
-  DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part
+  DBuf<int32_t> fix_count;  // dm_store_stats: the valid keys of one part (two words: k_count_cycle)
+  // DM_CYCLE=0: no part runs the cycle form and none asks for the alternate column (the
+  // ticks are the ones they were without it).  cyc_aux[b - 3]: the keys' second halves.
+  int cycle_ok = 1;
+  // DM_CYCLE_BYTES (a test hook, read when the context is created): the store size in bytes
+  // (48 per lease) above which a part may ask by itself; kStreamBytes by default.
+  int64_t cycle_bytes = kStreamBytes;
+  DBuf<CycAux> cyc_aux[kSplitBins];
+  bool cycle_asked() const {  // some part asks for the alternate column (CycleAuto)
+    for (const SplitSlot& s : split)
+      if (s.cyc.on && s.cyc.epoch == row_epoch && s.items() > 0) return true;
+    return false;
+  }
   // the update launchers' view of the store's columns (dm_launch.h StoreCols)
   StoreCols store_cols() const { return {row_index(), has.p, wants.p, sub.p, expiry.p, agg.p, expl.p, cfg.p}; }
   // the key-clearing refresh and update kernels' view of the keys (dm_device.h KeyClear)
@@ -630,7 +650,10 @@ struct dm_ctx {
     DBuf<FixKey>& k = fix_keys[b - 3];
     hipError_t e = k.ensure(std::max<size_t>(h_bins[b].size(), 1));
     if (e == hipSuccess) e = hipMemsetAsync(k.p, 0, k.n * sizeof(FixKey), st);
-    for (int j = 0; j < kParts; ++j) slot(b, j).fix_live = 0;
+    DBuf<CycAux>& a = cyc_aux[b - 3];
+    if (e == hipSuccess) e = a.ensure(std::max<size_t>(h_bins[b].size(), 1));
+    if (e == hipSuccess) e = hipMemsetAsync(a.p, 0, a.n * sizeof(CycAux), st);
+    for (int j = 0; j < kParts; ++j) slot(b, j).fix_live = slot(b, j).cyc_live = 0;
     return e;
   }
   // DM_SWEEP=0: a FIXED launch with keys in use stays k_block_dense_fixed over every item.
@@ -652,7 +675,7 @@ struct dm_ctx {
     for (int i = 0; i < kSplitSlots; ++i) {
       SplitSlot& s = split[i];
       s.b = slot_bin(i), s.j = slot_part(i);
-      s.lo = part_lo[s.b] + s.j, s.bin_keys = &fix_keys[s.b - 3];
+      s.lo = part_lo[s.b] + s.j, s.bin_keys = &fix_keys[s.b - 3], s.bin_aux = &cyc_aux[s.b - 3];
       s.queued = {h_dq.p + i, h_dq.d + i}, s.guard = {h_guard.p + i, h_guard.d + i};
       s.rec = {h_rec.p + 2 * i, h_rec.d + 2 * i}, s.sweep = {h_sw.p + 2 * i, h_sw.d + 2 * i};
     }

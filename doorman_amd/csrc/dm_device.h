@@ -103,6 +103,32 @@ struct FixKey {
 };
 static_assert(sizeof(FixKey) == 16, "one 16-B scalar load per item");
 
+// The cycle form (k_cycle_sweep, k_block_cycle_list: a steady writeback tick on the
+// alternate column) keeps the same key with three states in `valid`, and a second half in
+// an array of its own parallel to the keys, so that every kernel that reads or clears a
+// FixKey (the in-place FIXED builds, the key-clearing update kernels) is the code it was:
+//   0  none
+//   1  recorded: the item's last tick was a cycle-form tick that computed with this capacity
+//      and kind outside learning mode, read the running sum prev_has, and left every row of
+//      the item in what is now the current column; the destination column therefore holds
+//      the item's rows from before that tick
+//   2  valid: also, the tick after it, under the same capacity and kind, computed gets
+//      bit-equal to every row of the destination column and a sum_has bit-equal to prev_has
+//      (count and sum_wants do not move in a steady build).  The per-workgroup reduction
+//      order is fixed, so the next tick's rows are already in its destination column and
+//      its record is the one read with sum_has := prev_has: a cycle of period two, of
+//      which a fixed point is the case prev_has == sum_has.
+// An update kernel that clears a key leaves state 0, and the next tick stores every row.
+// wait / skip: after a failed proof the destination rows are loaded again only after
+// `wait` ticks (doubling, at most 64), of which `skip` are still to pass.
+struct CycAux {
+  uint64_t prev_has;  // the bits of the record's sum_has before the item's last tick
+  int32_t wait;
+  int32_t skip;
+};
+static_assert(sizeof(CycAux) == 16, "one 16-B scalar load per item");
+constexpr int kCycleProbeWaitMax = 64;
+
 // One entry of a part's sweep worklist (k_fixed_sweep -> k_block_dense_list,
 // dm_tick_group.hip): the work item's own fields and its index in the bin (its item and
 // its key), so that the entry is the row kernel's only load before the rows.
@@ -111,7 +137,7 @@ struct SweepEntry {
   int32_t n;  // WorkItem::n, the hint word included
   int64_t lo;
   int32_t idx;
-  int32_t pad[3];
+  int32_t pad[3];  // the cycle form: [0] load and compare the destination rows, [1] the back-off goes on
 };
 static_assert(sizeof(SweepEntry) == 32, "one 32-B scalar load per entry");
 

@@ -29,6 +29,7 @@ struct LargeInputs {
   bool stream_written = false;   // a store beyond the Infinity Cache whose rows a call wrote since the last writeback tick
   int redo_light = 1;            // DM_REDO_LIGHT: 0 never, 1 while the redo finds nothing marked, 2 always
   bool same_write_epoch = false;  // no row written since the last speculative tick
+  bool cycle = false;            // a workgroup-bin part asks for the alternate column (dm_split_form.h CycleAuto)
 };
 
 struct LargeForm {
@@ -58,7 +59,9 @@ inline LargeForm choose_large(const LargeInputs& in) {
   // A's round 1 to be exact (b_first's terms) and no resource that the chain hands on.
   const bool spec_eligible = in.spec_chain && in.writeback && !in.recompute && !in.expl_rows && !in.may_general &&
                              in.nchunks > 0;
-  f.pingpong = in.writeback && !in.inplace && (in.alternate || spec_eligible || in.stream_written);
+  // ... and a tick for which a workgroup-bin part asks writes it for the cycle form's sake;
+  // the caller's DM_WB_INPLACE goes before that too.
+  f.pingpong = in.writeback && !in.inplace && (in.alternate || spec_eligible || in.stream_written || in.cycle);
   // spec implies pingpong && !het && b_first && writeback && nchunks > 0 (the terms the chain's
   // launches once spelled out again)
   f.spec = spec_eligible && !in.inplace;

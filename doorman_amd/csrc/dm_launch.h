@@ -39,7 +39,11 @@ hipError_t launch_bin_dense(const BinItems& w, const DevParams& p, const SplitAr
                             FixKey* keys, bool use_keys, hipStream_t st);
 hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
                             hipStream_t st);
+hipError_t launch_bin_cycle(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+                            CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st);
 hipError_t launch_count_keys(const FixKey* keys, int n, int32_t* out, hipStream_t st);
+hipError_t launch_count_cycle(const FixKey* keys, const CycAux* aux, const WorkItem* items, const ResAgg* agg, int n,
+                              int32_t* out, hipStream_t st);
 hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long* rec, unsigned long long epoch,
                                 hipStream_t st);
 hipError_t launch_bin_rest(const BinItems& w, const DevParams& p, const SplitArgs& a, int32_t* host_count,

@@ -223,7 +223,8 @@ int dm::SplitSlot::reset(dm_ctx* c, hipStream_t st) {
   kept_epoch = 0;
   upd_rows = 0;
   recount = false;
-  fix_live = 0;
+  fix_live = cyc_live = 0;
+  cyc = CycleAuto{};
   __atomic_store_n(queued.h, 0, __ATOMIC_RELAXED);
   skip = 0;
   wait = 64;
@@ -306,6 +307,6 @@ int dm::upload_plan(dm_ctx* c) {
   // (last: the allocations above keep their order)
   for (int b = 3; b < 3 + dm_ctx::kSplitBins; ++b)
     DM_HIP(c, c->reset_keys(b, st), "fixed-point keys");
-  DM_HIP(c, c->fix_count.ensure(1), "fixed-point keys");
+  DM_HIP(c, c->fix_count.ensure(2), "fixed-point keys");
   return DM_OK;
 }

@@ -172,6 +172,8 @@ int dm_create(int device, dm_ctx** out) {
   if (const char* sd = getenv("DM_STEADY")) c->steady_ok = atoi(sd);
   if (const char* fx = getenv("DM_FIXED")) c->fixed_ok = atoi(fx) != 0;
   if (const char* sw = getenv("DM_SWEEP")) c->sweep_ok = atoi(sw) != 0;
+  if (const char* cy = getenv("DM_CYCLE")) c->cycle_ok = atoi(cy) != 0;
+  if (const char* cb = getenv("DM_CYCLE_BYTES")) c->cycle_bytes = atoll(cb);
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
   // hardware queue.  Plain streams share the process's GPU_MAX_HW_QUEUES (4) queues
@@ -329,7 +331,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[15 + kNumBins];
+  int64_t v[16 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -355,7 +357,9 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
     v[13 + kNumBins] += s.last.sweep;     // ... as the sweep and the row kernel over its worklist
   }
   v[14 + kNumBins] = c->kept_refreshes;  // wants refreshes kept under dm_keep_keys since dm_create
-  const int n = 15 + kNumBins;
+  v[15 + kNumBins] = 0;  // bin parts whose last tick ran the cycle form with the keys in use
+  for (const SplitSlot& s : c->split) v[15 + kNumBins] += s.last.cycle && s.last.use_keys;
+  const int n = 16 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }
@@ -376,7 +380,7 @@ int dm_store_stats(dm_ctx* c, int64_t* out, int max) {
   std::vector<uint8_t> ex((size_t)c->R);
   DM_HIP(c, download(ex.data(), (const uint8_t*)c->expl.p, 0, c->R, c->stream), "read row states");
   DM_HIP(c, hipStreamSynchronize(c->stream), "read row states");
-  int64_t v[5] = {0, 0, 0, 0, 0};
+  int64_t v[6] = {0, 0, 0, 0, 0, 0};
   for (int64_t r = 0; r < c->R; ++r) {
     if (ex[(size_t)r] >= 2) {
       v[0] += 1;
@@ -389,6 +393,19 @@ int dm_store_stats(dm_ctx* c, int64_t* out, int max) {
   // the valid fixed-point keys of the parts whose keys are in use (SplitSlot::fix_live),
   // counted here on demand, never by the tick
   for (const SplitSlot& s : c->split) {
+    // (a part in the cycle form: its keys in state 2, and in v[5] those of them whose prev_has
+    // differs from the record's sum_has: a cycle that is no fixed point)
+    if (max > 4 && s.cyc_live == c->row_epoch && s.items() > 0 && s.bin_keys->p && s.bin_aux->p) {
+      int32_t cnt[2] = {0, 0};
+      DM_HIP(c, launch_count_cycle(s.keys(), s.aux(), c->bins[s.b].p + s.lo[0], c->agg.p, (int)s.items(), c->fix_count.p,
+                                   c->stream),
+             "count keys");
+      DM_HIP(c, download(cnt, (const int32_t*)c->fix_count.p, 0, 2, c->stream), "count keys");
+      DM_HIP(c, hipStreamSynchronize(c->stream), "count keys");
+      v[4] += cnt[0];
+      v[5] += cnt[1];
+      continue;
+    }
     if (max <= 4 || s.fix_live != c->row_epoch || s.items() <= 0 || !s.bin_keys->p) continue;
     int32_t cnt = 0;
     DM_HIP(c, launch_count_keys(s.keys(), (int)s.items(), c->fix_count.p, c->stream), "count keys");
@@ -396,6 +413,6 @@ int dm_store_stats(dm_ctx* c, int64_t* out, int max) {
     DM_HIP(c, hipStreamSynchronize(c->stream), "count keys");
     v[4] += cnt;
   }
-  for (int i = 0; i < 5 && i < max; ++i) out[i] = v[i];
-  return 5;
+  for (int i = 0; i < 6 && i < max; ++i) out[i] = v[i];
+  return 6;
 }

@@ -13,6 +13,8 @@
 //   FIXED           the steady build of a writeback tick in place, rewriting every key ...
 //   FIXED with keys ... or trusting them (use_keys) ...
 //   the sweep       ... as k_fixed_sweep and k_block_dense_list over its worklist
+//   the cycle form  FIXED's twin for a steady writeback tick on the alternate column:
+//                   k_cycle_sweep and k_block_cycle_list (dm_device.h CycAux)
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -43,6 +45,15 @@ struct PartForm {
   // every rows_changed() clears it, and the first FIXED launch after that ignores and
   // rewrites every key.
   uint64_t fix_live = 0;
+  // The cycle form (with use_keys: trusting the keys' states, else rewriting every key) and
+  // the part's cyc_live after this tick, under fix_live's discipline: the row epoch when the
+  // cycle form is launched, else 0.  A key's states speak of both has columns, so nothing but
+  // cycle-form launches may have touched the part: a non-writeback tick writes its gets into
+  // the alternate column, an in-place tick leaves it behind, and so every other launch of
+  // the part, like every rows_changed(), ends the keys.  A FIXED launch clears cyc_live and
+  // a cycle-form launch fix_live: neither trusts the other's keys.
+  bool cycle = false;
+  uint64_t cyc_live = 0;
 };
 
 // The back-off of the split form.  The 128-thread bins split by the dense hint unless the
@@ -75,6 +86,7 @@ struct FormInputs {
   uint64_t fix_live = 0;     // the part's, before this tick
   uint64_t sw_epoch = 0;     // the sweep record: the epoch of the count the device last told ...
   int64_t sw_told = 0;       // ... and the count
+  uint32_t sw_stamp = 0;     // ... and, from the cycle form's row kernel, the stamp of the launch that told it
   int64_t refreshed = 0;     // kept refreshes' values and kept updates' rows since the last tick: each may have cleared a key
   int n = 0;                 // the part's items
   int64_t queued = 0;        // items the last split tick the host has heard of queued
@@ -82,6 +94,10 @@ struct FormInputs {
   bool keep_updates = false;  // the bit is set
   bool rec_kept = false;      // the record is the host's copy from before a kept update: an estimate, no proof
   int64_t upd_rows = 0;       // rows kept updates wrote since the record's count
+  // The cycle form.  The defaults give the answers choose_form gave without it.
+  bool cycle_ok = true;     // DM_CYCLE
+  bool cycle_want = false;  // the tick writes the alternate column for it: the caller's DM_WB_ALTERNATE, or a part asked (CycleAuto)
+  uint64_t cyc_live = 0;    // the part's, before this tick
 };
 
 // `tried`: try_split's answer (asked only of a part with hints in a bin that splits).
@@ -106,7 +122,8 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   // are together at most a quarter of the part's items, try_split's bound for "too many for
   // the rest kernel".  Above it the part runs the forms it always ran.
   const int64_t odd = (int64_t)(uint32_t)in.rec_counts + (int64_t)(in.rec_counts >> 32) + in.upd_rows;
-  const bool few = in.keep_updates && in.writeback && in.inplace && 4 * odd <= in.n;
+  const bool cycle_tick = in.cycle_ok && in.fixed_ok && in.cycle_want && in.writeback && !in.inplace;
+  const bool few = in.keep_updates && in.writeback && (in.inplace || cycle_tick) && 4 * odd <= in.n;
   const bool clean = in.rec_counts == 0 && !in.rec_kept;
   const bool steady_form = in.steady_ok && in.nparts == 1 && verified && (clean || few) && !in.recompute;
   f.steady = steady_form && in.steady_ok != 2;
@@ -122,6 +139,12 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   f.use_keys = f.fixed && in.fix_live == in.row_epoch;
   f.fix_live = f.fixed ? in.row_epoch : 0;
   f.sweep = f.use_keys && in.sweep_ok;
+  // The cycle form: the same steady conditions on a writeback tick that writes the alternate
+  // column because the caller or a part asked for it (a tick that alternates for the large
+  // chain's sake or after a write keeps the plain builds).
+  f.cycle = f.steady && cycle_tick;
+  if (f.cycle) f.use_keys = in.cyc_live == in.row_epoch;
+  f.cyc_live = f.cycle ? in.row_epoch : 0;
   // Grids are hints: both kernels stride over their lists, so correctness never depends
   // on them.  The rest kernel's is sized from the last split tick's queue (an empty queue
   // costs 16 workgroups that read one count); the row kernel's from the count the device
@@ -134,6 +157,105 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
     f.list_grid = (int)std::min<int64_t>(in.n, std::max<int64_t>(16, told + told / 8 + (told ? 64 : 0)));
   }
   return f;
+}
+
+// When a part asks for the alternate column by itself.  A caller's DM_WB_ALTERNATE gets the
+// cycle form wherever the steady conditions hold; without a flag only a store beyond the
+// Infinity Cache (48 * N > kStreamBytes) ever leaves in-place FIXED, and only once in place
+// has shown it is not enough: the part's in-place sweep has told the host a non-empty
+// worklist on kCycleTrigger consecutive ticks of one row epoch (items that are never at a
+// fixed point).  The part then asks, and a tick goes alternate if any part asks.  It is
+// judged by the count of its kCycleSettle-th cycle-form tick (the first rewrites every key,
+// the second proves).  The host enqueues ticks far ahead of the device, so a tick of its own
+// count proves nothing about what the device has told: every cycle-form launch of an engaged
+// part carries a stamp (seq) that the row kernel tells with its count, on every tick until
+// the judgement, and the host judges when the told stamp has reached seq0 + kCycleSettle.
+// It stays if that count fell to half of what it was when it engaged at most; otherwise it returns to in place and tries again after `wait`
+// ticks, doubling from kCycleWait0 to kCycleWaitMax, as try_split does.  A new row epoch
+// starts the count over (the keys are gone with it) and keeps the wait.  A store without
+// persistent non-fixed items never gets here.
+// Items that kept refreshes and updates put on the list do not count: a row written under
+// dm_keep_keys clears its resource's key, which is back within a few ticks, and on such a store
+// the alternate column only loses (it stores every run where in place skips the unchanged
+// ones: profiles/cycle_ab.md).  A tick counts towards the trigger only when the told count
+// exceeds `recent`, a running sum of the kept rows of about the last eight ticks.
+// An engaged part whose ticks cannot run the form (it stopped being steady, or the caller
+// keeps it in place) gets no stamp and so no judgement: after kCycleIdle such ticks in a row
+// it gives the ask up as a failed try does, so that it does not keep every other part off
+// in-place FIXED until the next row epoch.
+// The told word's high half: a part back in place tells through k_block_dense_list, which
+// writes no stamp and tells only a changed count, so the last cycle-form stamp may stay there
+// under an in-place count.  It is harmless: only an engaged part reads it, against a seq0
+// taken at or after that stamp, and kCycleSettle launches later at the earliest.
+constexpr int kCycleTrigger = 8, kCycleSettle = 8, kCycleWait0 = 64, kCycleWaitMax = 4096, kCycleIdle = 16;
+struct CycleAuto {
+  bool on = false;  // the part asks for the alternate column
+  int seen = 0;     // consecutive in-place sweep ticks with a non-empty list told
+  uint32_t seq = 0, seq0 = 0;  // the part's cycle-form launches while engaged, ever, and when it last engaged
+  bool judged = false;
+  int idle = 0;  // consecutive ticks of an engaged part that could not run the form
+  int64_t recent = 0;  // rows kept refreshes and updates wrote lately: recent := recent - recent / 8 + this tick's
+  int skip = 0, wait = kCycleWait0;
+  int64_t base = 0;  // the count told when it engaged
+  uint64_t epoch = 0;
+};
+struct CycleAutoIn {
+  bool cycle_ok = true;
+  bool stream_store = false;  // 48 * N > kStreamBytes
+  uint64_t row_epoch = 0;
+  bool told_valid = false;  // the sweep record is of this row epoch
+  int64_t told = 0;
+  uint32_t told_seq = 0;  // the stamp told with it (0: an in-place sweep's count)
+  int64_t refreshed = 0;  // FormInputs::refreshed: rows kept refreshes and updates wrote since the last tick
+};
+// Once per part and tick, after the form is chosen; returns whether the part asks.
+inline bool cycle_auto_step(CycleAuto& a, const CycleAutoIn& in, const PartForm& f) {
+  if (!in.cycle_ok || !in.stream_store) {
+    a = CycleAuto{};
+    return false;
+  }
+  a.recent = a.recent - a.recent / 8 + in.refreshed;
+  if (a.epoch != in.row_epoch) {
+    a.on = false;
+    a.seen = 0;
+    a.epoch = in.row_epoch;
+  }
+  if (!a.on) {
+    if (a.skip > 0) {
+      --a.skip;
+      a.seen = 0;
+      return false;
+    }
+    a.seen = (f.sweep && in.told_valid && in.told > a.recent) ? a.seen + 1 : 0;
+    if (a.seen >= kCycleTrigger) {
+      a.on = true;
+      a.judged = false;
+      a.seen = a.idle = 0;
+      a.seq0 = a.seq;
+      a.base = in.told;
+    }
+    return a.on;
+  }
+  if (f.cycle) ++a.seq;  // this launch's stamp (a tick that could not run the form has none)
+  a.idle = f.cycle ? 0 : a.idle + 1;
+  if (a.idle >= kCycleIdle) {
+    a.on = false;
+    a.skip = a.wait;
+    a.wait = std::min(2 * a.wait, kCycleWaitMax);
+    return false;
+  }
+  const uint32_t done = in.told_seq - a.seq0;  // cycle-form ticks of this try the device has told of
+  if (!a.judged && in.told_valid && done >= (uint32_t)kCycleSettle && done < 0x80000000u) {
+    a.judged = true;
+    if (2 * in.told <= a.base) {
+      a.wait = kCycleWait0;
+    } else {
+      a.on = false;
+      a.skip = a.wait;
+      a.wait = std::min(2 * a.wait, kCycleWaitMax);
+    }
+  }
+  return a.on;
 }
 
 }  // namespace dm

@@ -155,6 +155,7 @@ struct Tick {
   int64_t now_ns;
   uint32_t flags;
   bool wb = false, pingpong = false;
+  bool cycle_want = false;  // the tick writes the alternate column for the cycle form's sake (FormInputs::cycle_want)
   DevParams p{};
   LargeForm lf;  // the output column and the chain's form (dm_large_form.h), chosen in outputs()
   hipStream_t st = nullptr, s_large = nullptr, s_small = nullptr;
@@ -232,6 +233,8 @@ int Tick::outputs() {
   in.stream_written = c->N * 48 > kStreamBytes && c->wb_epoch != c->row_epoch;
   in.redo_light = lc.redo_light;
   in.same_write_epoch = lc.redo_epoch == c->write_epoch;
+  in.cycle = c->cycle_ok && c->cycle_asked();
+  cycle_want = in.cycle || in.alternate;
   lf = choose_large(in);
   lc.live_ok = false;
   pingpong = lf.pingpong;
@@ -391,6 +394,9 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   in.writeback = wb;
   in.inplace = pt.p.out_gets == pt.p.has;
   in.fix_live = sl.fix_live;
+  in.cycle_ok = c->cycle_ok;
+  in.cycle_want = cycle_want;
+  in.cyc_live = sl.cyc_live;
   in.refreshed = c->kept_rows;
   in.keep_updates = (c->keep_mode & kKeepUpdates) != 0;
   in.n = n;
@@ -400,6 +406,20 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   if (tried) sl.read_records(in);
   const PartForm f = sl.last = choose_form(in, tried);
   sl.fix_live = f.fix_live;  // the key rule (SplitSlot::fix_live): every launch of the part passes here
+  sl.cyc_live = f.cyc_live;
+  // whether the part asks the next tick for the alternate column (only a tick without the
+  // caller's column flags tells: with either the choice is the caller's)
+  if (wb && !(flags & (DM_WB_INPLACE | DM_WB_ALTERNATE))) {
+    CycleAutoIn ai;
+    ai.cycle_ok = c->cycle_ok;
+    ai.stream_store = c->N * 48 > c->cycle_bytes;
+    ai.row_epoch = c->row_epoch;
+    ai.told_valid = in.sw_epoch == c->row_epoch;
+    ai.told = in.sw_told;
+    ai.told_seq = in.sw_stamp;
+    ai.refreshed = in.refreshed;
+    cycle_auto_step(sl.cyc, ai, f);
+  }
   int rc = DM_OK;
   if (!f.split)
     rc = launch_mixed(pt);
@@ -414,8 +434,8 @@ int Tick::launch_dense_form(Part& pt, const PartForm& f) {
   SplitSlot& sl = pt.sl;
   // the guard and the tick's event go to a dense launch that no rest launch follows
   const SplitArgs a{sl.queue.p, sl.qcnt.p, sl.qpar, gl, gc, f.skip_rest ? sl.guard.d : nullptr};
-  FixKey* keys = f.fixed ? sl.keys() : nullptr;
-  if (f.sweep) {
+  FixKey* keys = f.fixed || f.cycle ? sl.keys() : nullptr;
+  if (f.sweep || f.cycle) {
     DM_HIP(c, sl.sw_list.ensure((size_t)pt.w.n), "sweep list");
     if (!sl.sw_cnt.p) {
       DM_HIP(c, sl.sw_cnt.ensure(4), "sweep count");  // two-slot count + the last {count, epoch} told the host
@@ -424,6 +444,13 @@ int Tick::launch_dense_form(Part& pt, const PartForm& f) {
     }
   }
   DM_HIP(c, timed(KC_DENSE3 + (sl.b - 3), pt.s, [&] {
+           if (f.cycle)
+             return launch_bin_cycle(pt.w, pt.p, a,
+                                     SweepArgs{keys, sl.sw_list.p, sl.sw_cnt.p, sl.lpar,
+                                               (unsigned long long*)sl.sweep.d, (unsigned long long)c->row_epoch,
+                                               f.list_grid},
+                                     sl.aux(), f.use_keys, sl.cyc.on ? sl.cyc.seq : 0u, sl.cyc.on && !sl.cyc.judged,
+                                     pt.s);
            if (f.sweep)
              return launch_bin_sweep(pt.w, pt.p, a,
                                      SweepArgs{keys, sl.sw_list.p, sl.sw_cnt.p, sl.lpar,
@@ -433,7 +460,7 @@ int Tick::launch_dense_form(Part& pt, const PartForm& f) {
            return launch_bin_dense(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, f.steady, keys, f.use_keys, pt.s);
          }),
          "group kernel (dense split)");
-  if (f.sweep) sl.lpar ^= 1;
+  if (f.sweep || f.cycle) sl.lpar ^= 1;
   return DM_OK;
 }
 

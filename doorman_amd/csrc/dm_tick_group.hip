@@ -100,20 +100,28 @@ __device__ __forceinline__ void hand_off(FixKey* key, const FixKey& fk, int use_
 // LIST: the caller is a loop over items (k_block_dense_list).  Behind an earlier item's
 // stores the compiler loads the record with vector loads, a register per dword and lane
 // through every pass (128 x 8: 88 VGPRs against 65); the record is moved back to SGPRs.
+// CYCLE (k_block_cycle_list alone): the FIXED list build on the alternate column, p.out_gets
+// != p.has (dm_device.h CycAux has the key's states and the proof).  probe: the item's key is
+// in state 1 under this capacity and kind (the sweep saw to it, SweepEntry::pad: no dependent
+// load): the destination rows are loaded with the others and the SKIP ballot compares against
+// them -- skipping an equal run is always correct, only the key's conclusion rests on what
+// the destination held.  Without it every run is stored.  carry: the back-off goes on.
 template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false, bool FIXED = false,
-          bool LIST = false>
+          bool LIST = false, bool CYCLE = false>
 __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
                                               Lds<G>& lds, int32_t* general_list, int32_t* general_count,
                                               int32_t* queue = nullptr, int32_t* qcount = nullptr,
                                               int32_t qidx = 0, int32_t* guard = nullptr, int qcap = 0,
                                               FixKey* key = nullptr, const FixKey fk = FixKey{0, 0, 0},
-                                              int use_keys = 0) {
+                                              int use_keys = 0, CycAux* aux = nullptr,
+                                              const CycAux ax = CycAux{0, 0, 0}, int probe = 0, int carry = 0) {
   // the dense state (below): every workgroup kernel tracks it and writes the hints;
   // only the 128-thread mixed kernel and the dense-only kernels load by the hint
   constexpr bool kDense = G >= 128 || (G == 64 && R >= 16);  // (64 x 16: kBin4Wave)
   constexpr bool kHintLoad = (G == 128 && MODE == kMixed) || MODE == kDenseOnly;
   static_assert(!STEADY || MODE == kDenseOnly, "the steady build is a dense-only build");
   static_assert(!FIXED || (SKIP && STEADY), "the fixed-point build is a steady build that skips unchanged stores");
+  static_assert(!CYCLE || (FIXED && LIST), "the cycle build is a list build of the fixed-point build");
   const int seg = wi.seg;
   const int64_t lo = wi.lo;
   const int n = kDense ? wi.n & 0xFFFF : wi.n;
@@ -182,6 +190,17 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
       w[k] = *col_at(wb, u);
       h[k] = *col_at(hb, u);
       sr[k] = hint;  // uniform: the mask's rows are taken out below (one register, not R)
+    }
+  }
+  // CYCLE: the destination rows of a probing item, in flight with the others (16 more
+  // registers for R = 8 while they wait; profiles/cycle_isa.md has each build's count)
+  [[maybe_unused]] double d[CYCLE ? R : 1];
+  if constexpr (CYCLE) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int i = k * G + t;
+      const unsigned u = (unsigned)(i < n ? i : n - 1);
+      d[k] = probe ? *col_at((const double*)p.out_gets + lo, u) : 0.0;
     }
   }
   const Res rs = LIST ? uniform(load_res(p, seg)) : load_res(p, seg);
@@ -419,7 +438,11 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
     if constexpr (SKIP) {
       const bool lv = live >> k & 1;
       const double g = lv ? row_gets(rs, ps, C, eq, cl, b, fu, w[k], h[k], s[k]) : 0.0;
-      const bool st = __ballot(__double_as_longlong(g) != __double_as_longlong(h[k])) != 0;
+      bool st;
+      if constexpr (CYCLE)
+        st = !probe || __ballot(__double_as_longlong(g) != __double_as_longlong(d[k])) != 0;
+      else
+        st = __ballot(__double_as_longlong(g) != __double_as_longlong(h[k])) != 0;
       if constexpr (FIXED) stored |= st;
       if (!lv) {  // released by Clean: no lease
         put_released<kGroupNT<G>>(p, lo, u, (relm >> k & 1) ? (int)kSubReleased : sr[k], st);
@@ -496,6 +519,32 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
       }
       delta.v = r.v;
       any = r.n;
+    }
+    if constexpr (CYCLE) {
+      // the key after a cycle-form tick: state 2 when the probe stored no run and the sum
+      // written is the one from before the last tick; else state 1 (every row of the item
+      // is in the column written or was equal there).  Both sums of a valid key must
+      // survive the sweep's `+ 0.0` (write_resource): never -0.0 or a signalling NaN.
+      if (t == 0) {
+        write_resource(p, seg, rs, cl, delta.v, hint);
+        const uint64_t was = (uint64_t)__double_as_longlong(rs.agg_has);
+        const uint64_t now_has = (uint64_t)__double_as_longlong(cl.sum_has + delta.v);
+        const bool stable = (uint64_t)__double_as_longlong(__longlong_as_double((long long)now_has) + 0.0) == now_has &&
+                            (uint64_t)__double_as_longlong(rs.agg_has + 0.0) == was;
+        const bool ok = probe && !any && now_has == ax.prev_has && stable && !rs.learning;
+        int wait = 0, skip = 0;
+        if (!ok && probe) {
+          wait = ax.wait < 1 ? 1 : (2 * ax.wait > kCycleProbeWaitMax ? kCycleProbeWaitMax : 2 * ax.wait);
+          skip = wait;
+        } else if (!ok && carry) {
+          wait = ax.wait;
+          skip = ax.skip;
+        }
+        const bool rec = !rs.learning;
+        *key = FixKey{rec ? (uint64_t)__double_as_longlong(C) : 0ull, rec ? rs.kind : 0, rec ? (ok ? 2 : 1) : 0};
+        *aux = CycAux{was, wait, skip};
+      }
+      return;
     }
     if (t == 0) {
       write_resource(p, seg, rs, cl, delta.v, hint);
@@ -706,6 +755,116 @@ __global__ __launch_bounds__(G) void k_block_dense_list(DevParams p, WorkItem* _
       group_segment<G, R, kDenseOnly, true, true, true, true>(p, wi, items + e.idx, t, lds, general_list,
                                                               general_count, queue, qcnt + par, e.idx, nullptr, nitems,
                                                               keys + e.idx, FixKey{0, 0, 0}, 1);
+    }
+    __syncthreads();  // the next item reuses the single-use LDS slots
+  }
+}
+
+// The cycle form: the sweep and the row kernel of a steady writeback tick that writes the
+// alternate column (dm_device.h CycAux: the key's states and the proof; dm_split_form.h: when
+// the host launches it).  k_cycle_sweep is k_fixed_sweep with the generalised test: an item
+// whose key is in state 2 and passes the steady `rest` test and the capacity / kind / learning
+// test reproduces its state of two ticks ago, which its destination column still holds: the
+// lane writes its record with sum_has := prev_has (write_fixed's record otherwise: follow_exp,
+// the published block, the state byte) and sets prev_has to the sum just read -- a store only
+// where the two differ, so an item at a fixed point writes no key.  Every other item goes to
+// the worklist with its key in memory cleared, and with what the row kernel must know before
+// its loads in the entry (SweepEntry::pad): whether to load the destination rows (state 1
+// under the same capacity and kind, the back-off run out) and whether the back-off goes on.
+// Without use_keys (the part's last tick was no cycle-form tick, or a call wrote rows since)
+// every key counts as state 0: every item is listed, stores every run and gets a fresh key.
+__global__ __launch_bounds__(1024) void k_cycle_sweep(DevParams p, const WorkItem* __restrict__ items, int nitems,
+                                                      FixKey* __restrict__ keys, CycAux* __restrict__ aux,
+                                                      SweepEntry* __restrict__ list, int32_t* lcnt, int par,
+                                                      int use_keys) {
+  __shared__ int wtot[16];
+  const int i = (int)(blockIdx.x * 1024u + threadIdx.x);
+  if (i == 0) lcnt[par ^ 1] = 0;
+  bool app = false;
+  int probe = 0, carry = 0;
+  WorkItem wi{0, 0, 0};
+  if (i < nitems) {
+    wi = items[i];
+    const FixKey fk = keys[i];
+    const CycAux ax = aux[i];
+    const int hw = wi.n >> 16;
+    const int state = use_keys ? fk.valid : 0;
+    bool done = false;
+    if (hw != 0 && state != 0) {
+      const Res rs = load_res(p, wi.seg);
+      const int hint = hw & 0xFF;
+      const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
+      if (!rest && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
+        if (state == 2) {
+          write_resource(p, wi.seg, rs, Clean{rs.agg_count, __longlong_as_double((long long)ax.prev_has), rs.agg_wants},
+                         0.0, hint);
+          const uint64_t was = (uint64_t)__double_as_longlong(rs.agg_has);
+          if (ax.prev_has != was) aux[i].prev_has = was;
+          done = true;
+        } else if (ax.skip > 0) {
+          aux[i].skip = ax.skip - 1;
+          carry = 1;
+        } else {
+          probe = carry = 1;
+        }
+      }
+    }
+    if (!done) {
+      app = true;
+      if (fk.valid) keys[i] = FixKey{0, 0, 0};
+    }
+  }
+  const uint64_t bal = __ballot(app);
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wtot[wave] = __popcll(bal);
+  __syncthreads();
+  if (threadIdx.x == 0) {  // the waves' totals -> their first slots in the list
+    int tot = 0;
+    for (int w = 0; w < 16; ++w) tot += wtot[w];
+    int base = tot > 0 ? atomicAdd(lcnt + par, tot) : 0;
+    for (int w = 0; w < 16; ++w) {
+      const int c = wtot[w];
+      wtot[w] = base;
+      base += c;
+    }
+  }
+  __syncthreads();
+  const int slot = wtot[wave] + pre;  // (below nitems: the slot's count started at zero)
+  if (app && slot < nitems) list[slot] = SweepEntry{wi.seg, wi.n, wi.lo, i, {probe, carry, 0}};
+}
+
+template <int G, int R>
+__global__ __launch_bounds__(G) void k_block_cycle_list(DevParams p, WorkItem* __restrict__ items, int nitems,
+                                                        const SweepEntry* __restrict__ list, int32_t* lcnt, int lpar,
+                                                        unsigned long long* host_count, unsigned long long epoch,
+                                                        int32_t* queue, int32_t* qcnt, int par, int32_t* general_list,
+                                                        int32_t* general_count, FixKey* __restrict__ keys,
+                                                        CycAux* __restrict__ aux, unsigned stamp, int tell) {
+  __shared__ Lds<G> lds;
+  const int count = min(lcnt[lpar], nitems);
+  SweepEntry e = list[blockIdx.x];  // with the count (the grid is at most nitems: in the list, used only below count)
+  // (the count's high half: the host's stamp of this launch; tell: told whether it changed or
+  // not, while the host waits to judge the form by a count of a known tick -- CycleAuto)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (tell || lcnt[2] != count || lcnt[3] != (int32_t)epoch)) {
+    __hip_atomic_store(host_count, (unsigned long long)(unsigned)count | (unsigned long long)stamp << 32,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    lcnt[2] = count;
+    lcnt[3] = (int32_t)epoch;
+  }
+  for (int q = blockIdx.x; q < count; q += gridDim.x) {
+    if (q != (int)blockIdx.x) e = uniform(list[q]);
+    const WorkItem wi{e.seg, e.n, e.lo};
+    int t = (int)threadIdx.x;  // (anew for every item: k_block_dense_list)
+    asm volatile("" : "+v"(t));
+    if ((wi.n >> 16) == 0) {  // (its key is invalid in memory: the sweep saw to it)
+      if (threadIdx.x == 0) hand_off<false>(nullptr, FixKey{0, 0, 0}, 0, queue, qcnt, par, e.idx, nitems, nullptr);
+    } else {
+      const CycAux ax = uniform(aux[e.idx]);
+      group_segment<G, R, kDenseOnly, true, true, true, true, true>(
+          p, wi, items + e.idx, t, lds, general_list, general_count, queue, qcnt + par, e.idx, nullptr, nitems,
+          keys + e.idx, FixKey{0, 0, 0}, 0, aux + e.idx, ax, e.pad[0], e.pad[1]);
     }
     __syncthreads();  // the next item reuses the single-use LDS slots
   }
@@ -1137,6 +1296,64 @@ hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitAr
                                                      a.queue, a.qcnt, a.par, a.glist, a.gcount, sw.keys);
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// The cycle form (k_cycle_sweep): a steady writeback tick on the alternate column.  The first
+// such launch of a part (use_keys false) lists and rewrites every item through the same two
+// kernels; the rest launch follows either.
+hipError_t launch_bin_cycle(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+                            CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st) {
+  const int n = w.n;
+  if (n <= 0) return hipSuccess;
+  if (!(p.writeback && p.out_gets != p.has) || !sw.keys || !aux) return hipErrorInvalidValue;
+  const dim3 lg((unsigned)std::max(1, std::min(n, use_keys ? sw.list_grid : n)));
+  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    k_cycle_sweep<<<dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, st>>>(p, w.items, n, sw.keys, aux, sw.list,
+                                                                              sw.lcnt, sw.lpar, use_keys ? 1 : 0);
+    k_block_cycle_list<G, R><<<lg, dim3(G), 0, st>>>(p, w.items, n, sw.list, sw.lcnt, sw.lpar, sw.host_count, sw.epoch,
+                                                     a.queue, a.qcnt, a.par, a.glist, a.gcount, sw.keys, aux, stamp,
+                                                     tell ? 1 : 0);
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// dm_store_stats for a part in the cycle form: out[0] the keys in state 2, out[1] those of
+// them whose prev_has differs from the record's sum_has (the items in a cycle that is no
+// fixed point)
+__global__ __launch_bounds__(1024) void k_count_cycle(const FixKey* __restrict__ keys, const CycAux* __restrict__ aux,
+                                                      const WorkItem* __restrict__ items, const ResAgg* __restrict__ agg,
+                                                      int n, int32_t* out) {
+  __shared__ int part[16], part_c[16];
+  int c = 0, y = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const bool v = keys[i].valid == 2;
+    c += v ? 1 : 0;
+    y += v && aux[i].prev_has != (uint64_t)__double_as_longlong(agg[items[i].seg].sum_has) ? 1 : 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_down(c, o, 64);
+    y += __shfl_down(y, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6] = c;
+    part_c[threadIdx.x >> 6] = y;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0, tot_c = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+      tot += part[w];
+      tot_c += part_c[w];
+    }
+    out[0] = tot;
+    out[1] = tot_c;
+  }
+}
+hipError_t launch_count_cycle(const FixKey* keys, const CycAux* aux, const WorkItem* items, const ResAgg* agg, int n,
+                              int32_t* out, hipStream_t st) {
+  k_count_cycle<<<1, 1024, 0, st>>>(keys, aux, items, agg, n, out);
+  return hipGetLastError();
 }
 
 // dm_store_stats: the valid keys among n (one workgroup, on demand; never on the tick)

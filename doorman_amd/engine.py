@@ -18,7 +18,7 @@ from .workloads import CFG_FIELDS
 _BIN_NAMES = ("small_tiles", "sub16x4", "sub32x4", "wave64x4", "block128x4", "block128x8", "block256x8",
               "block2k4k", "sub8x2", "sub16x2", "large_resources", "large_chunks", "leases", "bin_shapes",
               "redo_resident_cap", "spec_fits", "aux_own_queues", "stream_parts", "queue_perm", "wb_inplace",
-              "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes")
+              "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes", "cycle_parts")
 
 
 def _ptr(a):
@@ -371,11 +371,13 @@ class Engine:
         """dm_store_stats: dense resources (read at 24 B per lease) and their rows,
         resources that may hold explicit expiries, resources, and the workgroup-bin resources
         whose fixed-point key is valid in a part whose keys are in use (their next in-place
-        tick loads no row of them while their capacity and kind stay)."""
-        arr = (ctypes.c_int64 * 5)()
-        self._chk(self._L.dm_store_stats(self._ctx, arr, 5))
+        tick loads no row of them while their capacity and kind stay; in a part in the cycle
+        form: whose two-tick proof holds), and those of them whose record alternates between
+        two running sums (a cycle of period two that is no fixed point)."""
+        arr = (ctypes.c_int64 * 6)()
+        self._chk(self._L.dm_store_stats(self._ctx, arr, 6))
         return {"dense_resources": int(arr[0]), "dense_leases": int(arr[1]), "explicit_resources": int(arr[2]),
-                "resources": int(arr[3]), "fixed_items": int(arr[4])}
+                "resources": int(arr[3]), "fixed_items": int(arr[4]), "cycling_items": int(arr[5])}
 
 
 def device_count() -> int:

@@ -108,7 +108,14 @@ extern "C" {
    may take the speculative large chain (a store with a resource above 4096 rows), and on
    a store beyond the Infinity Cache the first writeback tick after a call that wrote
    rows, writes a second has column that becomes the store's after the tick (8 B per
-   lease of HBM).  dm_plan_info slot 19 reports which one the last tick wrote. */
+   lease of HBM).  dm_plan_info slot 19 reports which one the last tick wrote.
+   On the alternate column a steady workgroup-bin part runs the cycle form when the caller
+   asked for the column (DM_WB_ALTERNATE): a resource whose tick reproduces its state of two
+   ticks ago finds that state still in the destination column and moves no row.  Without
+   either flag a store beyond the Infinity Cache goes alternate for that form by itself once
+   its in-place ticks have kept finding resources that are never at a fixed point (an
+   oversubscribed FairShare resource's grants wobble with period two), and returns to in
+   place if that does not at least halve them.  DM_WB_INPLACE always keeps the tick in place. */
 #define DM_WB_INPLACE 8u    /* force in-place writeback */
 #define DM_WB_ALTERNATE 16u /* force the alternate columns */
 #define DM_DEFER_JOIN 32u   /* with DM_ASYNC: a tick whose work classes run on the context's
@@ -566,14 +573,22 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * workgroup-bin parts whose last tick ran the dense kernel's steady builds, and those of
  * them that ran with the fixed-point keys in use, and those of them that ran as the sweep,
  * and (slot 23) the wants refreshes the context kept under dm_keep_keys since it was
- * created; returns 24 */
+ * created (a caller that passes max = 24 gets what it got while the call returns 24), and
+ * (slot 24) the workgroup-bin parts whose last tick ran the cycle form with the keys in use
+ * (a steady writeback tick on the alternate column: a resource in a proven cycle of period
+ * two, of which a fixed point is one, is not read at all; DM_CYCLE=0 in the environment,
+ * read when the context is created, keeps the form off and every tick on the column it
+ * chose before); returns 25 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
  * their rows, resources that may hold explicit expiries, resources, and (only when max
  * > 4: it is counted on the device on demand) the workgroup-bin resources whose
  * fixed-point key is valid in a part whose keys are in use: while their capacity and kind
- * stay, the next writeback tick in place loads no row of them; returns 5 */
+ * stay, the next writeback tick in place loads no row of them (in a part whose last tick
+ * ran the cycle form: the keys whose two-tick proof holds), and (max > 5) those of them in
+ * the cycle form whose record alternates between two running sums, a cycle that is no
+ * fixed point; returns 6 */
 int dm_store_stats(dm_ctx* ctx, int64_t* out, int max);
 
 /* ---- round-oriented GetCapacity dispatch (dm_server.cpp) ----

@@ -55,12 +55,13 @@ from sweep_share import all_fixed_store  # noqa: E402
 
 NOW = W.NOW_NS
 STEP = 1.0 / 1024
+LIB = None  # --lib: another build of the library (make variant), for a run against a parent commit
 
 
 def engines(snap, modes=(0, 1)):
     """(mode off, mode on), both at the store's fixed point with keys in use."""
     from doorman_amd.engine import Engine
-    pair = (Engine(0), Engine(0))
+    pair = (Engine(0, LIB), Engine(0, LIB))
     for e, m in zip(pair, modes):
         e.keep_keys(m)
     R = len(snap["seg_off"]) - 1
@@ -269,7 +270,9 @@ if __name__ == "__main__":
     ap.add_argument("--writer", default="refresh",
                     help="refresh (modes 0 and 1), or a list of release, arrival, batch (modes 1 and 3)")
     ap.add_argument("--out")
+    ap.add_argument("--lib", default=None, help="another build of the library (tools/ab_libs/NAME.so)")
     a = ap.parse_args()
+    LIB = a.lib
     rng = np.random.default_rng(3)
     t0 = time.perf_counter()
     snap = all_fixed_store(a.resources)

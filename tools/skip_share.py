@@ -13,6 +13,12 @@ fixed_share() adds what a tick that recognises such a resource before its passes
 see unchanged besides the rows: the record it reads (the running sums, and with the
 exchange the template's capacity and kind, which k_hier_tick rewrites every step).  A
 dump without templates (--hier off) has none to change.
+
+cycle_share() takes three dumps one step apart each (--steps 20, 21, 22) and tells the
+resources at a fixed point from those in a cycle of period two (the whole sampled state equal
+two ticks apart, not one) and those that differ at both distances:
+
+  python tools/skip_share.py --cycle A B C [ROWS_PER_RESOURCE]
 """
 import os
 import sys
@@ -81,7 +87,53 @@ def fixed_share(dir_a, dir_b, per_res=1000):
     return out
 
 
+def _record_same(dir_a, dir_b, ids):
+    """Per sampled resource: the running sums and, where the dumps hold them, the template's
+    capacity and kind are bit-equal between the two dumps."""
+    same = np.ones(len(ids), bool)
+    for n in ("resource_count", "resource_sum_has", "resource_sum_wants",
+              "template_capacity", "template_kind"):
+        a, b = _ld(dir_a, n), _ld(dir_b, n)
+        if a is not None and b is not None:
+            same &= (_bits(a) == _bits(b))[ids]
+    return same
+
+
+def cycle_share(dir_a, dir_b, dir_c, per_res=1000):
+    """From three dumps one timed step apart each (A, B, C): per sampled resource, whether
+    its whole sampled state (every sampled row's lease_gets, the running sums, the template)
+    is bit-equal one tick apart (A = B and B = C: a fixed point), only two ticks apart
+    (A = C, A != B: a cycle of period two), or at neither distance."""
+    _, _, ids, _, rows_ab = _rows_by_resource(dir_a, dir_b, per_res)
+    _, _, ids_bc, _, rows_bc = _rows_by_resource(dir_b, dir_c, per_res)
+    _, _, ids_ac, _, rows_ac = _rows_by_resource(dir_a, dir_c, per_res)
+    assert np.array_equal(ids, ids_bc) and np.array_equal(ids, ids_ac)
+    ab = rows_ab & _record_same(dir_a, dir_b, ids)
+    bc = rows_bc & _record_same(dir_b, dir_c, ids)
+    ac = rows_ac & _record_same(dir_a, dir_c, ids)
+    fixed = ab & bc
+    cycle2 = ac & ~ab
+    neither = ~ac & ~ab
+    not_fixed = ~fixed
+    # what differs between A and B in a two-cycle: rows, or only the record
+    cyc_rows = cycle2 & ~rows_ab
+    return {"resources_sampled": int(len(ids)),
+            "fixed_A=B=C": float(fixed.mean()),
+            "not_fixed": float(not_fixed.mean()),
+            "cycle2_A=C_A!=B": float(cycle2.mean()),
+            "cycle2_with_rows_changing": float(cyc_rows.mean()),
+            "differs_at_both_distances": float(neither.mean()),
+            "A=B_but_B!=C": float((ab & ~bc).mean()),
+            "cycle2_share_of_not_fixed": float(cycle2.sum() / max(int(not_fixed.sum()), 1)),
+            "rows_only_cycle2_A=C_A!=B": float((rows_ac & ~rows_ab).mean())}
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--cycle":
+        per = int(sys.argv[5]) if len(sys.argv) > 5 else 1000
+        for k, v in cycle_share(sys.argv[2], sys.argv[3], sys.argv[4], per).items():
+            print(f"{k:40s} {v}")
+        sys.exit(0)
     per = int(sys.argv[3]) if len(sys.argv) > 3 else 1000
     for k, v in share(sys.argv[1], sys.argv[2], per).items():
         print(f"{k:40s} {v}")
