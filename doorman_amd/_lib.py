@@ -19,7 +19,7 @@ DM_HIER_INVALID, DM_HIER_COUNT_RANGE = 1, 2
 DM_RCCL_ID_BYTES = 128
 DM_RELAYOUT_COMPACT = 1
 DM_CLEAN_PEEK = 1
-DM_KEEP_REFRESH, DM_KEEP_UPDATES = 1, 2  # dm_keep_keys' bit set
+DM_KEEP_REFRESH, DM_KEEP_UPDATES, DM_KEEP_FREE_SLOTS = 1, 2, 4  # dm_keep_keys' bit set
 DM_NO_EXPIRY = 2**63 - 1  # INT64_MAX: dm_clean_result.next_expiry_ns when no live row is left
 DM_WRITEBACK, DM_AGG_RECOMPUTE, DM_ASYNC, DM_WB_INPLACE, DM_WB_ALTERNATE, DM_DEFER_JOIN = 1, 2, 4, 8, 16, 32
 

@@ -203,8 +203,9 @@ struct SplitSlot {
   DBuf<int32_t> queue, qcnt;
   int qpar = 0, skip = 0, wait = 64;
   Mapped<int32_t> queued;
-  // host-mapped: {undense counts, epoch} of the row epoch's density check
-  // (k_count_undense, enqueued in ver_epoch), and the guard a dense kernel sets should
+  // host-mapped: {undense counts, epoch, arrival count} of the row epoch's density check
+  // (k_count_undense, enqueued in ver_epoch; the third word is read only under
+  // DM_KEEP_FREE_SLOTS), and the guard a dense kernel sets should
   // it queue an item on a tick whose rest kernel was skipped (dm_ctx::check_device)
   Mapped<uint64_t> rec;
   Mapped<int32_t> guard;
@@ -214,13 +215,14 @@ struct SplitSlot {
   // epoch (0: none), as an estimate for the forms that the rest launch follows
   // (FormInputs::rec_kept); upd_rows: the rows kept updates wrote since that count; recount:
   // the next writeback tick's check_dense counts again.
-  uint64_t kept_counts = 0, kept_epoch = 0;
+  uint64_t kept_counts = 0, kept_epoch = 0, kept_arrivals = 0;
   int64_t upd_rows = 0;
   bool recount = false;
   void withdraw_record(uint64_t row_epoch, int64_t rows) {
     if (!rec.h) return;
     if (__atomic_load_n(rec.h + 1, __ATOMIC_ACQUIRE) == row_epoch) {
       kept_counts = __atomic_load_n(rec.h, __ATOMIC_RELAXED);
+      kept_arrivals = __atomic_load_n(rec.h + 2, __ATOMIC_RELAXED);
       kept_epoch = row_epoch;
       upd_rows = 0;
       __atomic_store_n(rec.h + 1, 0, __ATOMIC_RELEASE);
@@ -254,12 +256,14 @@ struct SplitSlot {
   void read_records(FormInputs& in) {
     in.rec_epoch = __atomic_load_n(rec.h + 1, __ATOMIC_ACQUIRE);
     in.rec_counts = __atomic_load_n(rec.h, __ATOMIC_RELAXED);
+    if (in.keep_free) in.rec_arrivals = (int64_t)__atomic_load_n(rec.h + 2, __ATOMIC_RELAXED);
     if (in.rec_epoch == in.row_epoch) {  // a count taken after every kept update: the copy has served
       kept_epoch = 0;
       upd_rows = 0;
     } else if (kept_epoch == in.row_epoch) {
       in.rec_epoch = kept_epoch;
       in.rec_counts = kept_counts;
+      if (in.keep_free) in.rec_arrivals = (int64_t)kept_arrivals;
       in.rec_kept = true;
       in.upd_rows = upd_rows;
     }
@@ -509,7 +513,8 @@ struct dm_ctx {
   // dm_keep_keys.  kept_refreshes: dm_plan_info slot 23.  kept_rows: values the kept
   // refreshes carried since the last tick, each of which may have cleared a key: the next
   // sweep's row kernel is sized for them (FormInputs::refreshed).
-  // keep_mode: the call's bit set (DM_KEEP_REFRESH, DM_KEEP_UPDATES).  A kept release, upsert
+  // keep_mode: the call's bit set (DM_KEEP_REFRESH, DM_KEEP_UPDATES; DM_KEEP_FREE_SLOTS keeps no call
+  // and only selects forms: dm_split_form.h).  A kept release, upsert
   // or synchronous batch ends as update_kept(): a kept refresh's effects, its own counter
   // (dm_keep_stats), and every part's density record withdrawn as a proof (SplitSlot::
   // withdraw_record).  The call has waited for the context stream behind DM_ENTER's join of
@@ -599,7 +604,7 @@ struct dm_ctx {
   static bool is_split_bin(int b) { return b >= 3 && b < 3 + kSplitBins; }
   // A split part whose items are all verified dense, none with released rows or arrivals
   // (k_count_undense's two counts), runs the steady builds of k_block_dense outside
-  // recompute mode: Clean's result is known, so its pass is left out (dm_tick_group.hip
+  // recompute mode: Clean's result is known, so its pass is left out (dm_tick_group.h
   // group_segment STEADY).  DM_STEADY=0: never; 2 (A/B only): the steady ticks' launches,
   // dense then rest, with the plain builds: what the trailing rest launch costs.
   int steady_ok = 1;
@@ -668,7 +673,7 @@ struct dm_ctx {
   bool bin4_wave = false;  // bin 4 on one wave per resource (kBin4Wave): most of its resources FairShare
   std::vector<int32_t> h_kind;  // the loaded configuration's kinds (bin 4's shape)
   // The split slots' host-mapped words, one allocation per kind (upload_plan), reached
-  // through the slots: a word per slot of h_dq and h_guard, two of h_rec and h_sw.
+  // through the slots: a word per slot of h_dq and h_guard, three of h_rec, two of h_sw.
   HBuf<int32_t> h_dq, h_guard;
   HBuf<uint64_t> h_rec, h_sw;
   void bind_split_slots() {  // once, when the words exist
@@ -677,7 +682,7 @@ struct dm_ctx {
       s.b = slot_bin(i), s.j = slot_part(i);
       s.lo = part_lo[s.b] + s.j, s.bin_keys = &fix_keys[s.b - 3], s.bin_aux = &cyc_aux[s.b - 3];
       s.queued = {h_dq.p + i, h_dq.d + i}, s.guard = {h_guard.p + i, h_guard.d + i};
-      s.rec = {h_rec.p + 2 * i, h_rec.d + 2 * i}, s.sweep = {h_sw.p + 2 * i, h_sw.d + 2 * i};
+      s.rec = {h_rec.p + 3 * i, h_rec.d + 3 * i}, s.sweep = {h_sw.p + 2 * i, h_sw.d + 2 * i};
     }
   }
   // the large-resource chain: its partials, the speculative form's state, the

@@ -119,6 +119,13 @@ static_assert(sizeof(FixKey) == 16, "one 16-B scalar load per item");
 //      its record is the one read with sum_has := prev_has: a cycle of period two, of
 //      which a fixed point is the case prev_has == sum_has.
 // An update kernel that clears a key leaves state 0, and the next tick stores every row.
+// The masked builds (DM_KEEP_FREE_SLOTS: the item may hold released rows) keep these states
+// unchanged.  A released row's gets is +0.0, and a release wrote its +0.0 into one column
+// only; the first cycle-form tick after it (state 0, its key cleared by the release or its
+// part's keys out of use) stores every run, so it zeroes the stale value the release left in
+// the other column.  That is what makes state 1's claim -- every row of the item is in the
+// column written -- true of masked rows too, and in a probe a masked row's destination value
+// joins the comparison like any other row's.
 // wait / skip: after a failed proof the destination rows are loaded again only after
 // `wait` ticks (doubling, at most 64), of which `skip` are still to pass.
 struct CycAux {

@@ -48,6 +48,14 @@ hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long
                                 hipStream_t st);
 hipError_t launch_bin_rest(const BinItems& w, const DevParams& p, const SplitArgs& a, int32_t* host_count,
                            int rest_grid, hipEvent_t done, hipStream_t st);
+// dm_tick_masked.hip: the steady forms of the three launchers above with the kernels' *_masked
+// siblings (PartForm::masked)
+hipError_t launch_bin_dense_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, hipEvent_t done,
+                                   FixKey* keys, bool use_keys, hipStream_t st);
+hipError_t launch_bin_sweep_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+                                   hipStream_t st);
+hipError_t launch_bin_cycle_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+                                   CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st);
 // dm_tick_large.hip
 int redo_blocks_per_cu();
 // The chain's one launcher takes the phase (dm_large_form.h LargePhase: each names its

@@ -285,7 +285,7 @@ int dm::upload_plan(dm_ctx* c) {
     // rocprofv3 need not issue: the rest-skip check was never seen there)
     const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
     DM_HIP(c, c->h_dq.alloc(dm_ctx::kSplitSlots, mapped), "dense split word");
-    DM_HIP(c, c->h_rec.alloc(dm_ctx::kSplitSlots * 2, mapped), "dense split check");
+    DM_HIP(c, c->h_rec.alloc(dm_ctx::kSplitSlots * 3, mapped), "dense split check");
     DM_HIP(c, c->h_guard.alloc(dm_ctx::kSplitSlots, mapped), "dense split guard");
     DM_HIP(c, c->h_sw.alloc(dm_ctx::kSplitSlots * 2, mapped), "sweep count");
     c->bind_split_slots();

@@ -75,7 +75,11 @@ struct RowWriteStart {
 };
 
 // dm_keep_keys' bit set (above).
-constexpr int kKeepRefresh = 1, kKeepUpdates = 2;
+// kKeepFreeSlots (4) keeps no call: it selects forms alone (dm_split_form.h FormInputs::keep_free,
+// PartForm::masked).  A dense workgroup-bin item that holds released rows, with no arrival bit
+// and a live row, then runs in the steady, FIXED, sweep and cycle forms' masked builds and keeps
+// a key; with the bit clear such an item goes through k_block_rest every tick.
+constexpr int kKeepRefresh = 1, kKeepUpdates = 2, kKeepFreeSlots = 4;
 constexpr bool is_update(RowWrite w) {
   return w == RowWrite::release || w == RowWrite::upsert || w == RowWrite::apply;
 }

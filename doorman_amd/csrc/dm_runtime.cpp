@@ -288,7 +288,7 @@ int dm_set_profiling(dm_ctx* c, int on) {
 
 int dm_keep_keys(dm_ctx* c, int on) {
   DM_CHECK_CTX(c);
-  c->keep_mode = on;  // a bit set (DM_KEEP_REFRESH, DM_KEEP_UPDATES); any non-zero value keeps refreshes
+  c->keep_mode = on;  // a bit set (DM_KEEP_REFRESH, DM_KEEP_UPDATES, DM_KEEP_FREE_SLOTS); any non-zero value keeps refreshes
   return DM_OK;
 }
 
@@ -331,7 +331,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[16 + kNumBins];
+  int64_t v[17 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -359,7 +359,9 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   v[14 + kNumBins] = c->kept_refreshes;  // wants refreshes kept under dm_keep_keys since dm_create
   v[15 + kNumBins] = 0;  // bin parts whose last tick ran the cycle form with the keys in use
   for (const SplitSlot& s : c->split) v[15 + kNumBins] += s.last.cycle && s.last.use_keys;
-  const int n = 16 + kNumBins;
+  v[16 + kNumBins] = 0;  // bin parts whose last tick ran a masked build (DM_KEEP_FREE_SLOTS)
+  for (const SplitSlot& s : c->split) v[16 + kNumBins] += s.last.masked;
+  const int n = 17 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

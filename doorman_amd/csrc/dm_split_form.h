@@ -15,6 +15,9 @@
 //   the sweep       ... as k_fixed_sweep and k_block_dense_list over its worklist
 //   the cycle form  FIXED's twin for a steady writeback tick on the alternate column:
 //                   k_cycle_sweep and k_block_cycle_list (dm_device.h CycAux)
+//   masked          any of the steady forms above, launched as the kernels' *_masked siblings
+//                   (dm_keep_keys' DM_KEEP_FREE_SLOTS: items that hold released rows are items
+//                   of the form like any other)
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -33,7 +36,7 @@ struct PartForm {
   // The part's fix_live after this tick: the row epoch when the FIXED build is launched,
   // else 0 (the mixed kernel included).  This one assignment is the key rule: a key is
   // trusted only while nothing but FIXED launches touched the part in this row epoch.
-  // Fixed points (dm_device.h FixKey, dm_tick_group.hip group_segment FIXED): a part that
+  // Fixed points (dm_device.h FixKey, dm_tick_group.h group_segment FIXED): a part that
   // runs a steady build on a writeback tick in place runs the FIXED build, which keeps a
   // key per item and loads no row of an item whose valid key matches its capacity and
   // kind.  A valid key says that nothing but FIXED builds has touched the item's rows,
@@ -54,6 +57,11 @@ struct PartForm {
   // a cycle-form launch fix_live: neither trusts the other's keys.
   bool cycle = false;
   uint64_t cyc_live = 0;
+  // The steady form's launches are the masked builds (group_segment MASKED).  The choice never
+  // affects results: a non-masked launch hands a masked item to the rest kernel, a masked
+  // launch handles a non-masked item identically, and both maintain keys by the same rules,
+  // so fix_live and cyc_live need no new discipline.
+  bool masked = false;
 };
 
 // The back-off of the split form.  The 128-thread bins split by the dense hint unless the
@@ -98,6 +106,9 @@ struct FormInputs {
   bool cycle_ok = true;     // DM_CYCLE
   bool cycle_want = false;  // the tick writes the alternate column for it: the caller's DM_WB_ALTERNATE, or a part asked (CycleAuto)
   uint64_t cyc_live = 0;    // the part's, before this tick
+  // dm_keep_keys' DM_KEEP_FREE_SLOTS.  The defaults give the answers choose_form gave without it.
+  bool keep_free = false;    // the bit is set
+  int64_t rec_arrivals = 0;  // the density record's third count: dense items with an arrival bit
 };
 
 // `tried`: try_split's answer (asked only of a part with hints in a bin that splits).
@@ -121,10 +132,17 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   // rows kept updates wrote since the count (each may have ended a dense state or set a bit)
   // are together at most a quarter of the part's items, try_split's bound for "too many for
   // the rest kernel".  Above it the part runs the forms it always ran.
-  const int64_t odd = (int64_t)(uint32_t)in.rec_counts + (int64_t)(in.rec_counts >> 32) + in.upd_rows;
+  // With DM_KEEP_FREE_SLOTS an item that holds released rows is no odd one: the masked builds
+  // decide it in the steady form and keep its key.  Odd are then the items not dense, those
+  // with an arrival bit (the record's third count) and the rows kept updates wrote since; the
+  // bound holds with or without DM_KEEP_UPDATES (a store with free slots and no updates is the
+  // common case), and a record without an undense or arrival item is clean on any tick.
+  const int64_t marked = in.keep_free ? in.rec_arrivals : (int64_t)(in.rec_counts >> 32);
+  const int64_t odd = (int64_t)(uint32_t)in.rec_counts + marked + in.upd_rows;
   const bool cycle_tick = in.cycle_ok && in.fixed_ok && in.cycle_want && in.writeback && !in.inplace;
-  const bool few = in.keep_updates && in.writeback && (in.inplace || cycle_tick) && 4 * odd <= in.n;
-  const bool clean = in.rec_counts == 0 && !in.rec_kept;
+  const bool few = (in.keep_updates || in.keep_free) && in.writeback && (in.inplace || cycle_tick) && 4 * odd <= in.n;
+  const bool none_odd = in.keep_free ? (uint32_t)in.rec_counts == 0 && in.rec_arrivals == 0 : in.rec_counts == 0;
+  const bool clean = none_odd && !in.rec_kept;
   const bool steady_form = in.steady_ok && in.nparts == 1 && verified && (clean || few) && !in.recompute;
   f.steady = steady_form && in.steady_ok != 2;
   // The dense kernel alone takes the record as a proof that nothing can be queued, which a
@@ -145,6 +163,10 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
   f.cycle = f.steady && cycle_tick;
   if (f.cycle) f.use_keys = in.cyc_live == in.row_epoch;
   f.cyc_live = f.cycle ? in.row_epoch : 0;
+  // The masked builds: only where the record, or its kept estimate, shows an item with a mask
+  // bit (or a kept update may have set one since), so a store without free slots launches the
+  // kernels it always launched.
+  f.masked = f.steady && in.keep_free && ((in.rec_counts >> 32) != 0 || (in.rec_kept && in.upd_rows > 0));
   // Grids are hints: both kernels stride over their lists, so correctness never depends
   // on them.  The rest kernel's is sized from the last split tick's queue (an empty queue
   // costs 16 workgroups that read one count); the row kernel's from the count the device

@@ -203,7 +203,7 @@ int Tick::outputs() {
   p.rmask = c->rmask.p;
   // Every tick decides every row's lease (released rows included).  A writeback tick
   // writes its gets in place, into the has column, where the dense kernels skip the
-  // gets store of every 64-row run the tick leaves unchanged (dm_tick_group.hip
+  // gets store of every 64-row run the tick leaves unchanged (dm_tick_group.h
   // group_segment: a third of a quiescent resource's bytes).  It writes the alternate
   // column, which becomes the store's has after the tick, when the caller asks for it,
   // when it may take the speculative large chain (dm_large_form.h), and on a store beyond the
@@ -399,6 +399,7 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   in.cyc_live = sl.cyc_live;
   in.refreshed = c->kept_rows;
   in.keep_updates = (c->keep_mode & kKeepUpdates) != 0;
+  in.keep_free = (c->keep_mode & kKeepFreeSlots) != 0;
   in.n = n;
   const bool may_split = in.hints && in.dense_split;
   if (may_split) in.queued = sl.read_queued();
@@ -444,19 +445,17 @@ int Tick::launch_dense_form(Part& pt, const PartForm& f) {
     }
   }
   DM_HIP(c, timed(KC_DENSE3 + (sl.b - 3), pt.s, [&] {
-           if (f.cycle)
-             return launch_bin_cycle(pt.w, pt.p, a,
-                                     SweepArgs{keys, sl.sw_list.p, sl.sw_cnt.p, sl.lpar,
-                                               (unsigned long long*)sl.sweep.d, (unsigned long long)c->row_epoch,
-                                               f.list_grid},
-                                     sl.aux(), f.use_keys, sl.cyc.on ? sl.cyc.seq : 0u, sl.cyc.on && !sl.cyc.judged,
-                                     pt.s);
-           if (f.sweep)
-             return launch_bin_sweep(pt.w, pt.p, a,
-                                     SweepArgs{keys, sl.sw_list.p, sl.sw_cnt.p, sl.lpar,
-                                               (unsigned long long*)sl.sweep.d, (unsigned long long)c->row_epoch,
-                                               f.list_grid},
-                                     pt.s);
+           const SweepArgs sw{keys, sl.sw_list.p, sl.sw_cnt.p, sl.lpar, (unsigned long long*)sl.sweep.d,
+                              (unsigned long long)c->row_epoch, f.list_grid};
+           const unsigned stamp = sl.cyc.on ? sl.cyc.seq : 0u;
+           const bool tell = sl.cyc.on && !sl.cyc.judged;
+           if (f.masked) {  // the same forms in the masked builds (dm_tick_masked.hip); masked implies steady
+             if (f.cycle) return launch_bin_cycle_masked(pt.w, pt.p, a, sw, sl.aux(), f.use_keys, stamp, tell, pt.s);
+             if (f.sweep) return launch_bin_sweep_masked(pt.w, pt.p, a, sw, pt.s);
+             return launch_bin_dense_masked(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, keys, f.use_keys, pt.s);
+           }
+           if (f.cycle) return launch_bin_cycle(pt.w, pt.p, a, sw, sl.aux(), f.use_keys, stamp, tell, pt.s);
+           if (f.sweep) return launch_bin_sweep(pt.w, pt.p, a, sw, pt.s);
            return launch_bin_dense(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, f.steady, keys, f.use_keys, pt.s);
          }),
          "group kernel (dense split)");

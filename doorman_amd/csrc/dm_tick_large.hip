@@ -10,7 +10,7 @@
 
 namespace dm {
 
-// the chain's gets stores are non-temporal (see kGroupNT, dm_tick_group.hip)
+// the chain's gets stores are non-temporal (see kGroupNT, dm_tick_group.h)
 constexpr bool kSpecNT = true;
 
 // --------------------------------------------------------------------------

@@ -18,7 +18,7 @@ from .workloads import CFG_FIELDS
 _BIN_NAMES = ("small_tiles", "sub16x4", "sub32x4", "wave64x4", "block128x4", "block128x8", "block256x8",
               "block2k4k", "sub8x2", "sub16x2", "large_resources", "large_chunks", "leases", "bin_shapes",
               "redo_resident_cap", "spec_fits", "aux_own_queues", "stream_parts", "queue_perm", "wb_inplace",
-              "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes", "cycle_parts")
+              "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes", "cycle_parts", "masked_parts")
 
 
 def _ptr(a):
@@ -334,7 +334,10 @@ class Engine:
         """dm_keep_keys: a wants refresh without NaN keeps the fixed-point keys of every resource
         in which it changed no row's wants bits (off by default).  `on` is a bit set: True or
         _lib.DM_KEEP_REFRESH (1) is that mode; with _lib.DM_KEEP_UPDATES (2) release, upsert and
-        the synchronous apply keep the keys of the resources whose rows they did not write."""
+        the synchronous apply keep the keys of the resources whose rows they did not write; with
+        _lib.DM_KEEP_FREE_SLOTS (4) a dense resource that holds released rows (free slots) runs in
+        the steady, fixed-point, sweep and cycle forms and keeps a key (plan_info's
+        "masked_parts").  No bit changes what a reader sees."""
         self._chk(self._L.dm_keep_keys(self._ctx, int(on)))
 
     def keep_stats(self) -> dict:

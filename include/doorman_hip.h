@@ -62,6 +62,8 @@ extern "C" {
    the context kept, and the call returns 24; dm_keep_keys' argument as a bit set
    (DM_KEEP_REFRESH, the mode it had, and DM_KEEP_UPDATES, which also keeps releases, upserts
    and synchronous batches) with dm_keep_stats (its counters; dm_plan_info is not extended);
+   DM_KEEP_FREE_SLOTS, a third bit (resources that hold released rows keep keys), with slot 25,
+   the parts whose last tick ran a masked build, and the call returns 26;
    dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
    are in use, and returns 5 (a caller that passes max = 4 gets the four it got).  (Added
    slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
@@ -541,9 +543,19 @@ int dm_set_profiling(dm_ctx* ctx, int on);
    (above that the bin runs as with the bit clear).  Subclient counts other than one do not end
    the mode.  Every other writer starts a row epoch as ever, under either bit:
    dm_store_apply_async (its NaN flag arrives two batches late), dm_decide, dm_store_clean,
-   dm_store_relayout, dm_store_load, dm_config_load and dm_hier_root_tick. */
+   dm_store_relayout, dm_store_load, dm_config_load and dm_hier_root_tick.
+   DM_KEEP_FREE_SLOTS (4) keeps no call; it selects the tick's forms alone.  With the bit clear
+   a dense workgroup-bin resource that holds released rows (free slots) runs through the
+   general path every tick and never holds a key.  With it set such a resource, while it has no
+   pending arrival and at least one live row, is decided by the steady, fixed-point, sweep and
+   cycle forms like any other (their masked builds): it keeps a key and is skipped at its fixed
+   point or in its proven two-tick cycle, and only resources that are not dense or have a
+   pending arrival count towards the quarter bound above, with or without DM_KEEP_UPDATES.
+   A part without free slots launches the kernels it launched with the bit clear.  What any
+   reader sees is unchanged bit for bit under this bit too. */
 #define DM_KEEP_REFRESH 1
 #define DM_KEEP_UPDATES 2
+#define DM_KEEP_FREE_SLOTS 4
 int dm_keep_keys(dm_ctx* ctx, int on);
 /* dm_keep_keys' counters: the mode (the bit set last passed), then what the context kept since
    it was created: wants refreshes, dm_store_release calls, dm_store_upsert calls, dm_store_apply
@@ -578,7 +590,9 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * (a steady writeback tick on the alternate column: a resource in a proven cycle of period
  * two, of which a fixed point is one, is not read at all; DM_CYCLE=0 in the environment,
  * read when the context is created, keeps the form off and every tick on the column it
- * chose before); returns 25 */
+ * chose before; a caller that passes max = 25 gets what it got while the call returned 25),
+ * and (slot 25) the workgroup-bin parts whose last tick ran a masked build (dm_keep_keys'
+ * DM_KEEP_FREE_SLOTS: resources that hold released rows decided in the steady forms); returns 26 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
