@@ -247,12 +247,23 @@ struct SplitSlot {
   DBuf<int32_t> sw_cnt;
   int lpar = 0;
   Mapped<uint64_t> sweep;
-  PartForm last;  // its last tick's form (all clear: no launch); dm_plan_info slots 20-22 count these
+  // The fused form (k_block_fused, dm_tick_fused.hip) has count words of its own, so that the
+  // two-kernel forms resume where they stopped: fu_cnt, a two-slot ring of the listed items
+  // and what was last told the host (through `sweep` above); fused_queued (host-mapped), a
+  // two-slot ring of the rest items, which stands in for `queued` after a fused tick; fpar:
+  // the ring slot of the next fused tick.  fu_cnt is allocated by the first tick that runs fused.
+  DBuf<int32_t> fu_cnt;
+  Mapped<int32_t> fused_queued;
+  int fpar = 0;
+  bool ran_fused = false;  // the part's last split-form tick ran fused (dm_tick.cpp launch_fused: whose told words are current)
+  PartForm last;  // its last tick's form (all clear: no launch); dm_plan_info slots 20-22, 24-26 count these
   // What the device last told the host, for the form's choice: each record's epoch first,
   // with acquire order (the device stores the count, then the epoch with release order).
   // Only the words the choice can use are read, as ever: the queued count for a part that
   // may split, the records for one that tries to, the sweep's where keys may be in use.
-  int64_t read_queued() const { return __atomic_load_n(queued.h, __ATOMIC_RELAXED); }
+  int64_t read_queued() const {  // (after a fused tick: the slot that tick added to)
+    return __atomic_load_n(ran_fused ? fused_queued.h + (fpar ^ 1) : queued.h, __ATOMIC_RELAXED);
+  }
   void read_records(FormInputs& in) {
     in.rec_epoch = __atomic_load_n(rec.h + 1, __ATOMIC_ACQUIRE);
     in.rec_counts = __atomic_load_n(rec.h, __ATOMIC_RELAXED);
@@ -631,6 +642,10 @@ struct dm_ctx {
   // DM_CYCLE=0: no part runs the cycle form and none asks for the alternate column (the
   // ticks are the ones they were without it).  cyc_aux[b - 3]: the keys' second halves.
   int cycle_ok = 1;
+  // DM_FUSED=0: no part runs the fused form (PartForm::fused): every tick's launches are the
+  // ones they were without it.  2 (a measuring hook): fused wherever the rule allows, whatever
+  // count the device told.
+  int fused_ok = 1;
   // DM_CYCLE_BYTES (a test hook, read when the context is created): the store size in bytes
   // (48 per lease) above which a part may ask by itself; kStreamBytes by default.
   int64_t cycle_bytes = kStreamBytes;
@@ -673,8 +688,8 @@ struct dm_ctx {
   bool bin4_wave = false;  // bin 4 on one wave per resource (kBin4Wave): most of its resources FairShare
   std::vector<int32_t> h_kind;  // the loaded configuration's kinds (bin 4's shape)
   // The split slots' host-mapped words, one allocation per kind (upload_plan), reached
-  // through the slots: a word per slot of h_dq and h_guard, three of h_rec, two of h_sw.
-  HBuf<int32_t> h_dq, h_guard;
+  // through the slots: a word per slot of h_dq and h_guard, three of h_rec, two of h_sw and h_fq.
+  HBuf<int32_t> h_dq, h_guard, h_fq;
   HBuf<uint64_t> h_rec, h_sw;
   void bind_split_slots() {  // once, when the words exist
     for (int i = 0; i < kSplitSlots; ++i) {
@@ -683,6 +698,7 @@ struct dm_ctx {
       s.lo = part_lo[s.b] + s.j, s.bin_keys = &fix_keys[s.b - 3], s.bin_aux = &cyc_aux[s.b - 3];
       s.queued = {h_dq.p + i, h_dq.d + i}, s.guard = {h_guard.p + i, h_guard.d + i};
       s.rec = {h_rec.p + 3 * i, h_rec.d + 3 * i}, s.sweep = {h_sw.p + 2 * i, h_sw.d + 2 * i};
+      s.fused_queued = {h_fq.p + 2 * i, h_fq.d + 2 * i};
     }
   }
   // the large-resource chain: its partials, the speculative form's state, the

@@ -56,6 +56,21 @@ hipError_t launch_bin_sweep_masked(const BinItems& w, const DevParams& p, const 
                                    hipStream_t st);
 hipError_t launch_bin_cycle_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
                                    CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st);
+// dm_tick_fused.hip: the sweep or the cycle form (by the tick's output column) with keys in
+// use, the row kernel and the rest kernel as one launch (PartForm::fused); `done` as
+// launch_bin_rest's
+struct FusedArgs {
+  FixKey* keys;
+  CycAux* aux;    // the cycle form's half of the keys (unused in place)
+  int32_t* fcnt;  // the form's own count words (SplitSlot::fu_cnt) ...
+  int par;        // ... and this tick's slot of their ring
+  bool fresh;     // the part's previous tick was not fused: the other slot's totals are not told
+  unsigned long long *host_count, epoch;  // (host-mapped) {count, row epoch}, as SweepArgs'
+  int32_t* host_rest;                     // (host-mapped) the rest items' two-slot ring (SplitSlot::fused_queued)
+  int32_t *glist, *gcount;                // k_general's worklist and its count
+};
+hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedArgs& a, hipEvent_t done,
+                            hipStream_t st);
 // dm_tick_large.hip
 int redo_blocks_per_cu();
 // The chain's one launcher takes the phase (dm_large_form.h LargePhase: each names its

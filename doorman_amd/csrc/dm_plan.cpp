@@ -236,6 +236,11 @@ int dm::SplitSlot::reset(dm_ctx* c, hipStream_t st) {
   __atomic_store_n(sweep.h + 1, (uint64_t)0, __ATOMIC_RELAXED);
   if (sw_cnt.p) DM_HIP(c, hipMemsetAsync(sw_cnt.p, 0, 4 * sizeof(int32_t), st), "sweep count");
   lpar = 0;
+  if (fu_cnt.p) DM_HIP(c, hipMemsetAsync(fu_cnt.p, 0, 8 * sizeof(int32_t), st), "fused count");
+  fpar = 0;
+  ran_fused = false;
+  __atomic_store_n(fused_queued.h, 0, __ATOMIC_RELAXED);
+  __atomic_store_n(fused_queued.h + 1, 0, __ATOMIC_RELAXED);
   return DM_OK;
 }
 
@@ -288,6 +293,7 @@ int dm::upload_plan(dm_ctx* c) {
     DM_HIP(c, c->h_rec.alloc(dm_ctx::kSplitSlots * 3, mapped), "dense split check");
     DM_HIP(c, c->h_guard.alloc(dm_ctx::kSplitSlots, mapped), "dense split guard");
     DM_HIP(c, c->h_sw.alloc(dm_ctx::kSplitSlots * 2, mapped), "sweep count");
+    DM_HIP(c, c->h_fq.alloc(dm_ctx::kSplitSlots * 2, mapped), "fused count");
     c->bind_split_slots();
   }
   c->rows_changed();  // new work items: no hints

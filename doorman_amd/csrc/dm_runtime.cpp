@@ -173,6 +173,7 @@ int dm_create(int device, dm_ctx** out) {
   if (const char* fx = getenv("DM_FIXED")) c->fixed_ok = atoi(fx) != 0;
   if (const char* sw = getenv("DM_SWEEP")) c->sweep_ok = atoi(sw) != 0;
   if (const char* cy = getenv("DM_CYCLE")) c->cycle_ok = atoi(cy) != 0;
+  if (const char* fu = getenv("DM_FUSED")) c->fused_ok = atoi(fu);
   if (const char* cb = getenv("DM_CYCLE_BYTES")) c->cycle_bytes = atoll(cb);
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
@@ -331,7 +332,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[17 + kNumBins];
+  int64_t v[20 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -361,7 +362,18 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   for (const SplitSlot& s : c->split) v[15 + kNumBins] += s.last.cycle && s.last.use_keys;
   v[16 + kNumBins] = 0;  // bin parts whose last tick ran a masked build (DM_KEEP_FREE_SLOTS)
   for (const SplitSlot& s : c->split) v[16 + kNumBins] += s.last.masked;
-  const int n = 17 + kNumBins;
+  v[17 + kNumBins] = 0;  // bin parts whose last tick ran fused (one launch: k_block_fused)
+  for (const SplitSlot& s : c->split) v[17 + kNumBins] += s.last.fused;
+  // what the device last told the host of the workgroup-bin parts, summed: the listed items
+  // (the sweep record's count, from the row kernel or a fused launch) and the rest items (the
+  // rest kernel's queue, or a fused launch's ring: SplitSlot::read_queued)
+  v[18 + kNumBins] = v[19 + kNumBins] = 0;
+  for (const SplitSlot& s : c->split) {
+    if (!s.sweep.h || !s.lo || s.items() <= 0) continue;
+    v[18 + kNumBins] += (int64_t)(uint32_t)__atomic_load_n(s.sweep.h, __ATOMIC_RELAXED);
+    v[19 + kNumBins] += s.read_queued();
+  }
+  const int n = 20 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

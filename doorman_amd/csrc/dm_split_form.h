@@ -18,6 +18,9 @@
 //   masked          any of the steady forms above, launched as the kernels' *_masked siblings
 //                   (dm_keep_keys' DM_KEEP_FREE_SLOTS: items that hold released rows are items
 //                   of the form like any other)
+//   fused           the sweep or the cycle form with keys in use, as one launch: k_block_fused
+//                   (dm_tick_fused.hip) sweeps, and decides the few items the sweep would list
+//                   or the row kernel queue itself; no row kernel, no rest launch
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -62,7 +65,24 @@ struct PartForm {
   // launch handles a non-masked item identically, and both maintain keys by the same rules,
   // so fix_live and cyc_live need no new discipline.
   bool masked = false;
+  // The sweep (or the cycle form's) and what follows it as one launch, k_block_fused: chosen
+  // only where keys are trusted (so fixed / sweep / cycle / use_keys, fix_live and cyc_live are
+  // what they are without it: a fused launch is a FIXED or cycle-form launch for the key rule)
+  // and the device last told of few listed items.  list_grid and rest_grid are then unused.
+  bool fused = false;
 };
+
+// The most listed items (the sweep's worklist: row items and rest items) a part of n items may
+// have been told of and still run fused.  A fused workgroup decides the listed items of its
+// chunk one after another, where the row kernel spreads a list over the GPU at the price of two
+// more launches.  Measured on the C3-shaped store of 100,000 items (tools/fused_ab.py,
+// profiles/fused_ab.md; the tick's host time, fused against two-kernel): 15.3 against 19.3 us
+// with nothing listed, 20.8 against 25.3 us with 10 items, 29.6 against 25.8 us with 100, 51.4
+// against 31.4 us with 1,000.  Between 10 and 100 the two lines cross at about 59 items, a
+// share of 5.9e-4; the threshold is half of that, a 3,400th of the part's items, so that a hint
+// a few ticks stale still picks the cheaper form.  At least 4: the measured 10 win by 4.5 us.
+constexpr int kFusedShareDenom = 3400;
+inline int64_t fused_limit(int n) { return std::max<int64_t>(4, n / kFusedShareDenom); }
 
 // The back-off of the split form.  The 128-thread bins split by the dense hint unless the
 // last split tick the host has heard of queued more than a quarter of the part's items for
@@ -109,6 +129,10 @@ struct FormInputs {
   // dm_keep_keys' DM_KEEP_FREE_SLOTS.  The defaults give the answers choose_form gave without it.
   bool keep_free = false;    // the bit is set
   int64_t rec_arrivals = 0;  // the density record's third count: dense items with an arrival bit
+  // The fused form.  The defaults give the answers choose_form gave without it.
+  bool fused_ok = false;    // DM_FUSED
+  bool unjudged = false;    // the part asked for the alternate column and awaits its judgement (CycleAuto: on && !judged)
+  int64_t fused_max = 0;    // fused_limit(n) (DM_FUSED=2, a measuring hook: no limit)
 };
 
 // `tried`: try_split's answer (asked only of a part with hints in a bin that splits).
@@ -178,6 +202,13 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
     const int64_t told = in.sw_told + in.refreshed;
     f.list_grid = (int)std::min<int64_t>(in.n, std::max<int64_t>(16, told + told / 8 + (told ? 64 : 0)));
   }
+  // The fused form: keys are trusted (the first key-rewriting launch of an epoch lists every
+  // item and stays the two-kernel form at full occupancy), no masked build, no judgement
+  // pending (it needs the row kernel's stamp, which a fused launch does not tell), and the
+  // sweep record is of this row epoch with few items listed, those that kept refreshes and
+  // updates may have added since included.
+  f.fused = in.fused_ok && (f.sweep || (f.cycle && f.use_keys)) && !f.masked && !in.unjudged &&
+            in.sw_epoch == in.row_epoch && in.sw_told + in.refreshed <= in.fused_max;
   return f;
 }
 

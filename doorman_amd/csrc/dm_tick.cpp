@@ -6,7 +6,8 @@
 // A workgroup bin's stream part (Tick::bin_part) works on its split slot (dm_ctx.h
 // SplitSlot): it reads the slot's host-mapped words, asks dm_split_form.h for the form of
 // this tick's launches (try_split, choose_form: the one place the forms and the key rule
-// are written), and hands the form to launch_dense_form, launch_rest or launch_mixed.
+// are written), and hands the form to launch_fused, launch_dense_form, launch_rest or
+// launch_mixed.
 // The large-resource chain (Tick::large_chain) works on its owner (dm_large_chain.h
 // LargeChain): Tick::outputs asks dm_large_form.h once for the tick's output column and the
 // chain's form (choose_large), and large_chain launches the form's phases in order.
@@ -184,6 +185,7 @@ struct Tick {
     hipEvent_t done;  // the part's tick event, for its last kernel (null: no queue waits for the tick)
   };
   int bin_part(int b, int lb, int nparts, int j);
+  int launch_fused(Part& pt, const PartForm& f);       // the sweep, its row kernel and the rest kernel as one launch
   int launch_dense_form(Part& pt, const PartForm& f);  // the dense kernel in the form's build, or the sweep
   int launch_rest(Part& pt, const PartForm& f);        // the rest kernel over what it queued
   int launch_mixed(Part& pt);                          // the one-kernel form
@@ -401,6 +403,9 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   in.keep_updates = (c->keep_mode & kKeepUpdates) != 0;
   in.keep_free = (c->keep_mode & kKeepFreeSlots) != 0;
   in.n = n;
+  in.fused_ok = c->fused_ok != 0;
+  in.unjudged = sl.cyc.on && !sl.cyc.judged;
+  in.fused_max = c->fused_ok == 2 ? INT64_MAX / 2 : fused_limit(n);
   const bool may_split = in.hints && in.dense_split;
   if (may_split) in.queued = sl.read_queued();
   const bool tried = may_split && try_split(in.queued, n, sl.skip, sl.wait);
@@ -422,7 +427,9 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
     cycle_auto_step(sl.cyc, ai, f);
   }
   int rc = DM_OK;
-  if (!f.split)
+  if (f.fused)
+    rc = launch_fused(pt, f);
+  else if (!f.split)
     rc = launch_mixed(pt);
   else if (!(rc = launch_dense_form(pt, f)) && !f.skip_rest)
     rc = launch_rest(pt, f);
@@ -431,8 +438,35 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
   return DM_OK;
 }
 
+// The fused form tells the host its listed count through the word the row kernel tells through
+// (SplitSlot::sweep), and each of the two writes only what differs from what it last told
+// itself.  So when the form changes, the kernel that takes over must not take its own last
+// word for the host's: a fused launch after another form is told so (FusedArgs::fresh), and
+// the first row kernel after a fused launch finds its last-told words cleared (a change of
+// form is rare; a steady part pays nothing).  The rest items have a host word of their own
+// (SplitSlot::fused_queued), read in place of `queued` until the next split launch.
+int Tick::launch_fused(Part& pt, const PartForm& f) {
+  SplitSlot& sl = pt.sl;
+  if (!sl.fu_cnt.p) {
+    DM_HIP(c, sl.fu_cnt.ensure(8), "fused count");  // k_block_fused has the layout
+    DM_HIP(c, hipMemsetAsync(sl.fu_cnt.p, 0, 8 * sizeof(int32_t), pt.s), "fused count");
+    sl.fpar = 0;
+  }
+  const FusedArgs a{sl.keys(), f.cycle ? sl.aux() : nullptr, sl.fu_cnt.p, sl.fpar, !sl.ran_fused,
+                    (unsigned long long*)sl.sweep.d, (unsigned long long)c->row_epoch, sl.fused_queued.d, gl, gc};
+  DM_HIP(c, timed(KC_DENSE3 + (sl.b - 3), pt.s, [&] { return launch_bin_fused(pt.w, pt.p, a, pt.done, pt.s); }),
+         "group kernel (fused)");
+  sl.fpar ^= 1;
+  sl.ran_fused = true;
+  return DM_OK;
+}
+
 int Tick::launch_dense_form(Part& pt, const PartForm& f) {
   SplitSlot& sl = pt.sl;
+  if (sl.ran_fused) {  // (launch_fused has the account)
+    if (sl.sw_cnt.p) DM_HIP(c, hipMemsetAsync(sl.sw_cnt.p + 2, 0xFF, 2 * sizeof(int32_t), pt.s), "sweep count");
+    sl.ran_fused = false;
+  }
   // the guard and the tick's event go to a dense launch that no rest launch follows
   const SplitArgs a{sl.queue.p, sl.qcnt.p, sl.qpar, gl, gc, f.skip_rest ? sl.guard.d : nullptr};
   FixKey* keys = f.fixed || f.cycle ? sl.keys() : nullptr;

@@ -1,0 +1,208 @@
+// dm_tick_fused.hip — the fused form of a steady dense tick (dm_split_form.h PartForm::fused):
+// the sweep, the row kernel over its worklist and the rest kernel as one launch.  A unit, and so
+// a code object, of its own, as dm_tick_masked.hip is: dm_tick_group.hip's device code is what
+// it is without it.
+//
+// A part at its fixed point (or in a proven two-tick cycle) launches k_fixed_sweep (or
+// k_cycle_sweep), then a row kernel over an empty list and a rest kernel over an empty queue:
+// two launches that read one count each, because only the device knows the lists are empty
+// (lease lengths, templates and learning ends change there).  Each costs the host and the
+// stream a launch (profiles/cycle_ab.md: 16.1 us a step against 12.7 us of enqueue).
+// k_block_fused makes the empty case cost nothing: a workgroup sweeps a chunk of the part's
+// items, one per lane, by the sweeps' tests, and decides the few items that need rows or the
+// rest body itself, with the same group_segment calls the list kernels and k_block_rest make.
+// No workgroup waits for another and there is no word that every workgroup updates: a workgroup
+// adds its counts to the device words only when they are not zero.
+#include "dm_tick_group.h"
+
+namespace dm {
+
+// Items per workgroup, one per lane of the sweep step: G by default (C3: 782 workgroups of two
+// waves, as many waves as k_cycle_sweep's 98 x 16).  DM_FUSED_CHUNK builds a variant with fewer
+// (profiles/fused_ab.md).
+#ifndef DM_FUSED_CHUNK
+#define DM_FUSED_CHUNK 0
+#endif
+template <int G>
+constexpr int kFusedChunk = (DM_FUSED_CHUNK > 0 && DM_FUSED_CHUNK < G) ? DM_FUSED_CHUNK : G;
+
+// One listed item of a workgroup's chunk, in LDS: the work item, its index in the part, what the
+// sweep step decided (rest: k_block_rest's body; else the row kernel's, with the cycle form's
+// probe and carry: SweepEntry::pad) and the item's CycAux as the sweep step left it.
+struct FusedEntry {
+  int32_t seg, n;
+  int64_t lo;
+  int32_t idx;
+  int32_t flags;  // bit 0: rest; bit 1: probe; bit 2: carry
+  int32_t wait, skip;
+  uint64_t prev_has;
+};
+static_assert(sizeof(FusedEntry) == 40, "ten dwords");
+
+// fcnt: the form's own count words (SplitSlot::fu_cnt).  [2 s]: the items listed (row and rest
+// items together, what the sweeps' worklist counts) by the fused tick of ring slot s; [4], [5]:
+// the listed count and row epoch last told the host; [7]: never read (the count word of a
+// hand-off that cannot happen).  This tick adds into slot par; workgroup 0 reads slot par ^ 1,
+// the previous fused tick's total, complete by stream order, tells the host when it differs
+// from what was last told (SplitSlot::sweep as k_block_dense_list tells it, without a stamp)
+// and zeroes the slot.  fresh: the part's previous tick was not fused, so the slot holds an
+// older tick's total, which is dropped, and the next fused tick tells whatever this one counts.
+// host_rest (host-mapped, SplitSlot::fused_queued): the rest items, a two-slot ring as well, but
+// added to by the workgroups that have some, in this tick's slot, so that the host knows of a
+// lapse before its next choice as it does from k_block_rest (try_split: a part most of whose
+// items are rest items runs the mixed kernel); workgroup 0 zeroes the other slot for the next
+// fused tick, when fcnt[2 s + 1], the same count on the device, says it is not zero.
+template <int G, int R, bool CYCLE>
+__global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __restrict__ items, int nitems,
+                                                   FixKey* __restrict__ keys, CycAux* __restrict__ aux, int32_t* fcnt,
+                                                   int par, int fresh, unsigned long long* host_count,
+                                                   unsigned long long epoch, int32_t* host_rest,
+                                                   int32_t* general_list, int32_t* general_count) {
+  constexpr int C = kFusedChunk<G>, W = G / 64;
+  static_assert(G >= 64 && C <= G, "one item per lane");
+  __shared__ Lds<G> lds;
+  __shared__ FusedEntry ent[C];
+  __shared__ int wtot[W];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    int32_t* prev = fcnt + 2 * (par ^ 1);
+    const int listed = prev[0], rest = prev[1];
+    if (fresh) {
+      fcnt[4] = -1;
+    } else {
+      if (fcnt[4] != listed || fcnt[5] != (int32_t)epoch) {
+        __hip_atomic_store(host_count, (unsigned long long)(unsigned)listed, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        fcnt[4] = listed;
+        fcnt[5] = (int32_t)epoch;
+      }
+    }
+    if (listed) prev[0] = 0;
+    if (rest) {  // (a store to host memory keeps an otherwise empty launch alive ~2 us longer: only when needed)
+      prev[1] = 0;
+      __hip_atomic_store(host_rest + (par ^ 1), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+
+  // ---- step 1: classify (k_fixed_sweep's / k_cycle_sweep's lane, and group_segment's `rest`
+  // test for the items the sweeps leave to the row kernel) ----
+  const int i = (int)(blockIdx.x * (unsigned)C + threadIdx.x);
+  bool app = false, to_rest = false;
+  int probe = 0, carry = 0;
+  WorkItem wi{0, 0, 0};
+  [[maybe_unused]] CycAux ax{0, 0, 0};
+  if ((int)threadIdx.x < C && i < nitems) {
+    wi = items[i];
+    const FixKey fk = keys[i];
+    if constexpr (CYCLE) ax = aux[i];
+    const int hw = wi.n >> 16;
+    bool done = false;
+    if (hw == 0) {
+      to_rest = true;
+    } else {
+      const Res rs = load_res(p, wi.seg);
+      const int hint = hw & 0xFF;
+      const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
+      if (rest) {
+        to_rest = true;
+      } else if (fk.valid != 0 && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind &&
+                 !rs.learning) {
+        if constexpr (CYCLE) {
+          if (fk.valid == 2) {
+            write_resource(p, wi.seg, rs,
+                           Clean{rs.agg_count, __longlong_as_double((long long)ax.prev_has), rs.agg_wants}, 0.0, hint);
+            const uint64_t was = (uint64_t)__double_as_longlong(rs.agg_has);
+            if (ax.prev_has != was) aux[i].prev_has = was;
+            done = true;
+          } else if (ax.skip > 0) {
+            ax.skip -= 1;
+            aux[i].skip = ax.skip;
+            carry = 1;
+          } else {
+            probe = carry = 1;
+          }
+        } else {
+          write_fixed(p, wi.seg, rs, hint);
+          done = true;
+        }
+      }
+    }
+    if (!done) {
+      app = true;
+      // the key in memory as the two-kernel form leaves it before the item's rows are read:
+      // the sweep clears a valid key, and the cycle form's row kernel (which does not use the
+      // keys) overwrites whatever the array holds when it hands an item with a hint word off
+      const bool dirty = CYCLE && to_rest && hw != 0 && (fk.cbits != 0 || fk.kind != 0);
+      if (fk.valid || dirty) keys[i] = FixKey{0, 0, 0};
+    }
+  }
+
+  // ---- step 2: compact the listed items into LDS (a ballot per wave, one LDS step across) ----
+  const uint64_t bal = __ballot(app), balr = __ballot(to_rest);
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  if (lane == 0) wtot[wave] = __popcll(bal) | __popcll(balr) << 16;
+  __syncthreads();
+  int base = 0, tot = 0, nrest = 0;
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const int c = wtot[w];
+    base += w < wave ? c & 0xFFFF : 0;
+    tot += c & 0xFFFF;
+    nrest += c >> 16;
+  }
+  if (tot == 0) return;  // (uniform) the steady case
+  if (threadIdx.x == 0) {
+    atomicAdd(fcnt + 2 * par, tot);
+    if (nrest) {
+      atomicAdd(fcnt + 2 * par + 1, nrest);
+      __hip_atomic_fetch_add(host_rest + par, nrest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  if (app)
+    ent[base + __popcll(bal & ((1ull << lane) - 1ull))] =
+        FusedEntry{wi.seg, wi.n, wi.lo, i, (to_rest ? 1 : 0) | probe << 1 | carry << 2, ax.wait, ax.skip, ax.prev_has};
+  __syncthreads();
+
+  // ---- step 3: the whole workgroup decides them, one after another ----
+  for (int q = 0; q < tot; ++q) {
+    const FusedEntry e = uniform(ent[q]);
+    const WorkItem it{e.seg, e.n, e.lo};
+    int t = (int)threadIdx.x;  // (anew for every item: k_block_dense_list)
+    asm volatile("" : "+v"(t));
+    if (e.flags & 1) {
+      group_segment<G, R, kRest>(p, it, items + e.idx, t, lds, general_list, general_count);
+    } else if constexpr (CYCLE) {
+      // (its own `rest` test is false: no hand-off; the queue arguments are never used)
+      group_segment<G, R, kDenseOnly, true, true, true, true, true>(
+          p, it, items + e.idx, t, lds, general_list, general_count, fcnt, fcnt + 7, e.idx, nullptr, 0, keys + e.idx,
+          FixKey{0, 0, 0}, 0, aux + e.idx, CycAux{e.prev_has, e.wait, e.skip}, e.flags >> 1 & 1, e.flags >> 2 & 1);
+    } else {
+      group_segment<G, R, kDenseOnly, true, true, true, true>(p, it, items + e.idx, t, lds, general_list,
+                                                              general_count, fcnt, fcnt + 7, e.idx, nullptr, 0,
+                                                              keys + e.idx, FixKey{0, 0, 0}, 1);
+    }
+    __syncthreads();  // the next item reuses the single-use LDS slots
+  }
+}
+
+// The launch is the part's last kernel of the tick: it completes `done` (hipExtLaunchKernel's
+// stop event) as the rest launch does in the other forms.
+hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedArgs& a, hipEvent_t done,
+                            hipStream_t st) {
+  const int n = w.n;
+  if (n <= 0) return hipSuccess;
+  const bool cycle = p.out_gets != p.has;
+  if (!p.writeback || !a.keys || !a.fcnt || !a.host_rest || (cycle && !a.aux)) return hipErrorInvalidValue;
+  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
+    constexpr int G = decltype(g)::value, R = decltype(r)::value;
+    const dim3 grid((unsigned)((n + kFusedChunk<G> - 1) / kFusedChunk<G>));
+    with_bool(cycle, [&](auto cy) {
+      hipExtLaunchKernelGGL((k_block_fused<G, R, decltype(cy)::value>), grid, dim3(G), 0, st, nullptr, done, 0, p,
+                            w.items, n, a.keys, a.aux, a.fcnt, a.par, a.fresh ? 1 : 0, a.host_count, a.epoch,
+                            a.host_rest, a.glist, a.gcount);
+    });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+}  // namespace dm

@@ -19,6 +19,8 @@ _BIN_NAMES = ("small_tiles", "sub16x4", "sub32x4", "wave64x4", "block128x4", "bl
               "block2k4k", "sub8x2", "sub16x2", "large_resources", "large_chunks", "leases", "bin_shapes",
               "redo_resident_cap", "spec_fits", "aux_own_queues", "stream_parts", "queue_perm", "wb_inplace",
               "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes", "cycle_parts", "masked_parts")
+# dm_plan_info's slots beyond the bins' table, in order
+_PLAN_NAMES = _BIN_NAMES + ("fused_parts", "told_listed", "told_queued")
 
 
 def _ptr(a):
@@ -361,7 +363,7 @@ class Engine:
     def plan_info(self) -> dict:
         arr = (ctypes.c_int64 * 32)()
         n = self._chk(self._L.dm_plan_info(self._ctx, arr, 32))
-        return {_BIN_NAMES[i]: int(arr[i]) for i in range(min(n, len(_BIN_NAMES)))}
+        return {_PLAN_NAMES[i]: int(arr[i]) for i in range(min(n, len(_PLAN_NAMES)))}
 
     def store_lost(self) -> bool:
         """dm_store_lost: a device-side invariant failed; ticks and updates refuse the store

@@ -65,7 +65,8 @@ extern "C" {
    DM_KEEP_FREE_SLOTS, a third bit (resources that hold released rows keep keys), with slot 25,
    the parts whose last tick ran a masked build, and the call returns 26;
    dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
-   are in use, and returns 5 (a caller that passes max = 4 gets the four it got).  (Added
+   are in use, and returns 5 (a caller that passes max = 4 gets the four it got);
+   dm_plan_info's slot 26, the parts whose last tick ran fused (one launch).  (Added
    slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
    pinned.)
    6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
@@ -592,7 +593,14 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * read when the context is created, keeps the form off and every tick on the column it
  * chose before; a caller that passes max = 25 gets what it got while the call returned 25),
  * and (slot 25) the workgroup-bin parts whose last tick ran a masked build (dm_keep_keys'
- * DM_KEEP_FREE_SLOTS: resources that hold released rows decided in the steady forms); returns 26 */
+ * DM_KEEP_FREE_SLOTS: resources that hold released rows decided in the steady forms), and
+ * (slot 26) the workgroup-bin parts whose last tick ran fused (the sweep or the cycle form
+ * with the keys in use, its row kernel and the rest kernel as one launch, chosen while the
+ * device tells of few listed items; DM_FUSED=0 in the environment, read when the context is
+ * created, keeps the launches as they were), and (slots 27, 28) the listed items and the rest
+ * items the device last told the host of, summed over the workgroup-bin parts (hints that size
+ * and choose the next launches; for tests and tools), with which the call returns 29: a caller
+ * that passes max = 26 gets the slots it got while the call returns 26 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
  * live follower with one subclient count: a tick reads 24 B per lease, not 28),
