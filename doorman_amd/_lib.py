@@ -143,6 +143,13 @@ _SIGS = {
     "dm_store_lost": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "dm_read_leases_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p]),
+    # the store from and into device memory (every data pointer a device pointer)
+    "dm_store_load_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Snapshot)]),
+    "dm_read_store_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    "dm_read_store_sums_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+                                  + [ctypes.c_void_p] * 3),
+    "dm_read_leases_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
     # round-oriented GetCapacity dispatch (dm_server.cpp)
     "dm_server_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.POINTER(ResourceCfg), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),

@@ -739,6 +739,8 @@ struct dm_ctx {
   DBuf<int64_t> cl_blk_pre, cl_blk_min, cl_list;
   bool cl_valid = false;
   int64_t cl_n = 0;
+  // dm_store_load_device: the flags its kernels raise (dm_launch.h kLdBadSub, kLdNotOne, kLdGeneral)
+  DBuf<uint32_t> ld_flags;
   // dm_decide: a round's requests (grouped by resource), per-resource work items, results
   DBuf<int64_t> rq_rows, rq_sub, rq_exp;
   DBuf<double> rq_has, rq_wants, rq_gets;

@@ -145,4 +145,25 @@ hipError_t launch_relayout(const RelayoutArgs& a, int32_t* nblk, ResAgg* n_agg, 
 // dm_clean.hip
 hipError_t launch_clean_count(const CleanArgs& a, hipStream_t st);
 hipError_t launch_clean_apply(const CleanArgs& a, const DenseUpd& du, bool peek, hipStream_t st);
+// dm_load.hip
+// A snapshot whose columns are device memory (dm_store_load_device), as its kernels take it:
+// the caller's columns, read only, and the context's flags word.
+struct LoadArgs {
+  int64_t R, N;
+  const double *wants, *has;
+  const int64_t *sub, *expiry;
+  const int64_t* agg_count;  // the three running sums, or all null: one Assign per row in row order
+  const double *agg_sum_has, *agg_sum_wants;
+  uint32_t* flags;
+};
+constexpr uint32_t kLdBadSub = 1u;   // a subclients value outside [0, kSubMax]: the load is rejected
+constexpr uint32_t kLdNotOne = 2u;   // some row that is not released has a count other than 1 (all_sub_one is false)
+constexpr uint32_t kLdGeneral = 4u;  // some non-small resource may need k_general (maybe_general)
+// the check zeroes the flags word, then reads the caller's rows only; the other two write
+// the context's columns: sub32 [N], agg [R], with seg_off the context's copy of the offsets
+hipError_t launch_load_check(const LoadArgs& a, hipStream_t st);
+hipError_t launch_load_sub(const LoadArgs& a, int32_t* sub32, hipStream_t st);
+hipError_t launch_load_resources(const LoadArgs& a, const int64_t* seg_off, ResAgg* agg, hipStream_t st);
+hipError_t launch_unpack_sums(const ResAgg* agg, int64_t n, int64_t* count, double* sum_has, double* sum_wants,
+                              hipStream_t st);
 }  // namespace dm

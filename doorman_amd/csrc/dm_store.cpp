@@ -1,5 +1,6 @@
 // dm_store.cpp — a store and its configuration onto the device (dm_store_load,
-// dm_config_load) and the calls that read them back (dm_read_*).
+// dm_store_load_device, dm_config_load) and the calls that read them back (dm_read_*, into
+// host memory or, dm_read_*_device, into device memory).
 #include "dm_ctx.h"
 
 // Could some non-small resource need k_general (heterogeneous subclients or NaN
@@ -21,6 +22,55 @@ static bool scan_maybe_general(const int64_t* off, int64_t R, const int64_t* sub
   return false;
 }
 
+// A store was just loaded: the four columns, the running sums and the explicit flags are
+// on the device (enqueued on the context stream).  What both loads do from there, so that
+// they cannot drift apart: the layout on host and device, the row index, the plan, and the
+// host's flags and state.  seg_off: the layout in host memory; dev_seg_off: the same in device
+// memory where the caller has it there (copied in HBM), else null (uploaded).
+static int store_loaded(dm_ctx* c, int64_t R, int64_t N, const int64_t* seg_off, const int64_t* dev_seg_off,
+                        bool maybe_general, bool all_sub_one) {
+  c->R = R;
+  c->N = N;
+  c->h_seg_off.assign(seg_off, seg_off + R + 1);
+  c->seg_uniform = uniform_rows(seg_off, R);  // every resource the same number of rows (a hierarchy root store: G)
+  hipStream_t st = c->stream;
+  if (dev_seg_off) {
+    DM_HIP(c, c->seg_off.ensure((size_t)R + 1), "copy seg_off");
+    DM_HIP(c, hipMemcpyAsync(c->seg_off.p, dev_seg_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, st),
+           "copy seg_off");
+  } else {
+    DM_HIP(c, upload(c->seg_off, seg_off, (size_t)R + 1, st), "upload seg_off");
+  }
+  {  // RowIndex: resource of the first row of every 2^kRowBlkShift-row block
+    const int64_t nb = (N >> kRowBlkShift) + 2;
+    std::vector<int32_t> blk((size_t)nb, 0);
+    int64_t sg = 0;
+    for (int64_t b = 0; b < nb && R > 0; ++b) {
+      const int64_t row = std::min<int64_t>(b << kRowBlkShift, std::max<int64_t>(N - 1, 0));
+      while (sg + 1 < R && seg_off[sg + 1] <= row) ++sg;
+      blk[(size_t)b] = (int32_t)sg;
+    }
+    DM_HIP(c, upload(c->blk_seg, blk.data(), blk.size(), st), "upload row index");
+    DM_HIP(c, hipStreamSynchronize(st), "upload row index");  // blk leaves scope
+  }
+  build_plan(c);
+  int rc = upload_plan(c);
+  if (rc) return rc;
+  c->maybe_general = maybe_general;
+  c->all_sub_one = all_sub_one;
+  DM_HIP(c, hipStreamSynchronize(st), "store load");
+  c->store_loaded = true;
+  c->cl_valid = false;  // the last clean's list named rows of the store this one replaced
+  c->store_lost = false;  // upload_plan cleared the device's failure words
+  c->expl_rows = true;
+  c->rows_changed();
+  c->have_result = false;
+  c->wb_inplace = -1;
+  c->hints_set = false;
+  if (c->cfg_loaded && (int64_t)c->h_refresh_s.size() != R) c->cfg_loaded = false;
+  return DM_OK;
+}
+
 int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
   DM_ENTER(c);
   async_drain(c);
@@ -39,24 +89,7 @@ int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
   if ((s->agg_count || s->agg_sum_has || s->agg_sum_wants) && !have_agg)
     return c->fail(DM_E_INVAL, "give all three running sums or none");
   DM_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  c->R = R;
-  c->N = N;
-  c->h_seg_off.assign(s->seg_off, s->seg_off + R + 1);
-  c->seg_uniform = uniform_rows(s->seg_off, R);  // every resource the same number of rows (a hierarchy root store: G)
   hipStream_t st = c->stream;
-  DM_HIP(c, upload(c->seg_off, s->seg_off, (size_t)R + 1, st), "upload seg_off");
-  {  // RowIndex: resource of the first row of every 2^kRowBlkShift-row block
-    const int64_t nb = (N >> kRowBlkShift) + 2;
-    std::vector<int32_t> blk((size_t)nb, 0);
-    int64_t sg = 0;
-    for (int64_t b = 0; b < nb && R > 0; ++b) {
-      const int64_t row = std::min<int64_t>(b << kRowBlkShift, std::max<int64_t>(N - 1, 0));
-      while (sg + 1 < R && s->seg_off[sg + 1] <= row) ++sg;
-      blk[(size_t)b] = (int32_t)sg;
-    }
-    DM_HIP(c, upload(c->blk_seg, blk.data(), blk.size(), st), "upload row index");
-    DM_HIP(c, hipStreamSynchronize(st), "upload row index");  // blk leaves scope
-  }
   DM_HIP(c, upload(c->wants, s->wants, (size_t)N, st), "upload wants");
   DM_HIP(c, upload(c->has, s->has, (size_t)N, st), "upload has");
   {
@@ -92,25 +125,12 @@ int dm_store_load(dm_ctx* c, const dm_snapshot* s) {
   DM_HIP(c, upload(c->agg, agg.data(), (size_t)R, st), "upload running sums");
   const std::vector<uint8_t> expl((size_t)std::max<int64_t>(R, 1), 1);  // loaded rows carry explicit expiries
   DM_HIP(c, upload(c->expl, expl.data(), expl.size(), st), "upload explicit flags");
-  build_plan(c);
-  int rc = upload_plan(c);
-  if (rc) return rc;
-  c->maybe_general = scan_maybe_general(s->seg_off, R, s->subclients, s->wants, s->expiry_ns);
+  const bool maybe_general = scan_maybe_general(s->seg_off, R, s->subclients, s->wants, s->expiry_ns);
   // released rows never take part in a tick, so they do not count against this
-  c->all_sub_one = true;
-  for (int64_t i = 0; i < N && c->all_sub_one; ++i)
-    c->all_sub_one = s->subclients[i] == 1 || s->expiry_ns[i] == DM_RELEASED;
-  DM_HIP(c, hipStreamSynchronize(st), "store load");
-  c->store_loaded = true;
-  c->cl_valid = false;  // the last clean's list named rows of the store this one replaced
-  c->store_lost = false;  // upload_plan cleared the device's failure words
-  c->expl_rows = true;
-  c->rows_changed();
-  c->have_result = false;
-  c->wb_inplace = -1;
-  c->hints_set = false;
-  if (c->cfg_loaded && (int64_t)c->h_refresh_s.size() != R) c->cfg_loaded = false;
-  return DM_OK;
+  bool all_sub_one = true;
+  for (int64_t i = 0; i < N && all_sub_one; ++i)
+    all_sub_one = s->subclients[i] == 1 || s->expiry_ns[i] == DM_RELEASED;
+  return store_loaded(c, R, N, s->seg_off, nullptr, maybe_general, all_sub_one);
 }
 
 int dm_config_load(dm_ctx* c, int64_t R, const dm_resource_cfg* cfg) {
@@ -309,4 +329,151 @@ int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants,
     DM_HIP(c, download(sub, (const int64_t*)S.sub.p, 0, n, c->stream), "read subclients");
   }
   return c->synced("read store");
+}
+
+// ---- the store from and into device memory (dm_load.hip) ----
+
+// A caller's device column, for the four calls below: p must be device memory of the
+// context's device, and where the runtime knows p's allocation, that allocation must hold
+// `bytes` bytes from p.  Asked of the runtime before any kernel or copy is given p.
+static int check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // (a pointer the runtime does not know: plain host memory on older runtimes)
+    return c->fail(DM_E_INVAL, std::string(what) + " is not device memory");
+  }
+  if (at.type != hipMemoryTypeDevice) return c->fail(DM_E_INVAL, std::string(what) + " is not device memory");
+  if (at.device != c->device) return c->fail(DM_E_INVAL, std::string(what) + " is memory of another device");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();  // no allocation reported: the attributes are what there is
+    return DM_OK;
+  }
+  const char *b = (const char*)base, *q = (const char*)p;
+  if (q < b || (size_t)(q - b) > size || bytes > size - (size_t)(q - b))
+    return c->fail(DM_E_INVAL, std::string(what) + ": its allocation does not hold the column");
+  return DM_OK;
+}
+// every non-NULL pointer of a call, each with its bytes
+#define DM_DEVICE_PTR(ctx, p, count, what)                                                    \
+  do {                                                                                        \
+    if (p)                                                                                    \
+      if (int _rc = check_device_ptr(ctx, p, (size_t)(count) * 8, what)) return _rc;          \
+  } while (0)
+
+int dm_store_load_device(dm_ctx* c, const dm_snapshot* s) {
+  DM_ENTER(c);
+  async_drain(c);
+  if (!s || s->n_resources < 0 || s->n_leases < 0 || !s->seg_off) return c->fail(DM_E_INVAL, "bad snapshot");
+  const int64_t R = s->n_resources, N = s->n_leases;
+  if (R > INT32_MAX - 1) return c->fail(DM_E_INVAL, "too many resources for one context (max 2^31-2)");
+  if (N > 0 && (!s->wants || !s->has || !s->subclients || !s->expiry_ns))
+    return c->fail(DM_E_INVAL, "snapshot columns missing");
+  const bool have_agg = s->agg_count && s->agg_sum_has && s->agg_sum_wants;
+  if ((s->agg_count || s->agg_sum_has || s->agg_sum_wants) && !have_agg)
+    return c->fail(DM_E_INVAL, "give all three running sums or none");
+  DM_DEVICE_PTR(c, s->seg_off, R + 1, "seg_off");
+  DM_DEVICE_PTR(c, s->wants, N, "wants");
+  DM_DEVICE_PTR(c, s->has, N, "has");
+  DM_DEVICE_PTR(c, s->subclients, N, "subclients");
+  DM_DEVICE_PTR(c, s->expiry_ns, N, "expiry_ns");
+  DM_DEVICE_PTR(c, s->agg_count, R, "agg_count");
+  DM_DEVICE_PTR(c, s->agg_sum_has, R, "agg_sum_has");
+  DM_DEVICE_PTR(c, s->agg_sum_wants, R, "agg_sum_wants");
+  hipStream_t st = c->stream;
+  DM_HIP(c, hipStreamSynchronize(st), "sync");
+  // Validation reads the caller's columns only: the layout on the host (the plan is built
+  // from it anyway), the rows by k_ld_check.  A rejection leaves the store as it was.
+  std::vector<int64_t> off((size_t)R + 1);
+  DM_HIP(c, hipMemcpyAsync(off.data(), s->seg_off, off.size() * 8, hipMemcpyDeviceToHost, st), "read seg_off");
+  DM_HIP(c, hipStreamSynchronize(st), "read seg_off");
+  if (off[0] != 0 || off[(size_t)R] != N) return c->fail(DM_E_INVAL, "seg_off must run from 0 to n_leases");
+  for (int64_t r = 0; r < R; ++r)
+    if (off[(size_t)r + 1] < off[(size_t)r]) return c->fail(DM_E_INVAL, "seg_off must be non-decreasing");
+  DM_HIP(c, c->ld_flags.ensure(1), "load flags");
+  const LoadArgs a{R,           N,           s->wants,         s->has,        s->subclients, s->expiry_ns,
+                   s->agg_count, s->agg_sum_has, s->agg_sum_wants, c->ld_flags.p};
+  uint32_t f = 0;
+  DM_HIP(c, launch_load_check(a, st), "check rows");
+  DM_HIP(c, hipMemcpyAsync(&f, c->ld_flags.p, sizeof f, hipMemcpyDeviceToHost, st), "read load flags");
+  DM_HIP(c, hipStreamSynchronize(st), "check rows");
+  if (f & kLdBadSub) return c->fail(DM_E_INVAL, "subclients must be in [0, 2^31-2]");
+  // from here on the context's own columns are written
+  const size_t n = (size_t)N;
+  DM_HIP(c, c->wants.ensure(n), "store columns");
+  DM_HIP(c, c->has.ensure(n), "store columns");
+  DM_HIP(c, c->sub.ensure(n), "store columns");
+  DM_HIP(c, c->expiry.ensure(n), "store columns");
+  DM_HIP(c, c->agg.ensure((size_t)R), "running sums");
+  DM_HIP(c, c->expl.ensure((size_t)std::max<int64_t>(R, 1)), "explicit flags");
+  if (N > 0) {
+    DM_HIP(c, hipMemcpyAsync(c->wants.p, s->wants, n * 8, hipMemcpyDeviceToDevice, st), "copy wants");
+    DM_HIP(c, hipMemcpyAsync(c->has.p, s->has, n * 8, hipMemcpyDeviceToDevice, st), "copy has");
+    DM_HIP(c, hipMemcpyAsync(c->expiry.p, s->expiry_ns, n * 8, hipMemcpyDeviceToDevice, st), "copy expiry");
+  }
+  DM_HIP(c, launch_load_sub(a, c->sub.p, st), "load subclients");
+  DM_HIP(c, launch_load_resources(a, s->seg_off, c->agg.p, st), "load running sums");
+  DM_HIP(c, hipMemsetAsync(c->expl.p, 1, c->expl.n, st), "explicit flags");  // loaded rows carry explicit expiries
+  DM_HIP(c, hipMemcpyAsync(&f, c->ld_flags.p, sizeof f, hipMemcpyDeviceToHost, st), "read load flags");
+  DM_HIP(c, hipStreamSynchronize(st), "load rows");
+  return store_loaded(c, R, N, off.data(), s->seg_off, (f & kLdGeneral) != 0, !(f & kLdNotOne));
+}
+
+int dm_read_store_device(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  int rc = check_range(c, off, n, c->N);
+  if (rc) return rc;
+  DM_DEVICE_PTR(c, has, n, "has");
+  DM_DEVICE_PTR(c, wants, n, "wants");
+  DM_DEVICE_PTR(c, sub, n, "subclients");
+  DM_DEVICE_PTR(c, exp, n, "expiry_ns");
+  if (n > 0) {
+    hipStream_t st = c->stream;
+    if (has) DM_HIP(c, hipMemcpyAsync(has, c->has.p + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st), "read has");
+    if (wants)
+      DM_HIP(c, hipMemcpyAsync(wants, c->wants.p + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st), "read wants");
+    if (sub || exp)  // subclients and expiry from the column encoding (dm_device.h), into the caller's columns
+      DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, exp, sub, st),
+             "resolve rows");
+  }
+  return c->synced("read store");
+}
+
+int dm_read_store_sums_device(dm_ctx* c, int64_t r0, int64_t n, int64_t* count, double* sum_has, double* sum_wants) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  int rc = check_range(c, r0, n, c->R);
+  if (rc) return rc;
+  DM_DEVICE_PTR(c, count, n, "count");
+  DM_DEVICE_PTR(c, sum_has, n, "sum_has");
+  DM_DEVICE_PTR(c, sum_wants, n, "sum_wants");
+  // always the store's running sums (agg), never a non-writeback tick's view (res)
+  if (n > 0) DM_HIP(c, launch_unpack_sums(c->agg.p + r0, n, count, sum_has, sum_wants, c->stream), "read sums");
+  return c->synced("read sums");
+}
+
+int dm_read_leases_device(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
+  DM_ENTER(c);
+  DM_STORE_READABLE(c);
+  if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
+  int rc = check_range(c, off, n, c->N);
+  if (rc) return rc;
+  DM_DEVICE_PTR(c, gets, n, "gets");
+  DM_DEVICE_PTR(c, expiry_ns, n, "expiry_ns");
+  if (n > 0) {
+    hipStream_t st = c->stream;
+    const double* g = c->last_writeback ? c->has.p : c->out_gets.p;
+    if (gets) DM_HIP(c, hipMemcpyAsync(gets, g + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st), "read gets");
+    if (expiry_ns && c->last_writeback)  // the store's encoding, resolved on the device
+      DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, expiry_ns,
+                                    nullptr, st),
+             "resolve expiry");
+    else if (expiry_ns)
+      DM_HIP(c, hipMemcpyAsync(expiry_ns, c->out_expiry.p + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st),
+             "read expiry");
+  }
+  return c->synced("read leases");
 }

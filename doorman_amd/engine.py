@@ -265,6 +265,124 @@ class Engine:
                                       _ptr(out["subclients"]), _ptr(out["expiry_ns"])))
         return out
 
+    # -- the store from and into device memory (no row over PCIe) --
+    _DEV_COLS = (("seg_off", "int64"), ("wants", "float64"), ("has", "float64"), ("subclients", "int64"),
+                 ("expiry_ns", "int64"))
+    _DEV_AGG = (("agg_count", "int64"), ("agg_sum_has", "float64"), ("agg_sum_wants", "float64"))
+
+    def _device_snapshot(self, snap: dict):
+        """The columns of a device snapshot, checked without a context or a library call:
+        each a CUDA tensor of torch (or any object with data_ptr(), dtype, device and a
+        length) on this engine's device, of its dtype, contiguous, the row columns as long as
+        seg_off says.  Returns (n_resources, n_leases, {name: column})."""
+        import torch
+        want = torch.device("cuda", self.device)
+        have_agg = snap.get("agg_count") is not None
+        cols = {}
+        for name, dt in self._DEV_COLS + (self._DEV_AGG if have_agg else ()):
+            t = snap[name]
+            dev = torch.device(t.device)
+            if dev.type != "cuda":
+                raise ValueError(f"{name} is on {dev}: a device snapshot's columns live on {want}")
+            if dev.index is not None and dev.index != self.device:
+                raise ValueError(f"{name} is on {dev}, the engine on {want}")
+            if str(t.dtype).replace("torch.", "") != dt:
+                raise ValueError(f"{name} must be {dt}, not {t.dtype}")
+            if getattr(t, "ndim", 1) != 1 or (hasattr(t, "is_contiguous") and not t.is_contiguous()):
+                raise ValueError(f"{name} must be one contiguous column")
+            cols[name] = t
+        if len(cols["seg_off"]) < 1:
+            raise ValueError("seg_off must hold n_resources + 1 offsets")
+        R, N = len(cols["seg_off"]) - 1, len(cols["wants"])
+        for name, _ in self._DEV_COLS[1:]:
+            if len(cols[name]) != N:
+                raise ValueError(f"{name} has {len(cols[name])} rows, wants has {N}")
+        for name, _ in (self._DEV_AGG if have_agg else ()):
+            if len(cols[name]) != R:
+                raise ValueError(f"{name} has {len(cols[name])} entries for {R} resources")
+        return R, N, cols
+
+    def _torch_ready(self):
+        """Before a call that reads or writes torch's memory on the context stream: what
+        torch's current stream holds is done (a snapshot's producer; the earlier user of a
+        block the caching allocator just handed out)."""
+        import torch
+        torch.cuda.current_stream(self.device).synchronize()
+        return torch
+
+    def load_store_device(self, snap: dict):
+        """dm_store_load_device: load_store from columns in this device's memory (the same
+        keys; torch CUDA tensors).  Leaves the state load_store would for the same values."""
+        R, N, cols = self._device_snapshot(snap)
+        torch = self._torch_ready()
+        seg_off = torch.as_tensor(cols["seg_off"], device=torch.device("cuda", self.device)).cpu().numpy()
+        if N != int(seg_off[-1]):
+            raise ValueError(f"the row columns hold {N} rows, seg_off ends at {int(seg_off[-1])}")
+        s = _lib.Snapshot()
+        s.n_resources, s.n_leases = R, N
+        for name, t in cols.items():
+            setattr(s, name, t.data_ptr() or None)
+        self._chk(self._L.dm_store_load_device(self._ctx, ctypes.byref(s)))
+        self.n_resources, self.n_leases = R, N
+        self.seg_off = seg_off.astype(np.int64, copy=True)
+
+    def load_device(self, snap: dict):
+        """load() with the store's columns in device memory (the configuration stays on the host)."""
+        self.load_store_device(snap)
+        self.load_config(snap)
+
+    def _device_out(self, torch, n, names, columns):
+        dt = {"has": torch.float64, "wants": torch.float64, "gets": torch.float64, "sum_has": torch.float64,
+              "sum_wants": torch.float64}
+        for k in columns:
+            if k not in names:
+                raise ValueError(f"unknown column {k!r}: one of {names}")
+        dev = torch.device("cuda", self.device)
+        out = {k: torch.empty(n, dtype=dt.get(k, torch.int64), device=dev) for k in names if k in columns}
+        return out, [out[k].data_ptr() or None if k in out else None for k in names]
+
+    def read_store_device(self, off: int = 0, n: int | None = None, columns=None) -> dict:
+        """dm_read_store_device: read_store into torch tensors on this device (columns: a
+        subset of has, wants, subclients, expiry_ns; default all)."""
+        names = ("has", "wants", "subclients", "expiry_ns")
+        n = self.n_leases - off if n is None else n
+        torch = self._torch_ready()
+        out, ptrs = self._device_out(torch, max(int(n), 0), names, names if columns is None else columns)
+        self._chk(self._L.dm_read_store_device(self._ctx, int(off), int(n), *ptrs))
+        return out
+
+    def store_sums_device(self, r0: int = 0, n: int | None = None, columns=None) -> dict:
+        """dm_read_store_sums_device: the store's running sums (count, sum_has, sum_wants: what
+        a load takes as agg_*) as torch tensors on this device."""
+        names = ("count", "sum_has", "sum_wants")
+        n = self.n_resources - r0 if n is None else n
+        torch = self._torch_ready()
+        out, ptrs = self._device_out(torch, max(int(n), 0), names, names if columns is None else columns)
+        self._chk(self._L.dm_read_store_sums_device(self._ctx, int(r0), int(n), *ptrs))
+        return out
+
+    def leases_device(self, off: int = 0, n: int | None = None):
+        """dm_read_leases_device: leases() as (gets, expiry_ns) torch tensors on this device."""
+        names = ("gets", "expiry_ns")
+        n = self.n_leases - off if n is None else n
+        torch = self._torch_ready()
+        out, ptrs = self._device_out(torch, max(int(n), 0), names, names)
+        self._chk(self._L.dm_read_leases_device(self._ctx, int(off), int(n), *ptrs))
+        return out["gets"], out["expiry_ns"]
+
+    def clone_store_to(self, other: "Engine"):
+        """The store, running sums included, into `other` (an engine on the same device)
+        without a row leaving HBM: the two store reads into device tensors, then
+        other.load_store_device with the sums carried."""
+        if other.device != self.device:
+            raise ValueError(f"clone_store_to: the other engine is on device {other.device}, this one on {self.device}")
+        st = self.read_store_device()
+        sums = self.store_sums_device()
+        torch = self._torch_ready()
+        st["seg_off"] = torch.from_numpy(np.ascontiguousarray(self.seg_off, np.int64)).to(st["has"].device)
+        st.update(agg_count=sums["count"], agg_sum_has=sums["sum_has"], agg_sum_wants=sums["sum_wants"])
+        other.load_store_device(st)
+
     # -- the batch algorithm --
     def apportion(self, now_ns: int, writeback: bool = False, recompute: bool = False, asynchronous: bool = False,
                   wb_columns: str = "auto", defer_join: bool = False):

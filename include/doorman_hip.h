@@ -392,6 +392,54 @@ int dm_read_leases_proto(dm_ctx* ctx, int64_t off, int64_t n, double* capacity, 
 int dm_read_resources(dm_ctx* ctx, int64_t r0, int64_t n, int64_t* count, double* sum_has, double* sum_wants,
                       double* safe_capacity);
 
+/* ---- the store from and into device memory: no row over PCIe ---- */
+/* dm_store_load from device memory: the same dm_snapshot, every non-NULL pointer in it
+   device memory of the context's device (a snapshot a kernel generated, another context's
+   store read by the calls below, a shard on its way to another context of the same GPU).
+     The columns are read on the context stream and the call is synchronous on return.  The
+       caller makes sure that whatever produced the columns has finished (or is ordered
+       before the context stream) when the call is made; they may be reused after it.
+     After a successful call the context is in exactly the state dm_store_load would leave for
+       the same values in host memory: the four columns as dm_read_store reports them, the
+       running sums as dm_read_resources reports them bit for bit, the same plan, ticks that
+       launch the same kernels, no last tick (dm_read_leases: DM_E_STATE), a configuration
+       of another resource count stale.  In-flight dm_store_apply_async batches finish
+       first and their outcome is dropped, as by dm_store_load.
+     Running sums: agg_* as given; when they are NULL, those of one Assign per row in row
+       order (store.go:156-158): from +0.0, sum += has[i] for i ascending within the resource,
+       likewise wants and the count -- the additions dm_store_load makes on the host, in
+       their order, so one resource's additions are a serial chain on the device (a wave per
+       resource; a resource of 10^6 rows is a few milliseconds of one wave).
+     Over PCIe: seg_off to the host (8 (n_resources + 1) B: the plan is built there), a few
+       flag words, and the plan and the row index to the device as after dm_store_load.
+     DM_E_INVAL, the previous store exactly as it was (validation reads the caller's columns
+       only, before any column of the context is written): seg_off not from 0, not ending at
+       n_leases or decreasing; a subclients value outside [0, 2^31 - 2] (found on the device);
+       two of the three agg_*; columns missing with n_leases > 0; n_resources > 2^31 - 2; a
+       pointer that hipPointerGetAttributes does not report as device memory of the context's
+       device (plain host memory included); a pointer whose allocation, where
+       hipMemGetAddressRange reports one, does not hold the column's bytes.  No kernel or
+       copy is given a pointer that failed these checks. */
+int dm_store_load_device(dm_ctx* ctx, const dm_snapshot* snap);
+/* The device twins of dm_read_store, of dm_read_resources' count and sums, and of
+   dm_read_leases: the same values bit for bit (subclients and expiries resolved from the
+   column encoding; gets from the has column after a writeback tick, from the tick's output
+   columns after another), written into device memory of the context's device on the
+   context stream, synchronous on return.  Preconditions and error codes are the twin's
+   (DM_E_STATE without a store / without a tick's result, DM_E_RANGE; a lost store can be
+   read); any destination may be NULL and is skipped; the others pass the pointer checks of
+   dm_store_load_device (DM_E_INVAL, nothing written).  dm_read_store_device and
+   dm_read_store_sums_device of one context followed by dm_store_load_device on another,
+   with the sums as agg_*, is a device-to-device clone of the store.
+     dm_read_store_sums_device always reports the store's running sums, the ones a load
+       takes as agg_* -- after a tick without DM_WRITEBACK too, where dm_read_resources
+       reports that tick's view.  Hence the other name. */
+int dm_read_store_device(dm_ctx* ctx, int64_t off, int64_t n, double* has, double* wants, int64_t* subclients,
+                         int64_t* expiry_ns);
+int dm_read_store_sums_device(dm_ctx* ctx, int64_t r0, int64_t n, int64_t* count, double* sum_has,
+                              double* sum_wants);
+int dm_read_leases_device(dm_ctx* ctx, int64_t off, int64_t n, double* gets, int64_t* expiry_ns);
+
 /* ---- hierarchy (intermediate servers) ---- */
 /* server.go:850-879: wants_total = sum(wants), subclients_total = sum(num_clients);
  * DM_E_ARGUMENT when some num_clients < 1 */
