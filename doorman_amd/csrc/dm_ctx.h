@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/doorman_hip.h"
+#include "dm_carry_rule.h"
 #include "dm_device.h"
 #include "dm_large_form.h"
 #include "dm_launch.h"
@@ -783,6 +784,19 @@ struct dm_ctx {
   void* hs_gathered = nullptr;
   ncclComm_t nccl_comm = nullptr;
   bool hs_ordered = false;  // dm_hier_step already ordered the exchange stream after the tick
+  // The carried round (dm_carry_rule.h).  Root side: the launch arguments dm_hier_step kept
+  // instead of launching (everything else the round does on the host is done: the slot is
+  // staged, the epochs moved), and whether dm_hier_step holds it for its own tick.  The raw
+  // pointers in it survive commit_templates' swaps (a DBuf swap moves ownership, not memory)
+  // and every call that could free or replace a buffer flushes first.  Leaf side: the root
+  // that may hold a round for this leaf (dm_hier_attach).  DM_CARRY_ROUND=0: never carried.
+  // rounds_in_tick (both sides, dm_plan_info slot 29): the rounds that ran inside a leaf
+  // launch since the store was loaded.
+  int carry_ok = 1;
+  bool carried = false, carry_held = false;
+  RootRound carried_round{};
+  dm_ctx* carry_root = nullptr;
+  int64_t rounds_in_tick = 0;
   // a stream part's auxiliary stream (part 0: the bin's class stream).  Part 1 beside
   // bins 4-6's stream 1: stream 2 or 0 run C1 at 40.6-40.8 us per tick, stream 3 at
   // 61.6-64.2 us (which hardware queues pair well: take_aux; profiles/r05_parts_ab.txt)
@@ -866,19 +880,35 @@ struct dm_ctx {
   }
 };
 
+namespace dm {
+// dm_hier_host.cpp: the carried root round (dm_carry_rule.h) of c or of its attached peer,
+// launched now unless dm_hier_step holds it; and the launch itself
+int flush_carried(dm_ctx* c);
+int launch_carried(dm_ctx* root);
+}
+
 #define DM_HIP(ctx, expr, what)                  \
   do {                                           \
     hipError_t _e = (expr);                      \
     if (_e != hipSuccess) return (ctx)->hip_fail(_e, what); \
   } while (0)
 
-#define DM_CHECK_CTX(ctx)                                   \
+#define DM_CHECK_CTX_KEEP(ctx)                              \
   do {                                                      \
     if (!(ctx)) {                                           \
       dm::set_last_error("null context");                   \
       return DM_E_INVAL;                                    \
     }                                                       \
     DM_HIP(ctx, hipSetDevice((ctx)->device), "hipSetDevice"); \
+  } while (0)
+
+// Entry of every exported call that takes a context: a root round carried for the context
+// or for its attached peer is launched first (dm_carry_rule.h flush_round; dm_hier_step
+// alone enters with DM_CHECK_CTX_KEEP and holds the round for its own tick).
+#define DM_CHECK_CTX(ctx)                                     \
+  do {                                                        \
+    DM_CHECK_CTX_KEEP(ctx);                                   \
+    if (int _fl = dm::flush_carried(ctx)) return _fl;         \
   } while (0)
 
 // Entry of every call that puts work on the context stream: join the auxiliary

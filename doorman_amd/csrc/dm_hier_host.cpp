@@ -115,7 +115,10 @@ static hipError_t wait_leaf(dm_ctx* leaf, TickWait how, hipStream_t s) {
 // its leaf -- in place, or into a staged slot the leaf takes one tick later
 // (dm_hier_pipeline).  Stream-ordered: the all-gather that produced `gathered`
 // must precede it on the root's stream.
-int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t now_ns, dm_ctx* leaf, int server) {
+// carry (dm_hier_step, dm_carry_rule.h carry_round): everything but the launch, whose arguments
+// the root keeps as its carried round; errors found up to there are this call's.
+static int root_round(dm_ctx* root, const void* gathered, int n_servers, int64_t now_ns, dm_ctx* leaf, int server,
+                      bool carry) {
   DM_ENTER(root);
   DM_STORE_OK(root);
   if (!root->store_loaded || !root->cfg_loaded) return root->fail(DM_E_STATE, "root store / config not loaded");
@@ -221,8 +224,13 @@ int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t
   ha.G = n_servers;
   ha.K = K;
   ha.server = server;
-  DM_HIP(root, root->timed(KC_HIER_ROOT, root->stream, [&] { return launch_hier_tick(p, ha, root->stream); }),
-         "hierarchy root tick");
+  if (carry) {
+    root->carried_round = RootRound{p, ha};
+    root->carried = true;
+  } else {
+    DM_HIP(root, root->timed(KC_HIER_ROOT, root->stream, [&] { return launch_hier_tick(p, ha, root->stream); }),
+           "hierarchy root tick");
+  }
   if (slot >= 0) {
     if (same)  // the leaf's ticks follow in stream order
       leaf->order.xs_signal_lazy(StreamOrder::XS_READY0 + slot, root->stream, &tp.ready[slot]);
@@ -238,6 +246,28 @@ int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t
   root->last_writeback = true;
   root->have_result = true;
   return DM_OK;
+}
+
+int dm_hier_root_tick(dm_ctx* root, const void* gathered, int n_servers, int64_t now_ns, dm_ctx* leaf, int server) {
+  return root_round(root, gathered, n_servers, now_ns, leaf, server, false);
+}
+
+// The carried round as a launch of its own on the root's stream: what the round would have
+// been without the carry, at a later place of the same stream.
+int dm::launch_carried(dm_ctx* root) {
+  root->carried = false;
+  const RootRound& r = root->carried_round;
+  DM_HIP(root, root->timed(KC_HIER_ROOT, root->stream, [&] { return launch_hier_tick(r.p, r.ha, root->stream); }),
+         "hierarchy root tick");
+  return DM_OK;
+}
+
+int dm::flush_carried(dm_ctx* c) {
+  dm_ctx* root = c->carried ? c : c->carry_root;
+  if (!root || !flush_round(root->carried, root->carry_held)) return DM_OK;
+  const int rc = launch_carried(root);
+  if (rc && root != c) c->fail(rc, "carried root round: " + root->err);
+  return rc;
 }
 
 // librccl, loaded on first use: the copy torch already mapped if there is one (one
@@ -332,12 +362,18 @@ int dm_hier_attach(dm_ctx* leaf, dm_ctx* root, int server, void* const* ring, in
   if (server < 0 || server >= root->hier_G) return root->fail(DM_E_RANGE, "server index out of range");
   if (nring < 3 || !ring) return root->fail(DM_E_INVAL, "the publish ring needs at least 3 blocks");
   if (root->hier_G > 1 && !gathered) return root->fail(DM_E_INVAL, "several servers need a gathered buffer");
-  int rc = dm_publish_ring(leaf, nring, ring);
-  if (rc) return rc;
+  int rc = flush_carried(leaf);  // (a round another root carries for this leaf)
+  if (rc) return root->fail(rc, "leaf: " + leaf->err);
+  if ((rc = dm_publish_ring(leaf, nring, ring))) return rc;
   if ((rc = dm_hier_pipeline(leaf, leaf->tpl.on ? leaf->tpl.q.lag : 1))) return rc;
   if ((rc = dm_set_stream(root, exchange_stream ? exchange_stream : leaf->stream))) return rc;
   // an exchange on a stream of its own waits for every leaf tick: no stream parts
   if ((rc = set_parts_ok(leaf, root->stream == leaf->stream))) return rc;
+  // the pair's back-pointers: the leaf reaches a round its root carries (dm_carry_rule.h)
+  if (root->hs_leaf && root->hs_leaf != leaf && root->hs_leaf->carry_root == root) root->hs_leaf->carry_root = nullptr;
+  if (leaf->carry_root && leaf->carry_root != root && leaf->carry_root->hs_leaf == leaf)
+    leaf->carry_root->hs_leaf = nullptr;
+  leaf->carry_root = root;
   root->hs_leaf = leaf;
   root->hs_server = server;
   root->hs_ring.assign(ring, ring + nring);
@@ -345,11 +381,28 @@ int dm_hier_attach(dm_ctx* leaf, dm_ctx* root, int server, void* const* ring, in
   return DM_OK;
 }
 
+namespace {
+// dm_hier_step holds a carried round for its own leaf tick: the calls it makes do not flush it.
+struct CarryHold {
+  dm_ctx* root;
+  explicit CarryHold(dm_ctx* r) : root(r) { root->carry_held = true; }
+  ~CarryHold() { root->carry_held = false; }
+};
+}  // namespace
+
 int dm_hier_step(dm_ctx* leaf, dm_ctx* root, int64_t now_ns) {
-  DM_CHECK_CTX(root);
-  if (!leaf || root->hs_leaf != leaf) return root->fail(DM_E_STATE, "dm_hier_attach this leaf to the root first");
+  DM_CHECK_CTX_KEEP(root);
+  if (!leaf || root->hs_leaf != leaf) {
+    if (int rc = flush_carried(root)) return rc;
+    return root->fail(DM_E_STATE, "dm_hier_attach this leaf to the root first");
+  }
+  // The last step's round, when carried, rides in this step's leaf tick or is launched ahead
+  // of its launches (dm_tick.cpp, by dm_carry_rule.h place_round); this step's is carried in
+  // its turn when the rule allows.
+  CarryHold hold(root);
   int rc = dm_apportion(leaf, now_ns, DM_WRITEBACK | DM_ASYNC | DM_DEFER_JOIN);
   if (rc) return root->fail(rc, "leaf tick: " + leaf->err);  // callers read the root's message
+  if (root->carried && (rc = launch_carried(root))) return rc;  // (never: the tick placed it)
   const int64_t n = (int64_t)root->hs_ring.size();
   void* block = root->hs_ring[(size_t)((leaf->pub_k - 1) % n)];  // what this tick published
   const int G = root->hier_G;
@@ -385,7 +438,12 @@ int dm_hier_step(dm_ctx* leaf, dm_ctx* root, int64_t now_ns) {
     gathered = root->hs_gathered;
   }
   root->hs_ordered = G > 1;
-  rc = dm_hier_root_tick(root, gathered, G, now_ns, leaf, root->hs_server);
+  CarryInputs ci;
+  ci.carry_ok = root->carry_ok != 0;
+  ci.servers = G;
+  ci.same_stream = root->stream == leaf->stream;
+  ci.pipelined = leaf->tpl.on;
+  rc = root_round(root, gathered, G, now_ns, leaf, root->hs_server, carry_round(ci));
   root->hs_ordered = false;
   return rc;
 }

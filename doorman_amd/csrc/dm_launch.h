@@ -69,8 +69,19 @@ struct FusedArgs {
   int32_t* host_rest;                     // (host-mapped) the rest items' two-slot ring (SplitSlot::fused_queued)
   int32_t *glist, *gcount;                // k_general's worklist and its count
 };
-hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedArgs& a, hipEvent_t done,
-                            hipStream_t st);
+// A root round that rides in the launch (dm_carry_rule.h; k_block_fused's ROOT build): the
+// DevParams / HierArgs pair launch_hier_tick would have taken, the round's own `now` in p.now.
+// One server, one root row per resource (K = 1), and the launch's items are every resource of
+// the leaf: the lane of leaf item i decides root resource ha.leaf_lo + items[i].seg.
+struct RootRound {
+  DevParams p;
+  HierArgs ha;
+};
+// round: null, or the round the launch carries (launch_bin_fused_root, dm_tick_fused_root.hip)
+hipError_t launch_bin_fused_root(const BinItems& w, const DevParams& p, const FusedArgs& a, const RootRound& round,
+                                 hipEvent_t done, hipStream_t st);
+hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedArgs& a, const RootRound* round,
+                            hipEvent_t done, hipStream_t st);
 // dm_tick_large.hip
 int redo_blocks_per_cu();
 // The chain's one launcher takes the phase (dm_large_form.h LargePhase: each names its

@@ -175,6 +175,7 @@ int dm_create(int device, dm_ctx** out) {
   if (const char* cy = getenv("DM_CYCLE")) c->cycle_ok = atoi(cy) != 0;
   if (const char* fu = getenv("DM_FUSED")) c->fused_ok = atoi(fu);
   if (const char* cb = getenv("DM_CYCLE_BYTES")) c->cycle_bytes = atoll(cb);
+  if (const char* cr = getenv("DM_CARRY_ROUND")) c->carry_ok = atoi(cr) != 0;
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
   // hardware queue.  Plain streams share the process's GPU_MAX_HW_QUEUES (4) queues
@@ -208,6 +209,11 @@ int dm_create(int device, dm_ctx** out) {
 void dm_destroy(dm_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
+  // a carried round (dm_carry_rule.h) is launched before either context of the pair goes: the
+  // root store holds it, and the leaf's template slots it writes outlive it (the drain below)
+  (void)flush_carried(c);
+  if (c->carry_root && c->carry_root->hs_leaf == c) c->carry_root->hs_leaf = nullptr;
+  if (c->hs_leaf && c->hs_leaf->carry_root == c) c->hs_leaf->carry_root = nullptr;
   if (c->nccl_comm) {
     rccl_destroy(rccl_api(), c->nccl_comm);
     c->nccl_comm = nullptr;
@@ -332,7 +338,7 @@ int dm_reset_kernel_times(dm_ctx* c) {
 
 int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
   if (!c || !out) return DM_E_INVAL;
-  int64_t v[20 + kNumBins];
+  int64_t v[21 + kNumBins];
   v[0] = (int64_t)c->h_tiles.size();
   for (int b = 0; b < kNumBins; ++b) v[1 + b] = (int64_t)c->h_bins[b].size();
   v[1 + kNumBins] = (int64_t)c->h_large.size();
@@ -373,7 +379,8 @@ int dm_plan_info(dm_ctx* c, int64_t* out, int max) {
     v[18 + kNumBins] += (int64_t)(uint32_t)__atomic_load_n(s.sweep.h, __ATOMIC_RELAXED);
     v[19 + kNumBins] += s.read_queued();
   }
-  const int n = 20 + kNumBins;
+  v[20 + kNumBins] = c->rounds_in_tick;  // root rounds that ran inside a leaf launch since the store was loaded
+  const int n = 21 + kNumBins;
   for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
   return n;
 }

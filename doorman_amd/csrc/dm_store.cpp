@@ -60,6 +60,7 @@ static int store_loaded(dm_ctx* c, int64_t R, int64_t N, const int64_t* seg_off,
   c->all_sub_one = all_sub_one;
   DM_HIP(c, hipStreamSynchronize(st), "store load");
   c->store_loaded = true;
+  c->rounds_in_tick = 0;
   c->cl_valid = false;  // the last clean's list named rows of the store this one replaced
   c->store_lost = false;  // upload_plan cleared the device's failure words
   c->expl_rows = true;

@@ -163,6 +163,10 @@ struct Tick {
   int nch = 0;
   int32_t *gl = nullptr, *gc = nullptr;  // k_general's worklist and its count
   bool general = false, fork = false, one_class = false;
+  // A root round carried for this leaf (dm_carry_rule.h), when the tick's shape lets it ride:
+  // bin_part places it once the part's form is chosen.
+  dm_ctx* ride_root = nullptr;
+  TickShape shape;
 
   template <typename F>
   hipError_t timed(int cls, hipStream_t s, F&& fn) {
@@ -185,7 +189,8 @@ struct Tick {
     hipEvent_t done;  // the part's tick event, for its last kernel (null: no queue waits for the tick)
   };
   int bin_part(int b, int lb, int nparts, int j);
-  int launch_fused(Part& pt, const PartForm& f);       // the sweep, its row kernel and the rest kernel as one launch
+  // the sweep, its row kernel and the rest kernel as one launch; round: the root round it carries, or null
+  int launch_fused(Part& pt, const PartForm& f, const RootRound* round);
   int launch_dense_form(Part& pt, const PartForm& f);  // the dense kernel in the form's build, or the sweep
   int launch_rest(Part& pt, const PartForm& f);        // the rest kernel over what it queued
   int launch_mixed(Part& pt);                          // the one-kernel form
@@ -427,8 +432,17 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
     cycle_auto_step(sl.cyc, ai, f);
   }
   int rc = DM_OK;
+  const RootRound* round = nullptr;
+  if (ride_root) {  // the carried round: in this part's one launch, or ahead of its launches
+    if (place_round(shape, f.fused) == RoundPlace::ride) {
+      round = &ride_root->carried_round;
+    } else {
+      if ((rc = launch_carried(ride_root))) return c->fail(rc, "carried root round: " + ride_root->err);
+      ride_root = nullptr;
+    }
+  }
   if (f.fused)
-    rc = launch_fused(pt, f);
+    rc = launch_fused(pt, f, round);
   else if (!f.split)
     rc = launch_mixed(pt);
   else if (!(rc = launch_dense_form(pt, f)) && !f.skip_rest)
@@ -445,7 +459,7 @@ int Tick::bin_part(int b, int lb, int nparts, int j) {
 // the first row kernel after a fused launch finds its last-told words cleared (a change of
 // form is rare; a steady part pays nothing).  The rest items have a host word of their own
 // (SplitSlot::fused_queued), read in place of `queued` until the next split launch.
-int Tick::launch_fused(Part& pt, const PartForm& f) {
+int Tick::launch_fused(Part& pt, const PartForm& f, const RootRound* round) {
   SplitSlot& sl = pt.sl;
   if (!sl.fu_cnt.p) {
     DM_HIP(c, sl.fu_cnt.ensure(8), "fused count");  // k_block_fused has the layout
@@ -454,8 +468,14 @@ int Tick::launch_fused(Part& pt, const PartForm& f) {
   }
   const FusedArgs a{sl.keys(), f.cycle ? sl.aux() : nullptr, sl.fu_cnt.p, sl.fpar, !sl.ran_fused,
                     (unsigned long long*)sl.sweep.d, (unsigned long long)c->row_epoch, sl.fused_queued.d, gl, gc};
-  DM_HIP(c, timed(KC_DENSE3 + (sl.b - 3), pt.s, [&] { return launch_bin_fused(pt.w, pt.p, a, pt.done, pt.s); }),
+  DM_HIP(c, timed(KC_DENSE3 + (sl.b - 3), pt.s, [&] { return launch_bin_fused(pt.w, pt.p, a, round, pt.done, pt.s); }),
          "group kernel (fused)");
+  if (round) {  // the round ran in the launch
+    ride_root->carried = false;
+    ride_root->rounds_in_tick += 1;
+    c->rounds_in_tick += 1;
+    ride_root = nullptr;
+  }
   sl.fpar ^= 1;
   sl.ran_fused = true;
   return DM_OK;
@@ -569,6 +589,29 @@ int dm_apportion(dm_ctx* c, int64_t now_ns, uint32_t flags) {
   c->tpl.q.tick();
   c->done.sig.begin();
   Tick t{c, now_ns, flags};
+  // A round carried for this leaf is still here only under dm_hier_step's hold (every other
+  // entry launched it): it rides if the tick can only be one launch of a workgroup bin over
+  // every resource, else it runs ahead of the tick's launches, where it ran before.
+  if (dm_ctx* root = c->carry_root; root && root->carried) {
+    TickShape& sh = t.shape;
+    sh.work_classes = (c->h_tiles.empty() ? 0 : 1) + (c->h_chunks.empty() ? 0 : 1);
+    sh.split_bin = false;
+    for (int b = 0; b < kNumBins; ++b) {
+      if (c->h_bins[b].empty()) continue;
+      sh.work_classes += 1;
+      sh.split_bin = dm_ctx::is_split_bin(b);
+      sh.parts = c->bin_parts[b];
+      sh.items = (int64_t)c->h_bins[b].size();
+    }
+    sh.general = (c->maybe_general || c->async_may_general()) && c->n_nonsmall > 0;
+    sh.writeback = (flags & DM_WRITEBACK) != 0;
+    sh.resources = c->R;
+    if (may_ride(sh) && root->stream == c->stream) {
+      t.ride_root = root;
+    } else if ((rc = launch_carried(root))) {
+      return c->fail(rc, "carried root round: " + root->err);
+    }
+  }
   if ((rc = t.outputs()) || (rc = t.streams()) || (rc = t.large_chain()) || (rc = t.subs()) ||
       (rc = t.bins()))
     return rc;

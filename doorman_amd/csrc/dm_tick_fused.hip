@@ -13,6 +13,7 @@
 // rest body itself, with the same group_segment calls the list kernels and k_block_rest make.
 // No workgroup waits for another and there is no word that every workgroup updates: a workgroup
 // adds its counts to the device words only when they are not zero.
+#include "dm_hier_round.h"
 #include "dm_tick_group.h"
 
 namespace dm {
@@ -52,18 +53,36 @@ static_assert(sizeof(FusedEntry) == 40, "ten dwords");
 // lapse before its next choice as it does from k_block_rest (try_split: a part most of whose
 // items are rest items runs the mixed kernel); workgroup 0 zeroes the other slot for the next
 // fused tick, when fcnt[2 s + 1], the same count on the device, says it is not zero.
-template <int G, int R, bool CYCLE>
+//
+// ROOT: the launch also carries the root's exchange round of the previous step (dm_carry_rule.h
+// has the rule and why no order is lost; RootRound, dm_launch.h).  Every lane that holds an item
+// decides the round for that item's resource, rest items and items without a hint word included
+// (dm_hier_round.h, K = 1): its loads are issued with the item's own, before the first of
+// either is consumed, so the two dependency chains are in flight together, and its registers
+// are dead before step 2.  The round reads the block the previous tick published and the root's
+// store and configuration, and writes the root's rows and sums and a free template slot: nothing
+// this tick's sweep touches, and nothing of another lane's.  Workgroup 0 writes the round's
+// status word as k_hier_tick's does.  The builds without it take an empty argument and keep
+// their device code.
+struct NoRound {};
+template <bool ROOT>
+using RoundArg = std::conditional_t<ROOT, RootRound, NoRound>;
+
+template <int G, int R, bool CYCLE, bool ROOT>
 __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __restrict__ items, int nitems,
                                                    FixKey* __restrict__ keys, CycAux* __restrict__ aux, int32_t* fcnt,
                                                    int par, int fresh, unsigned long long* host_count,
                                                    unsigned long long epoch, int32_t* host_rest,
-                                                   int32_t* general_list, int32_t* general_count) {
+                                                   int32_t* general_list, int32_t* general_count,
+                                                   RoundArg<ROOT> rnd) {
   constexpr int C = kFusedChunk<G>, W = G / 64;
   static_assert(G >= 64 && C <= G, "one item per lane");
   __shared__ Lds<G> lds;
   __shared__ FusedEntry ent[C];
   __shared__ int wtot[W];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if constexpr (ROOT)  // the round's flags (dm_hier_status)
+      rnd.ha.status_out[0] = pub_flags(rnd.ha.gathered[0].x);
     int32_t* prev = fcnt + 2 * (par ^ 1);
     const int listed = prev[0], rest = prev[1];
     if (fresh) {
@@ -95,6 +114,12 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
     wi = items[i];
     const FixKey fk = keys[i];
     if constexpr (CYCLE) ax = aux[i];
+    [[maybe_unused]] HierLane rln;
+    [[maybe_unused]] HierLoads rld;
+    if constexpr (ROOT) {  // the round's loads, ahead of the item's own
+      rln = hier_lane_one(rnd.ha, rnd.ha.leaf_lo + wi.seg);
+      rld = hier_round_load(rnd.p, rnd.ha, rln);
+    }
     const int hw = wi.n >> 16;
     bool done = false;
     if (hw == 0) {
@@ -135,6 +160,7 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
       const bool dirty = CYCLE && to_rest && hw != 0 && (fk.cbits != 0 || fk.kind != 0);
       if (fk.valid || dirty) keys[i] = FixKey{0, 0, 0};
     }
+    if constexpr (ROOT) hier_round_decide<true>(rnd.p, rnd.ha, rln, rld);
   }
 
   // ---- step 2: compact the listed items into LDS (a ballot per wave, one LDS step across) ----
@@ -187,8 +213,14 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
 
 // The launch is the part's last kernel of the tick: it completes `done` (hipExtLaunchKernel's
 // stop event) as the rest launch does in the other forms.
-hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedArgs& a, hipEvent_t done,
-                            hipStream_t st) {
+//
+// The ROOT builds are a unit, and so a code object, of their own (dm_tick_fused_root.hip, which
+// includes this file with DM_FUSED_ROOT_UNIT set and defines launch_bin_fused_root): the
+// kernels of this unit are then what they are without them (twice the callers of group_segment
+// in one unit changed the compiler's inlining, and with it the registers of the builds here).
+template <bool ROOT>
+static hipError_t launch_fused_build(const BinItems& w, const DevParams& p, const FusedArgs& a,
+                                     const RoundArg<ROOT>& round, hipEvent_t done, hipStream_t st) {
   const int n = w.n;
   if (n <= 0) return hipSuccess;
   const bool cycle = p.out_gets != p.has;
@@ -197,12 +229,29 @@ hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedAr
     constexpr int G = decltype(g)::value, R = decltype(r)::value;
     const dim3 grid((unsigned)((n + kFusedChunk<G> - 1) / kFusedChunk<G>));
     with_bool(cycle, [&](auto cy) {
-      hipExtLaunchKernelGGL((k_block_fused<G, R, decltype(cy)::value>), grid, dim3(G), 0, st, nullptr, done, 0, p,
+      hipExtLaunchKernelGGL((k_block_fused<G, R, decltype(cy)::value, ROOT>), grid, dim3(G), 0, st, nullptr, done, 0, p,
                             w.items, n, a.keys, a.aux, a.fcnt, a.par, a.fresh ? 1 : 0, a.host_count, a.epoch,
-                            a.host_rest, a.glist, a.gcount);
+                            a.host_rest, a.glist, a.gcount, round);
     });
   });
   return known ? hipGetLastError() : hipErrorInvalidValue;
 }
+
+#ifndef DM_FUSED_ROOT_UNIT
+hipError_t launch_bin_fused(const BinItems& w, const DevParams& p, const FusedArgs& a, const RootRound* round,
+                            hipEvent_t done, hipStream_t st) {
+  if (round) return launch_bin_fused_root(w, p, a, *round, done, st);
+  return launch_fused_build<false>(w, p, a, NoRound{}, done, st);
+}
+#else
+hipError_t launch_bin_fused_root(const BinItems& w, const DevParams& p, const FusedArgs& a, const RootRound& round,
+                                 hipEvent_t done, hipStream_t st) {
+  // a carried round: one server, one root row per resource, and an item for every resource
+  const HierArgs& ha = round.ha;
+  if (ha.K != 1 || ha.G != 1 || ha.server != 0 || ha.r_hi - ha.r_lo != w.n || ha.r_lo != ha.leaf_lo)
+    return hipErrorInvalidValue;
+  return launch_fused_build<true>(w, p, a, round, done, st);
+}
+#endif
 
 }  // namespace dm

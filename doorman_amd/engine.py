@@ -20,7 +20,7 @@ _BIN_NAMES = ("small_tiles", "sub16x4", "sub32x4", "wave64x4", "block128x4", "bl
               "redo_resident_cap", "spec_fits", "aux_own_queues", "stream_parts", "queue_perm", "wb_inplace",
               "steady_parts", "fixed_parts", "sweep_parts", "kept_refreshes", "cycle_parts", "masked_parts")
 # dm_plan_info's slots beyond the bins' table, in order
-_PLAN_NAMES = _BIN_NAMES + ("fused_parts", "told_listed", "told_queued")
+_PLAN_NAMES = _BIN_NAMES + ("fused_parts", "told_listed", "told_queued", "rounds_in_tick")
 
 
 def _ptr(a):

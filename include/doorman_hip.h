@@ -66,7 +66,9 @@ extern "C" {
    the parts whose last tick ran a masked build, and the call returns 26;
    dm_store_stats has a fifth value, the resources whose key is valid in a part whose keys
    are in use, and returns 5 (a caller that passes max = 4 gets the four it got);
-   dm_plan_info's slot 26, the parts whose last tick ran fused (one launch).  (Added
+   dm_plan_info's slot 26, the parts whose last tick ran fused (one launch); slot 29, the
+   root rounds dm_hier_step ran inside a leaf launch (the carried round: after dm_hier_step
+   the round is on the stream only after the next call on either context).  (Added
    slots, as slot 18 was: the version stays 7, which the clean and re-layout additions
    pinned.)
    6 (round 6): dm_store_apply_async / dm_store_apply_wait (a round's store batch enqueued
@@ -546,7 +548,20 @@ int dm_hier_status(dm_ctx* root, uint32_t* status, int n_servers);
  * unused with one server), the exchange stream (NULL: the leaf's), the server index; it
  * needs dm_hier_layout on the root and turns dm_hier_pipeline on for the leaf.  The
  * per-step host work is then a handful of stream operations: a step of a small shard
- * stays device-bound instead of host-bound. */
+ * stays device-bound instead of host-bound.
+ * The carried round: with one server, the exchange on the leaf's stream and the template
+ * pipe on, dm_hier_step does not launch the root's round; it keeps it and runs it inside the
+ * next dm_hier_step's leaf launch when that tick is one fused launch over every resource of
+ * the leaf (dm_plan_info slot 29 counts those), else ahead of that tick's launches.  Every
+ * result is bit for bit what the launch of its own gave.  After dm_hier_step the round's
+ * writes (the root's rows and sums, the status of dm_hier_status, the staged templates) are
+ * therefore ordered on the stream only after the next library call on either context: every
+ * exported call that takes the leaf or the root first launches a carried round on its
+ * stream (dm_sync, dm_join, dm_stream_wait, the reads, dm_hier_status, dm_hier_pipeline,
+ * dm_config_load, the store updates, a plain dm_apportion, dm_set_stream, dm_set_profiling,
+ * dm_destroy of either context among them).  A foreign stream that reads what the round
+ * writes orders itself with dm_stream_wait, as it did.  DM_CARRY_ROUND=0 in the environment,
+ * read when the context is created, launches every round behind its tick as before. */
 int dm_hier_attach(dm_ctx* leaf, dm_ctx* root, int server, void* const* ring, int nring, void* gathered,
                    void* exchange_stream);
 int dm_hier_step(dm_ctx* leaf, dm_ctx* root, int64_t now_ns);
@@ -647,7 +662,9 @@ int dm_reset_kernel_times(dm_ctx* ctx);
  * device tells of few listed items; DM_FUSED=0 in the environment, read when the context is
  * created, keeps the launches as they were), and (slots 27, 28) the listed items and the rest
  * items the device last told the host of, summed over the workgroup-bin parts (hints that size
- * and choose the next launches; for tests and tools), with which the call returns 29: a caller
+ * and choose the next launches; for tests and tools), and (slot 29) the root rounds that ran
+ * inside a leaf launch since the store was loaded (dm_hier_step's carried round, counted on
+ * the leaf and on the root alike), with which the call returns 30: a caller
  * that passes max = 26 gets the slots it got while the call returns 26 */
 int dm_plan_info(dm_ctx* ctx, int64_t* out, int max);
 /* row-state summary of the device store (synchronous): dense resources (every row a
