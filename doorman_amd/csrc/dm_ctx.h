@@ -240,7 +240,7 @@ struct SplitSlot {
   // alternate column by itself (dm_split_form.h CycleAuto).
   uint64_t cyc_live = 0;
   CycleAuto cyc;
-  // The sweep (k_fixed_sweep) lists the items whose key does not hold in sw_list, one
+  // The sweep (k_sweep) lists the items whose key does not hold in sw_list, one
   // entry per item at most.  sw_cnt: the list's two-slot count ring and the last {count,
   // epoch} told the host; lpar: the ring slot of the next sweep; sweep (host-mapped):
   // {count, row epoch}, which sizes the next grids.  Allocated by the first tick that sweeps.
@@ -677,7 +677,7 @@ struct dm_ctx {
     for (int j = 0; j < kParts; ++j) slot(b, j).fix_live = slot(b, j).cyc_live = 0;
     return e;
   }
-  // DM_SWEEP=0: a FIXED launch with keys in use stays k_block_dense_fixed over every item.
+  // DM_SWEEP=0: a FIXED launch with keys in use stays k_block_dense's kFixed build over every item.
   int sweep_ok = 1;
   int bin_parts[kNumBins] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
   // off for a leaf whose ticks an exchange on another stream waits for (dm_hier_attach):

@@ -103,7 +103,7 @@ struct FixKey {
 };
 static_assert(sizeof(FixKey) == 16, "one 16-B scalar load per item");
 
-// The cycle form (k_cycle_sweep, k_block_cycle_list: a steady writeback tick on the
+// The cycle form (the cycle builds of k_sweep and k_block_list: a steady writeback tick on the
 // alternate column) keeps the same key with three states in `valid`, and a second half in
 // an array of its own parallel to the keys, so that every kernel that reads or clears a
 // FixKey (the in-place FIXED builds, the key-clearing update kernels) is the code it was:
@@ -136,7 +136,7 @@ struct CycAux {
 static_assert(sizeof(CycAux) == 16, "one 16-B scalar load per item");
 constexpr int kCycleProbeWaitMax = 64;
 
-// One entry of a part's sweep worklist (k_fixed_sweep -> k_block_dense_list,
+// One entry of a part's sweep worklist (k_sweep -> k_block_list,
 // dm_tick_group.hip): the work item's own fields and its index in the bin (its item and
 // its key), so that the entry is the row kernel's only load before the rows.
 struct SweepEntry {

@@ -35,11 +35,25 @@ struct SweepArgs {
 };
 hipError_t launch_bin(const BinItems& w, const DevParams& p, int32_t* glist, int32_t* gcount, hipStream_t st);
 hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, int32_t* gcount, hipStream_t st);
+// The split form's dense side.  masked: the form's masked builds (PartForm::masked, which
+// implies steady; dm_tick_masked.hip holds them).
+// done (optional): an event the launch itself completes (hipExtLaunchKernel's stop event: no
+// marker packet of its own on the queue), for another stream to wait on.  steady: the builds
+// that take Clean's result as known and queue every item it is not known for (group_segment
+// kSteady); the caller launches the rest kernel after them.  keys (optional; only with steady,
+// on a writeback tick in place): the kFixed build, over the keys of these items; use_keys:
+// valid keys may be trusted (else every key is rewritten).
 hipError_t launch_bin_dense(const BinItems& w, const DevParams& p, const SplitArgs& a, hipEvent_t done, bool steady,
-                            FixKey* keys, bool use_keys, hipStream_t st);
-hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+                            bool masked, FixKey* keys, bool use_keys, hipStream_t st);
+// A kFixed launch with keys in use (a writeback tick in place), as the sweep and the row
+// kernel over its worklist (k_sweep, k_block_list): the rest launch follows as after
+// launch_bin_dense's steady builds.
+hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw, bool masked,
                             hipStream_t st);
-hipError_t launch_bin_cycle(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+// The cycle form: a steady writeback tick on the alternate column, through the same two
+// kernels' cycle builds.  The first such launch of a part (use_keys false) lists and rewrites
+// every item; the rest launch follows either.
+hipError_t launch_bin_cycle(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw, bool masked,
                             CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st);
 hipError_t launch_count_keys(const FixKey* keys, int n, int32_t* out, hipStream_t st);
 hipError_t launch_count_cycle(const FixKey* keys, const CycAux* aux, const WorkItem* items, const ResAgg* agg, int n,
@@ -48,14 +62,6 @@ hipError_t launch_count_undense(const WorkItem* items, int n, unsigned long long
                                 hipStream_t st);
 hipError_t launch_bin_rest(const BinItems& w, const DevParams& p, const SplitArgs& a, int32_t* host_count,
                            int rest_grid, hipEvent_t done, hipStream_t st);
-// dm_tick_masked.hip: the steady forms of the three launchers above with the kernels' *_masked
-// siblings (PartForm::masked)
-hipError_t launch_bin_dense_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, hipEvent_t done,
-                                   FixKey* keys, bool use_keys, hipStream_t st);
-hipError_t launch_bin_sweep_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
-                                   hipStream_t st);
-hipError_t launch_bin_cycle_masked(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
-                                   CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st);
 // dm_tick_fused.hip: the sweep or the cycle form (by the tick's output column) with keys in
 // use, the row kernel and the rest kernel as one launch (PartForm::fused); `done` as
 // launch_bin_rest's

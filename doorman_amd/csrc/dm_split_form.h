@@ -12,10 +12,10 @@
 //   steady          k_block_dense's steady builds, then the rest launch
 //   FIXED           the steady build of a writeback tick in place, rewriting every key ...
 //   FIXED with keys ... or trusting them (use_keys) ...
-//   the sweep       ... as k_fixed_sweep and k_block_dense_list over its worklist
+//   the sweep       ... as k_sweep and k_block_list over its worklist
 //   the cycle form  FIXED's twin for a steady writeback tick on the alternate column:
-//                   k_cycle_sweep and k_block_cycle_list (dm_device.h CycAux)
-//   masked          any of the steady forms above, launched as the kernels' *_masked siblings
+//                   the cycle builds of k_sweep and k_block_list (dm_device.h CycAux)
+//   masked          any of the steady forms above, launched as the kernels' kMasked builds
 //                   (dm_keep_keys' DM_KEEP_FREE_SLOTS: items that hold released rows are items
 //                   of the form like any other)
 //   fused           the sweep or the cycle form with keys in use, as one launch: k_block_fused
@@ -35,11 +35,11 @@ struct PartForm {
   bool use_keys = false;   // ... trusting the items' valid keys
   bool sweep = false;      // ... as the sweep and the row kernel over its worklist
   int rest_grid = 0;       // k_block_rest's workgroups
-  int list_grid = 0;       // k_block_dense_list's workgroups
+  int list_grid = 0;       // k_block_list's workgroups
   // The part's fix_live after this tick: the row epoch when the FIXED build is launched,
   // else 0 (the mixed kernel included).  This one assignment is the key rule: a key is
   // trusted only while nothing but FIXED launches touched the part in this row epoch.
-  // Fixed points (dm_device.h FixKey, dm_tick_group.h group_segment FIXED): a part that
+  // Fixed points (dm_device.h FixKey, dm_tick_group.h group_segment kFixed): a part that
   // runs a steady build on a writeback tick in place runs the FIXED build, which keeps a
   // key per item and loads no row of an item whose valid key matches its capacity and
   // kind.  A valid key says that nothing but FIXED builds has touched the item's rows,
@@ -60,7 +60,7 @@ struct PartForm {
   // a cycle-form launch fix_live: neither trusts the other's keys.
   bool cycle = false;
   uint64_t cyc_live = 0;
-  // The steady form's launches are the masked builds (group_segment MASKED).  The choice never
+  // The steady form's launches are the masked builds (group_segment kMasked).  The choice never
   // affects results: a non-masked launch hands a masked item to the rest kernel, a masked
   // launch handles a non-masked item identically, and both maintain keys by the same rules,
   // so fix_live and cyc_live need no new discipline.
@@ -236,7 +236,7 @@ inline PartForm choose_form(const FormInputs& in, bool tried) {
 // keeps it in place) gets no stamp and so no judgement: after kCycleIdle such ticks in a row
 // it gives the ask up as a failed try does, so that it does not keep every other part off
 // in-place FIXED until the next row epoch.
-// The told word's high half: a part back in place tells through k_block_dense_list, which
+// The told word's high half: a part back in place tells through k_block_list's in-place build, which
 // writes no stamp and tells only a changed count, so the last cycle-form stamp may stay there
 // under an in-place count.  It is harmless: only an engaged part reads it, against a seq0
 // taken at or after that stamp, and kCycleSettle launches later at the earliest.

@@ -503,14 +503,10 @@ int Tick::launch_dense_form(Part& pt, const PartForm& f) {
                               (unsigned long long)c->row_epoch, f.list_grid};
            const unsigned stamp = sl.cyc.on ? sl.cyc.seq : 0u;
            const bool tell = sl.cyc.on && !sl.cyc.judged;
-           if (f.masked) {  // the same forms in the masked builds (dm_tick_masked.hip); masked implies steady
-             if (f.cycle) return launch_bin_cycle_masked(pt.w, pt.p, a, sw, sl.aux(), f.use_keys, stamp, tell, pt.s);
-             if (f.sweep) return launch_bin_sweep_masked(pt.w, pt.p, a, sw, pt.s);
-             return launch_bin_dense_masked(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, keys, f.use_keys, pt.s);
-           }
-           if (f.cycle) return launch_bin_cycle(pt.w, pt.p, a, sw, sl.aux(), f.use_keys, stamp, tell, pt.s);
-           if (f.sweep) return launch_bin_sweep(pt.w, pt.p, a, sw, pt.s);
-           return launch_bin_dense(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, f.steady, keys, f.use_keys, pt.s);
+           if (f.cycle) return launch_bin_cycle(pt.w, pt.p, a, sw, f.masked, sl.aux(), f.use_keys, stamp, tell, pt.s);
+           if (f.sweep) return launch_bin_sweep(pt.w, pt.p, a, sw, f.masked, pt.s);
+           return launch_bin_dense(pt.w, pt.p, a, f.skip_rest ? pt.done : nullptr, f.steady, f.masked, keys, f.use_keys,
+                                   pt.s);
          }),
          "group kernel (dense split)");
   if (f.sweep || f.cycle) sl.lpar ^= 1;

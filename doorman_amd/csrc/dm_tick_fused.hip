@@ -3,8 +3,8 @@
 // a code object, of its own, as dm_tick_masked.hip is: dm_tick_group.hip's device code is what
 // it is without it.
 //
-// A part at its fixed point (or in a proven two-tick cycle) launches k_fixed_sweep (or
-// k_cycle_sweep), then a row kernel over an empty list and a rest kernel over an empty queue:
+// A part at its fixed point (or in a proven two-tick cycle) launches k_sweep (in its cycle
+// build), then a row kernel over an empty list and a rest kernel over an empty queue:
 // two launches that read one count each, because only the device knows the lists are empty
 // (lease lengths, templates and learning ends change there).  Each costs the host and the
 // stream a launch (profiles/cycle_ab.md: 16.1 us a step against 12.7 us of enqueue).
@@ -19,7 +19,7 @@
 namespace dm {
 
 // Items per workgroup, one per lane of the sweep step: G by default (C3: 782 workgroups of two
-// waves, as many waves as k_cycle_sweep's 98 x 16).  DM_FUSED_CHUNK builds a variant with fewer
+// waves, as many waves as k_sweep's 98 x 16).  DM_FUSED_CHUNK builds a variant with fewer
 // (profiles/fused_ab.md).
 #ifndef DM_FUSED_CHUNK
 #define DM_FUSED_CHUNK 0
@@ -45,7 +45,7 @@ static_assert(sizeof(FusedEntry) == 40, "ten dwords");
 // the listed count and row epoch last told the host; [7]: never read (the count word of a
 // hand-off that cannot happen).  This tick adds into slot par; workgroup 0 reads slot par ^ 1,
 // the previous fused tick's total, complete by stream order, tells the host when it differs
-// from what was last told (SplitSlot::sweep as k_block_dense_list tells it, without a stamp)
+// from what was last told (SplitSlot::sweep as k_block_list tells it, tell_count, without a stamp)
 // and zeroes the slot.  fresh: the part's previous tick was not fused, so the slot holds an
 // older tick's total, which is dropped, and the next fused tick tells whatever this one counts.
 // host_rest (host-mapped, SplitSlot::fused_queued): the rest items, a two-slot ring as well, but
@@ -85,17 +85,10 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
       rnd.ha.status_out[0] = pub_flags(rnd.ha.gathered[0].x);
     int32_t* prev = fcnt + 2 * (par ^ 1);
     const int listed = prev[0], rest = prev[1];
-    if (fresh) {
+    if (fresh)
       fcnt[4] = -1;
-    } else {
-      if (fcnt[4] != listed || fcnt[5] != (int32_t)epoch) {
-        __hip_atomic_store(host_count, (unsigned long long)(unsigned)listed, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        fcnt[4] = listed;
-        fcnt[5] = (int32_t)epoch;
-      }
-    }
+    else
+      tell_count(true, fcnt + 4, listed, host_count, epoch, 0u, false);
     if (listed) prev[0] = 0;
     if (rest) {  // (a store to host memory keeps an otherwise empty launch alive ~2 us longer: only when needed)
       prev[1] = 0;
@@ -103,11 +96,11 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
     }
   }
 
-  // ---- step 1: classify (k_fixed_sweep's / k_cycle_sweep's lane, and group_segment's `rest`
-  // test for the items the sweeps leave to the row kernel) ----
+  // ---- step 1: classify (the sweep's lane, sweep_lane, with the `rest` test made for the items
+  // the sweep leaves to the row kernel as well) ----
   const int i = (int)(blockIdx.x * (unsigned)C + threadIdx.x);
-  bool app = false, to_rest = false;
-  int probe = 0, carry = 0;
+  bool app = false;
+  LaneClass lc{false, false, 0, 0};
   WorkItem wi{0, 0, 0};
   [[maybe_unused]] CycAux ax{0, 0, 0};
   if ((int)threadIdx.x < C && i < nitems) {
@@ -121,50 +114,20 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
       rld = hier_round_load(rnd.p, rnd.ha, rln);
     }
     const int hw = wi.n >> 16;
-    bool done = false;
-    if (hw == 0) {
-      to_rest = true;
-    } else {
-      const Res rs = load_res(p, wi.seg);
-      const int hint = hw & 0xFF;
-      const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
-      if (rest) {
-        to_rest = true;
-      } else if (fk.valid != 0 && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind &&
-                 !rs.learning) {
-        if constexpr (CYCLE) {
-          if (fk.valid == 2) {
-            write_resource(p, wi.seg, rs,
-                           Clean{rs.agg_count, __longlong_as_double((long long)ax.prev_has), rs.agg_wants}, 0.0, hint);
-            const uint64_t was = (uint64_t)__double_as_longlong(rs.agg_has);
-            if (ax.prev_has != was) aux[i].prev_has = was;
-            done = true;
-          } else if (ax.skip > 0) {
-            ax.skip -= 1;
-            aux[i].skip = ax.skip;
-            carry = 1;
-          } else {
-            probe = carry = 1;
-          }
-        } else {
-          write_fixed(p, wi.seg, rs, hint);
-          done = true;
-        }
-      }
-    }
-    if (!done) {
+    lc = sweep_lane<CYCLE, false, true>(p, wi, fk, fk.valid, CYCLE ? aux + i : nullptr, ax);
+    if (!lc.done) {
       app = true;
       // the key in memory as the two-kernel form leaves it before the item's rows are read:
       // the sweep clears a valid key, and the cycle form's row kernel (which does not use the
       // keys) overwrites whatever the array holds when it hands an item with a hint word off
-      const bool dirty = CYCLE && to_rest && hw != 0 && (fk.cbits != 0 || fk.kind != 0);
+      const bool dirty = CYCLE && lc.to_rest && hw != 0 && (fk.cbits != 0 || fk.kind != 0);
       if (fk.valid || dirty) keys[i] = FixKey{0, 0, 0};
     }
     if constexpr (ROOT) hier_round_decide<true>(rnd.p, rnd.ha, rln, rld);
   }
 
   // ---- step 2: compact the listed items into LDS (a ballot per wave, one LDS step across) ----
-  const uint64_t bal = __ballot(app), balr = __ballot(to_rest);
+  const uint64_t bal = __ballot(app), balr = __ballot(lc.to_rest);
   const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
   if (lane == 0) wtot[wave] = __popcll(bal) | __popcll(balr) << 16;
   __syncthreads();
@@ -186,26 +149,25 @@ __global__ __launch_bounds__(G) void k_block_fused(DevParams p, WorkItem* __rest
   }
   if (app)
     ent[base + __popcll(bal & ((1ull << lane) - 1ull))] =
-        FusedEntry{wi.seg, wi.n, wi.lo, i, (to_rest ? 1 : 0) | probe << 1 | carry << 2, ax.wait, ax.skip, ax.prev_has};
+        FusedEntry{wi.seg, wi.n, wi.lo, i, (lc.to_rest ? 1 : 0) | lc.probe << 1 | lc.carry << 2, ax.wait, ax.skip, ax.prev_has};
   __syncthreads();
 
   // ---- step 3: the whole workgroup decides them, one after another ----
   for (int q = 0; q < tot; ++q) {
     const FusedEntry e = uniform(ent[q]);
     const WorkItem it{e.seg, e.n, e.lo};
-    int t = (int)threadIdx.x;  // (anew for every item: k_block_dense_list)
+    int t = (int)threadIdx.x;  // (anew for every item: k_block_list)
     asm volatile("" : "+v"(t));
     if (e.flags & 1) {
       group_segment<G, R, kRest>(p, it, items + e.idx, t, lds, general_list, general_count);
     } else if constexpr (CYCLE) {
       // (its own `rest` test is false: no hand-off; the queue arguments are never used)
-      group_segment<G, R, kDenseOnly, true, true, true, true, true>(
+      group_segment<G, R, kDenseOnly, kCycle>(
           p, it, items + e.idx, t, lds, general_list, general_count, fcnt, fcnt + 7, e.idx, nullptr, 0, keys + e.idx,
           FixKey{0, 0, 0}, 0, aux + e.idx, CycAux{e.prev_has, e.wait, e.skip}, e.flags >> 1 & 1, e.flags >> 2 & 1);
     } else {
-      group_segment<G, R, kDenseOnly, true, true, true, true>(p, it, items + e.idx, t, lds, general_list,
-                                                              general_count, fcnt, fcnt + 7, e.idx, nullptr, 0,
-                                                              keys + e.idx, FixKey{0, 0, 0}, 1);
+      group_segment<G, R, kDenseOnly, kFixed | kList>(p, it, items + e.idx, t, lds, general_list, general_count, fcnt,
+                                                      fcnt + 7, e.idx, nullptr, 0, keys + e.idx, FixKey{0, 0, 0}, 1);
     }
     __syncthreads();  // the next item reuses the single-use LDS slots
   }

@@ -1,9 +1,9 @@
 // dm_tick_group.h — what the units of the resource-per-group kernels share: group_segment (the
 // body of every workgroup-bin and sub-wave kernel) with the device functions it uses, and the
-// host-side list of the workgroup bins' shapes.  dm_tick_group.hip holds the kernels and their
-// launchers; dm_tick_masked.hip holds the masked builds (dm_keep_keys' DM_KEEP_FREE_SLOTS) in a
-// unit, and so a code object, of their own: dm_tick_group.hip's device code, the placement of
-// its kernels included, does not depend on them.
+// host-side list of the workgroup bins' shapes.  dm_tick_steady.h states the split form's
+// dense-side kernels over it; dm_tick_group.hip holds the other kernels and the launchers;
+// dm_tick_masked.hip instantiates the masked builds (dm_keep_keys' DM_KEEP_FREE_SLOTS) in a unit,
+// and so a code object, of their own: dm_tick_group.hip's device code does not depend on them.
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -59,20 +59,116 @@ __device__ __forceinline__ void put_key(FixKey* key, const FixKey& fk, int use_k
   if (!use_keys || nk.cbits != fk.cbits || nk.kind != fk.kind || nk.valid != fk.valid) *key = nk;
 }
 
-// What group_segment<.., FIXED> and the sweep's lanes (k_fixed_sweep) do with an item whose
-// key holds: the record as the full path would write it (follow_exp moves, the exchange's
-// block is published, the state byte stays), the sums it read and a delta of +0.0.
-// (The two tests before it -- the steady `rest` test and the key against the record -- stay
-// written out in both places: as functions they change the kernels' code, the compiler
-// ordering the tests' terms differently behind a call.  k_fixed_sweep's copy must stay
-// equal to group_segment's.)
+// The builds of group_segment, a set of flags: group_segment<G, R, kDenseOnly, kFixed | kList>.
+// A flag's value includes the flags it implies (has_build asks for all of its bits).  Kernels
+// that differ only in their build are one template over these flags (dm_tick_steady.h); what
+// guards each build's code is tools/isa_diff.py, against the parent's, kernel for kernel.
+//   kSkip    unchanged runs of gets are not stored (a writeback tick in place)
+//   kSteady  Clean's result is known; an item it is not known for goes to the rest queue
+//   kFixed   the steady, skipping build that keeps a fixed-point key per item (FixKey)
+//   kList    the caller is a loop over a worklist (k_block_list, k_block_fused)
+//   kCycle   the fixed-point list build on the alternate column (CycAux)
+//   kMasked  a steady build that also takes items with released rows (DM_KEEP_FREE_SLOTS)
+using Build = unsigned;
+constexpr Build kSkip = 1u, kSteady = 2u, kFixed = 4u | kSkip | kSteady, kList = 8u, kCycle = 16u | kFixed | kList,
+                kMasked = 32u | kSteady;
+constexpr bool has_build(Build b, Build f) { return (b & f) == f; }
+
+// The steady `rest` test: an item a steady build does not decide (k_block_rest does).  A stale
+// hint, a released-row or arrival bit, lapsed followers, recompute mode.  MASKED: the
+// released-row bit alone does not send the item there, but an item with no live row does
+// (under these conditions the running count is exact and every live row counts at least 1):
+// the plain path's empty-range arithmetic stays in one place.  (group_segment keeps the one
+// written-out copy of this test, which must equal this function: called there, the unmasked
+// steady builds' code moves.  key_holds is called there too.)
+template <bool MASKED>
+__device__ __forceinline__ bool steady_rest(const DevParams& p, const Res& rs, int hw, int hint) {
+  return dense_subclients(rs) != hint || (hw >> 8 & (MASKED ? 2 : 3)) != 0 || p.now > rs.follow_exp || p.recompute ||
+         (MASKED && rs.agg_count == 0);
+}
+// The key against the record: its tick computed with this capacity and kind, outside learning.
+__device__ __forceinline__ bool key_holds(const FixKey& fk, const Res& rs) {
+  return fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning;
+}
+
+// What a fixed-point build and the sweep's lanes do with an item whose key holds: the record
+// as the full path would write it (follow_exp moves, the exchange's block is published, the
+// state byte stays), the sums it read and a delta of +0.0.
 __device__ __forceinline__ void write_fixed(const DevParams& p, int seg, const Res& rs, int hint) {
   write_resource(p, seg, rs, Clean{rs.agg_count, rs.agg_has, rs.agg_wants}, 0.0, hint);
+}
+// The cycle form's step for an item whose key holds (CycAux; axp: the item's entry in memory,
+// ax: its copy).  State 2: the item reproduces its state of two ticks ago, which its destination
+// column still holds -- write_fixed's record with sum_has := prev_has, and prev_has becomes the
+// sum just read, a store only where they differ; true: done.  State 1: the back-off goes on
+// (carry), or has run out and the row kernel probes.
+__device__ __forceinline__ bool cycle_step(const DevParams& p, int seg, const Res& rs, int hint, int state, CycAux* axp,
+                                           CycAux& ax, int& probe, int& carry) {
+  if (state == 2) {
+    write_resource(p, seg, rs, Clean{rs.agg_count, __longlong_as_double((long long)ax.prev_has), rs.agg_wants}, 0.0,
+                   hint);
+    const uint64_t was = (uint64_t)__double_as_longlong(rs.agg_has);
+    if (ax.prev_has != was) axp->prev_has = was;
+    return true;
+  }
+  if (ax.skip > 0) {
+    ax.skip -= 1;
+    axp->skip = ax.skip;
+    carry = 1;
+  } else {
+    probe = carry = 1;
+  }
+  return false;
+}
+
+// One lane's item in a sweep (k_sweep, step 1 of k_block_fused): the tests a kFixed build makes
+// before its rows -- a zero hint word, the `rest` test, the key against the record -- and, where
+// all pass, the item's whole tick.  state: the key's, as the launch trusts it (0: not at all).
+// done: nothing is left to do; else the item is listed, for k_block_rest's body if to_rest.
+// SPLIT (k_block_fused, which runs both bodies) classifies an item without a trusted key too;
+// else it is listed with no record loaded, and the row kernel's own test hands it on.
+struct LaneClass { bool done, to_rest; int probe, carry; };
+template <bool CYCLE, bool MASKED, bool SPLIT>
+__device__ __forceinline__ LaneClass sweep_lane(const DevParams& p, const WorkItem& wi, const FixKey& fk, int state,
+                                                CycAux* axp, CycAux& ax) {
+  LaneClass c{false, false, 0, 0};
+  const int hw = wi.n >> 16;
+  if (hw == 0) {
+    c.to_rest = true;
+  } else if (SPLIT || state != 0) {
+    const Res rs = load_res(p, wi.seg);
+    const int hint = hw & 0xFF;
+    if (steady_rest<MASKED>(p, rs, hw, hint)) {
+      c.to_rest = true;
+    } else if (state != 0 && key_holds(fk, rs)) {
+      if constexpr (CYCLE) {
+        c.done = cycle_step(p, wi.seg, rs, hint, state, axp, ax, c.probe, c.carry);
+      } else {
+        write_fixed(p, wi.seg, rs, hint);
+        c.done = true;
+      }
+    }
+  }
+  return c;
+}
+
+// One thread (`one`) tells the host a worklist's {count, row epoch} (host-mapped: the next
+// launches' grid size, a hint) when either differs from the last told (told[0], told[1]), or
+// `always`.  The count's high half: the host's stamp of the launch (the cycle form; else 0).
+__device__ __forceinline__ void tell_count(bool one, int32_t* told, int count, unsigned long long* host_count,
+                                           unsigned long long epoch, unsigned stamp, bool always) {
+  if (one && (always || told[0] != count || told[1] != (int32_t)epoch)) {
+    __hip_atomic_store(host_count, (unsigned long long)(unsigned)count | (unsigned long long)stamp << 32,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    told[0] = count;
+    told[1] = (int32_t)epoch;
+  }
 }
 // One thread hands item qidx to the rest queue: its key cleared first (KEY), at most one
 // entry per item and tick (a guarded tick's count may grow past qcap), and the guard set
 // where the launch has one.  (The count's slot is qcnt + par, added here and not by the
-// caller: ahead of the key's store the addition moves k_block_dense_fixed's code.)
+// caller: ahead of the key's store the addition moves the kFixed build's code.)
 template <bool KEY>
 __device__ __forceinline__ void hand_off(FixKey* key, const FixKey& fk, int use_keys, int32_t* queue, int32_t* qcnt,
                                          int par, int32_t qidx, int qcap, int32_t* guard) {
@@ -82,16 +178,16 @@ __device__ __forceinline__ void hand_off(FixKey* key, const FixKey& fk, int use_
   if (guard) __hip_atomic_store(guard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// LIST: the caller is a loop over items (k_block_dense_list).  Behind an earlier item's
+// kList: the caller is a loop over items (k_block_list).  Behind an earlier item's
 // stores the compiler loads the record with vector loads, a register per dword and lane
 // through every pass (128 x 8: 88 VGPRs against 65); the record is moved back to SGPRs.
-// CYCLE (k_block_cycle_list alone): the FIXED list build on the alternate column, p.out_gets
-// != p.has (dm_device.h CycAux has the key's states and the proof).  probe: the item's key is
+// kCycle (k_block_list's and k_block_fused's cycle builds): kFixed | kList on the alternate
+// column, p.out_gets != p.has (dm_device.h CycAux has the key's states and the proof).  probe: the item's key is
 // in state 1 under this capacity and kind (the sweep saw to it, SweepEntry::pad: no dependent
 // load): the destination rows are loaded with the others and the SKIP ballot compares against
 // them -- skipping an equal run is always correct, only the key's conclusion rests on what
 // the destination held.  Without it every run is stored.  carry: the back-off goes on.
-// MASKED (the *_masked kernels alone, launched for a part under DM_KEEP_FREE_SLOTS:
+// kMasked (dm_tick_masked.hip's builds, launched for a part under DM_KEEP_FREE_SLOTS:
 // dm_split_form.h): a steady build that also takes an item whose hint word carries the
 // released-row bit, with no arrival bit and at least one live row.  With no arrival, lapse or
 // recompute Clean releases nothing there either: the masked rows hold zeros, the live rows are
@@ -99,8 +195,7 @@ __device__ __forceinline__ void hand_off(FixKey* key, const FixKey& fk, int use_
 // the steady argument with one more register.  A masked row takes the map's not-live path: a
 // gets of +0.0 against the +0.0 it holds, and put_released with kSubReleased, which stores
 // nothing more in a writeback tick.
-template <int G, int R, int MODE = kMixed, bool SKIP = false, bool STEADY = false, bool FIXED = false,
-          bool LIST = false, bool CYCLE = false, bool MASKED = false>
+template <int G, int R, int MODE = kMixed, Build BUILD = 0u>
 __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem wi, WorkItem* item, int t,
                                               Lds<G>& lds, int32_t* general_list, int32_t* general_count,
                                               int32_t* queue = nullptr, int32_t* qcount = nullptr,
@@ -112,10 +207,12 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   // only the 128-thread mixed kernel and the dense-only kernels load by the hint
   constexpr bool kDense = G >= 128 || (G == 64 && R >= 16);  // (64 x 16: kBin4Wave)
   constexpr bool kHintLoad = (G == 128 && MODE == kMixed) || MODE == kDenseOnly;
-  static_assert(!STEADY || MODE == kDenseOnly, "the steady build is a dense-only build");
-  static_assert(!FIXED || (SKIP && STEADY), "the fixed-point build is a steady build that skips unchanged stores");
-  static_assert(!CYCLE || (FIXED && LIST), "the cycle build is a list build of the fixed-point build");
-  static_assert(!MASKED || STEADY, "the masked build is a steady build");
+  constexpr bool SKIP = has_build(BUILD, kSkip), STEADY = has_build(BUILD, kSteady), FIXED = has_build(BUILD, kFixed),
+                 LIST = has_build(BUILD, kList), CYCLE = has_build(BUILD, kCycle), MASKED = has_build(BUILD, kMasked);
+  static_assert(!STEADY || MODE == kDenseOnly, "kSteady: a dense-only build");
+  static_assert(!FIXED || (SKIP && STEADY), "kFixed: a steady build that skips unchanged stores");
+  static_assert(!CYCLE || (FIXED && LIST), "kCycle: a list build of the fixed-point build");
+  static_assert(!MASKED || STEADY, "kMasked: a steady build");
   const int seg = wi.seg;
   const int64_t lo = wi.lo;
   const int n = kDense ? wi.n & 0xFFFF : wi.n;
@@ -158,7 +255,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
   constexpr unsigned kRowBits = R >= 32 ? ~0u : (1u << R) - 1u;
   const bool arrivals = !STEADY && kDense && ((hw >> 9) & 1);
   bool by_hint = MODE == kDenseOnly;  // the rows' states come from the hint and the masks, not the column
-  // FIXED (k_block_dense's build for a steady part ticking in place, dm_tick.cpp): an item
+  // kFixed (k_block_dense's build for a steady part ticking in place, dm_tick.cpp): an item
   // whose key is valid, in a launch that uses the keys, issues no row load before its
   // record has confirmed or refuted the key (below); every other item loads first, as ever.
   const bool keyed = FIXED && use_keys && fk.valid;
@@ -209,9 +306,8 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
     // the device, so only the kernel can tell), goes to k_block_rest like a stale hint.
     // What is left has a known Clean (below), with no row examined.
     const bool stale = dense_subclients(rs) != hint;
-    // MASKED: the released-row bit alone does not send the item there, but an item with no live
-    // row does (under these conditions the running count is exact and every live row counts at
-    // least 1): the plain path's empty-range arithmetic stays in one place.
+    // (steady_rest<MASKED>, written out and equal to it: behind the call the compiler orders
+    // the test's terms differently and the unmasked steady builds' code moves)
     const bool rest = STEADY ? stale || (hw >> 8 & (MASKED ? 2 : 3)) != 0 || p.now > rs.follow_exp || p.recompute ||
                                    (MASKED && rs.agg_count == 0)
                              : stale || arr_lapse;
@@ -225,7 +321,7 @@ __device__ __forceinline__ void group_segment(const DevParams& p, const WorkItem
         // the rows, running sums and state that are still there (FixKey): this tick would
         // store no gets, reduce a delta of +0.0 and write the sums it read.  It writes the
         // record as the full path would and is done.
-        if (fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
+        if (key_holds(fk, rs)) {
           if (t == 0) write_fixed(p, seg, rs, hint);
           return;
         }

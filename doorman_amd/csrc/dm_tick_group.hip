@@ -1,8 +1,8 @@
 // dm_tick_group.hip — gfx950 kernels for one apportionment tick: the resource-per-group
 // kernels (workgroup bins, sub-wave groups, packed tiles).  The other work classes of a
 // tick: dm_tick_large.hip (the large-resource chain), dm_tick_general.hip (k_general).
-// group_segment, the body of the workgroup and sub-wave kernels, is in dm_tick_group.h, which
-// dm_tick_masked.hip (the steady kernels' masked builds) instantiates too.
+// group_segment, the body of the workgroup and sub-wave kernels, is in dm_tick_group.h; the
+// split form's dense-side kernels are in dm_tick_steady.h (this unit: their unmasked builds).
 //
 // Every lease row is decided against the same frozen store (include/doorman_hip.h).
 // Per resource the reference's per-request loops (go/server/doorman/algorithm.go)
@@ -22,7 +22,7 @@
 //
 // Float semantics follow Go on amd64: binary64, no FMA contraction (built with
 // -ffp-contract=off), minF = `l > r ? r : l`, IEEE division by zero.
-#include "dm_tick_group.h"
+#include "dm_tick_steady.h"
 
 namespace dm {
 
@@ -42,286 +42,7 @@ __global__ __launch_bounds__(G, (G <= 256 && R == 8) ? 5 : 1) void k_block(DevPa
   group_segment<G, R>(p, items[blockIdx.x], items + blockIdx.x, threadIdx.x, lds, general_list, general_count);
 }
 
-// The workgroup bins split by the dense hint (launch_bin_dense / launch_bin_rest):
-// k_block_dense decides the items whose hint is set without the subclients column
-// (128 x 8: 73 VGPRs, 6 waves per SIMD instead of 5; its steady builds 66 and 7: 14336
-// rows in flight per CU) and queues the others; k_block_rest decides the queue with the
-// mixed body, a grid striding over it (sized from the last split tick's queue; an empty queue costs
-// one small launch).  qcnt is a two-slot ring: this tick's count in qcnt[par], and
-// k_block_rest clears qcnt[par ^ 1] for the next tick (stream order); host_count
-// (host-mapped) tells the host how many items went to the queue (its choice of
-// split or mixed), written only when the count differs from the last one written
-// (qcnt[2]): a system-scope store to host memory keeps an otherwise empty launch
-// alive ~2 us longer, every tick of a dense store.
-// When the host skips k_block_rest (every item of the bin verified dense in this row
-// epoch, dm_tick.cpp), `guard` (host-mapped) is set should the dense kernel queue
-// an item after all, which the host reports as DM_E_INTERNAL (and refuses the store)
-// instead of leaving the item undecided unnoticed.  The tick's last kernel (this one,
-// or the rest kernel) is launched with the tick's stop event when another queue waits
-// for the tick (dm_ctx.h tick_ev).
-// (128 x 8 held to 7 waves per SIMD: 71 VGPRs + 20 B of spill, C3 430 -> 590 us; round 5.)
-// SKIP: the build a writeback tick in place runs (group_segment: unchanged runs of gets
-// are not stored); every other tick runs the build without it.
-// STEADY: the builds for a part the host knows to hold only dense items without released
-// rows or arrivals, outside recompute mode (group_segment: Clean's result is known; an item
-// it is not known for is queued, so the rest kernel follows every steady launch).  As a
-// run-time branch in one build the two bodies need 84-87 VGPRs (5 waves per SIMD).
-template <int G, int R, bool SKIP = false, bool STEADY = false>
-__global__ __launch_bounds__(G) void k_block_dense(DevParams p, WorkItem* __restrict__ items, int nitems,
-                                                   int32_t* queue, int32_t* qcnt, int par,
-                                                   int32_t* general_list, int32_t* general_count,
-                                                   int32_t* guard) {
-  __shared__ Lds<G> lds;
-  if ((int)blockIdx.x < nitems) {
-    const WorkItem wi = items[blockIdx.x];
-    if ((wi.n >> 16) == 0) {
-      if (threadIdx.x == 0)
-        hand_off<false>(nullptr, FixKey{0, 0, 0}, 0, queue, qcnt, par, (int32_t)blockIdx.x, nitems, guard);
-    } else {
-      group_segment<G, R, kDenseOnly, SKIP, STEADY>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
-                                                    general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
-                                                    nitems);
-    }
-  }
-}
-
-// FIXED: k_block_dense<G, R, true, true> for a part ticking in place, as a kernel of its own
-// name and arguments, so that the builds above stay the code they were.  Each item has a
-// key (dm_device.h FixKey; `keys` runs parallel to `items`) that the build sets when the
-// item's tick changed nothing, and clears when it did or hands the item to other code;
-// with use_keys (the part's last tick was this build too and no call has written rows
-// since: dm_ctx.h fix_live) an item whose key still matches its capacity and kind loads
-// no row at all.
-template <int G, int R>
-__global__ __launch_bounds__(G) void k_block_dense_fixed(DevParams p, WorkItem* __restrict__ items, int nitems,
-                                                         int32_t* queue, int32_t* qcnt, int par,
-                                                         int32_t* general_list, int32_t* general_count,
-                                                         int32_t* guard, FixKey* __restrict__ keys, int use_keys) {
-  __shared__ Lds<G> lds;
-  if ((int)blockIdx.x < nitems) {
-    const WorkItem wi = items[blockIdx.x];
-    const FixKey fk = keys[blockIdx.x];
-    if ((wi.n >> 16) == 0) {
-      if (threadIdx.x == 0)
-        hand_off<true>(keys + blockIdx.x, fk, use_keys, queue, qcnt, par, (int32_t)blockIdx.x, nitems, guard);
-    } else {
-      group_segment<G, R, kDenseOnly, true, true, true>(p, wi, items + blockIdx.x, threadIdx.x, lds, general_list,
-                                                        general_count, queue, qcnt + par, (int32_t)blockIdx.x, guard,
-                                                        nitems, keys + blockIdx.x, fk, use_keys);
-    }
-  }
-}
-
-// The sweep: a FIXED launch with keys in use (above) spends a workgroup on every item only
-// to find, from two scalar loads, that most need no rows (C3: 69,400 of 100,000; such a
-// launch over items all at their fixed point runs 55 us with no row loaded,
-// profiles/sweep_share.md).  That test is a lane's work.  k_fixed_sweep takes one lane per
-// item of the part: the item, its key and its record, exactly the tests of
-// group_segment<.., FIXED> before its rows (the steady `rest` test, a zero hint word, the
-// key against the record); an item that passes them all gets the same write_fixed call
-// and is done, any other is appended to the part's worklist with its key in memory cleared.
-// k_block_dense_list then runs the FIXED build over the worklist alone: every item it sees
-// has an invalid key in memory, so it loads none (FixKey{0, 0, 0}), loads its rows at once
-// and stores a key only for an item that turns out fixed.  Everything behind the key test
-// (the rest queue, k_general's list, the keys) is group_segment's code as it was.
-// Appends: a ballot and prefix within the wave, one LDS step across the waves, one
-// returning atomicAdd per 1,024 items on the count word (one per item or wave on one word:
-// DESIGN.md section 3.1).  The list's order varies from run to run; no result depends on
-// it (resources are independent, each one's sums stay in its workgroup's fixed order).
-// lcnt is a two-slot ring as qcnt is: this tick's count in lcnt[par], the sweep clears
-// lcnt[par ^ 1]; the list kernel tells the host the count ({count, row epoch},
-// host-mapped: the next launches' grid size, a hint only) when either differs from the
-// last told (lcnt[2], lcnt[3]).
-__global__ __launch_bounds__(1024) void k_fixed_sweep(DevParams p, const WorkItem* __restrict__ items, int nitems,
-                                                      FixKey* __restrict__ keys, SweepEntry* __restrict__ list,
-                                                      int32_t* lcnt, int par) {
-  __shared__ int wtot[16];
-  const int i = (int)(blockIdx.x * 1024u + threadIdx.x);
-  if (i == 0) lcnt[par ^ 1] = 0;
-  bool app = false;
-  WorkItem wi{0, 0, 0};
-  if (i < nitems) {
-    wi = items[i];
-    const FixKey fk = keys[i];
-    const int hw = wi.n >> 16;
-    bool done = false;
-    if (hw != 0 && fk.valid) {
-      const Res rs = load_res(p, wi.seg);
-      const int hint = hw & 0xFF;
-      const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
-      if (!rest && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
-        write_fixed(p, wi.seg, rs, hint);
-        done = true;
-      }
-    }
-    if (!done) {
-      app = true;
-      if (fk.valid) keys[i] = FixKey{0, 0, 0};
-    }
-  }
-  const uint64_t bal = __ballot(app);
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wtot[wave] = __popcll(bal);
-  __syncthreads();
-  if (threadIdx.x == 0) {  // the waves' totals -> their first slots in the list
-    int tot = 0;
-    for (int w = 0; w < 16; ++w) tot += wtot[w];
-    int base = tot > 0 ? atomicAdd(lcnt + par, tot) : 0;
-    for (int w = 0; w < 16; ++w) {
-      const int c = wtot[w];
-      wtot[w] = base;
-      base += c;
-    }
-  }
-  __syncthreads();
-  const int slot = wtot[wave] + pre;  // (below nitems: the slot's count started at zero)
-  if (app && slot < nitems) list[slot] = SweepEntry{wi.seg, wi.n, wi.lo, i, {0, 0, 0}};
-}
-
-template <int G, int R>
-__global__ __launch_bounds__(G) void k_block_dense_list(DevParams p, WorkItem* __restrict__ items, int nitems,
-                                                        const SweepEntry* __restrict__ list, int32_t* lcnt, int lpar,
-                                                        unsigned long long* host_count, unsigned long long epoch,
-                                                        int32_t* queue, int32_t* qcnt, int par, int32_t* general_list,
-                                                        int32_t* general_count, FixKey* __restrict__ keys) {
-  __shared__ Lds<G> lds;
-  const int count = min(lcnt[lpar], nitems);
-  SweepEntry e = list[blockIdx.x];  // with the count (the grid is at most nitems: in the list, used only below count)
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (lcnt[2] != count || lcnt[3] != (int32_t)epoch)) {
-    __hip_atomic_store(host_count, (unsigned long long)(unsigned)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    lcnt[2] = count;
-    lcnt[3] = (int32_t)epoch;
-  }
-  for (int q = blockIdx.x; q < count; q += gridDim.x) {
-    if (q != (int)blockIdx.x) e = uniform(list[q]);
-    const WorkItem wi{e.seg, e.n, e.lo};
-    // (the lane index anew for every item: what the compiler derives from it once for the
-    // whole loop stays in VGPRs across the item's passes: 103 against 65)
-    int t = (int)threadIdx.x;
-    asm volatile("" : "+v"(t));
-    if ((wi.n >> 16) == 0) {  // (its key is invalid in memory: the sweep saw to it)
-      if (threadIdx.x == 0) hand_off<false>(nullptr, FixKey{0, 0, 0}, 0, queue, qcnt, par, e.idx, nitems, nullptr);
-    } else {
-      group_segment<G, R, kDenseOnly, true, true, true, true>(p, wi, items + e.idx, t, lds, general_list,
-                                                              general_count, queue, qcnt + par, e.idx, nullptr, nitems,
-                                                              keys + e.idx, FixKey{0, 0, 0}, 1);
-    }
-    __syncthreads();  // the next item reuses the single-use LDS slots
-  }
-}
-
-// The cycle form: the sweep and the row kernel of a steady writeback tick that writes the
-// alternate column (dm_device.h CycAux: the key's states and the proof; dm_split_form.h: when
-// the host launches it).  k_cycle_sweep is k_fixed_sweep with the generalised test: an item
-// whose key is in state 2 and passes the steady `rest` test and the capacity / kind / learning
-// test reproduces its state of two ticks ago, which its destination column still holds: the
-// lane writes its record with sum_has := prev_has (write_fixed's record otherwise: follow_exp,
-// the published block, the state byte) and sets prev_has to the sum just read -- a store only
-// where the two differ, so an item at a fixed point writes no key.  Every other item goes to
-// the worklist with its key in memory cleared, and with what the row kernel must know before
-// its loads in the entry (SweepEntry::pad): whether to load the destination rows (state 1
-// under the same capacity and kind, the back-off run out) and whether the back-off goes on.
-// Without use_keys (the part's last tick was no cycle-form tick, or a call wrote rows since)
-// every key counts as state 0: every item is listed, stores every run and gets a fresh key.
-__global__ __launch_bounds__(1024) void k_cycle_sweep(DevParams p, const WorkItem* __restrict__ items, int nitems,
-                                                      FixKey* __restrict__ keys, CycAux* __restrict__ aux,
-                                                      SweepEntry* __restrict__ list, int32_t* lcnt, int par,
-                                                      int use_keys) {
-  __shared__ int wtot[16];
-  const int i = (int)(blockIdx.x * 1024u + threadIdx.x);
-  if (i == 0) lcnt[par ^ 1] = 0;
-  bool app = false;
-  int probe = 0, carry = 0;
-  WorkItem wi{0, 0, 0};
-  if (i < nitems) {
-    wi = items[i];
-    const FixKey fk = keys[i];
-    const CycAux ax = aux[i];
-    const int hw = wi.n >> 16;
-    const int state = use_keys ? fk.valid : 0;
-    bool done = false;
-    if (hw != 0 && state != 0) {
-      const Res rs = load_res(p, wi.seg);
-      const int hint = hw & 0xFF;
-      const bool rest = dense_subclients(rs) != hint || (hw >> 8 & 3) != 0 || p.now > rs.follow_exp || p.recompute;
-      if (!rest && fk.cbits == (uint64_t)__double_as_longlong(rs.C) && fk.kind == rs.kind && !rs.learning) {
-        if (state == 2) {
-          write_resource(p, wi.seg, rs, Clean{rs.agg_count, __longlong_as_double((long long)ax.prev_has), rs.agg_wants},
-                         0.0, hint);
-          const uint64_t was = (uint64_t)__double_as_longlong(rs.agg_has);
-          if (ax.prev_has != was) aux[i].prev_has = was;
-          done = true;
-        } else if (ax.skip > 0) {
-          aux[i].skip = ax.skip - 1;
-          carry = 1;
-        } else {
-          probe = carry = 1;
-        }
-      }
-    }
-    if (!done) {
-      app = true;
-      if (fk.valid) keys[i] = FixKey{0, 0, 0};
-    }
-  }
-  const uint64_t bal = __ballot(app);
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wtot[wave] = __popcll(bal);
-  __syncthreads();
-  if (threadIdx.x == 0) {  // the waves' totals -> their first slots in the list
-    int tot = 0;
-    for (int w = 0; w < 16; ++w) tot += wtot[w];
-    int base = tot > 0 ? atomicAdd(lcnt + par, tot) : 0;
-    for (int w = 0; w < 16; ++w) {
-      const int c = wtot[w];
-      wtot[w] = base;
-      base += c;
-    }
-  }
-  __syncthreads();
-  const int slot = wtot[wave] + pre;  // (below nitems: the slot's count started at zero)
-  if (app && slot < nitems) list[slot] = SweepEntry{wi.seg, wi.n, wi.lo, i, {probe, carry, 0}};
-}
-
-template <int G, int R>
-__global__ __launch_bounds__(G) void k_block_cycle_list(DevParams p, WorkItem* __restrict__ items, int nitems,
-                                                        const SweepEntry* __restrict__ list, int32_t* lcnt, int lpar,
-                                                        unsigned long long* host_count, unsigned long long epoch,
-                                                        int32_t* queue, int32_t* qcnt, int par, int32_t* general_list,
-                                                        int32_t* general_count, FixKey* __restrict__ keys,
-                                                        CycAux* __restrict__ aux, unsigned stamp, int tell) {
-  __shared__ Lds<G> lds;
-  const int count = min(lcnt[lpar], nitems);
-  SweepEntry e = list[blockIdx.x];  // with the count (the grid is at most nitems: in the list, used only below count)
-  // (the count's high half: the host's stamp of this launch; tell: told whether it changed or
-  // not, while the host waits to judge the form by a count of a known tick -- CycleAuto)
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (tell || lcnt[2] != count || lcnt[3] != (int32_t)epoch)) {
-    __hip_atomic_store(host_count, (unsigned long long)(unsigned)count | (unsigned long long)stamp << 32,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(host_count + 1, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    lcnt[2] = count;
-    lcnt[3] = (int32_t)epoch;
-  }
-  for (int q = blockIdx.x; q < count; q += gridDim.x) {
-    if (q != (int)blockIdx.x) e = uniform(list[q]);
-    const WorkItem wi{e.seg, e.n, e.lo};
-    int t = (int)threadIdx.x;  // (anew for every item: k_block_dense_list)
-    asm volatile("" : "+v"(t));
-    if ((wi.n >> 16) == 0) {  // (its key is invalid in memory: the sweep saw to it)
-      if (threadIdx.x == 0) hand_off<false>(nullptr, FixKey{0, 0, 0}, 0, queue, qcnt, par, e.idx, nitems, nullptr);
-    } else {
-      const CycAux ax = uniform(aux[e.idx]);
-      group_segment<G, R, kDenseOnly, true, true, true, true, true>(
-          p, wi, items + e.idx, t, lds, general_list, general_count, queue, qcnt + par, e.idx, nullptr, nitems,
-          keys + e.idx, FixKey{0, 0, 0}, 0, aux + e.idx, ax, e.pad[0], e.pad[1]);
-    }
-    __syncthreads();  // the next item reuses the single-use LDS slots
-  }
-}
-
+// The split form's dense side -- k_block_dense, k_sweep, k_block_list -- is dm_tick_steady.h.
 template <int G, int R>
 __global__ __launch_bounds__(G) void k_block_rest(DevParams p, WorkItem* __restrict__ items,
                                                   const int32_t* __restrict__ queue, int32_t* qcnt, int par,
@@ -677,76 +398,26 @@ hipError_t launch_subs(const DevParams& p, const SubBins& sb, int32_t* glist, in
   return hipGetLastError();
 }
 
-// The 128-thread bins (3: 128 x 4, 4: 128 x 8) split by the dense hint: the dense
-// kernel over every item, then the rest kernel over what it queued (two launches,
-// timed separately).
-// done (optional): an event the launch itself completes (hipExtLaunchKernel's stop
-// event: no marker packet of its own on the queue), for another stream to wait on
-// steady: the builds that take Clean's result as known and queue every item it is not
-// known for (group_segment STEADY); the caller launches the rest kernel after them.
-// keys (optional; only with steady, on a writeback tick in place): the FIXED build, over the
-// keys of these items; use_keys: valid keys may be trusted (else every key is rewritten).
+// The bins split by the dense hint: the dense kernel over every item, then the rest kernel over
+// what it queued (two launches, timed separately).  dm_launch.h has the three launchers'
+// arguments; a masked launch goes to dm_tick_masked.hip's half.
 hipError_t launch_bin_dense(const BinItems& w, const DevParams& p, const SplitArgs& a, hipEvent_t done, bool steady,
-                            FixKey* keys, bool use_keys, hipStream_t st) {
-  const int n = w.n;
-  if (n <= 0) return hipSuccess;
-  const dim3 grid((unsigned)n);
-  // in place (the gets go to the column the has came from): the build that skips unchanged runs
-  const bool skip = p.writeback && p.out_gets == p.has;
-  if (keys && !(skip && steady)) return hipErrorInvalidValue;
-  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
-    constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    if (keys) {
-      hipExtLaunchKernelGGL((k_block_dense_fixed<G, R>), grid, dim3(G), 0, st, nullptr, done, 0, p, w.items, n, a.queue,
-                            a.qcnt, a.par, a.glist, a.gcount, a.guard, keys, use_keys ? 1 : 0);
-      return;
-    }
-    with_bool(skip, [&](auto sk) {
-      with_bool(steady, [&](auto sd) {
-        hipExtLaunchKernelGGL((k_block_dense<G, R, decltype(sk)::value, decltype(sd)::value>), grid, dim3(G), 0, st,
-                              nullptr, done, 0, p, w.items, n, a.queue, a.qcnt, a.par, a.glist, a.gcount, a.guard);
-      });
-    });
-  });
-  return known ? hipGetLastError() : hipErrorInvalidValue;
+                            bool masked, FixKey* keys, bool use_keys, hipStream_t st) {
+  if (masked && !steady) return hipErrorInvalidValue;  // masked implies steady
+  if (masked) return launch_dense_masked(w, p, a, done, keys, use_keys, st);
+  return launch_dense_build<false>(w, p, a, done, steady, keys, use_keys, st);
 }
 
-// A FIXED launch with keys in use, as the sweep and the row kernel over its worklist
-// (k_fixed_sweep): the rest launch follows as after launch_bin_dense's steady builds.
-hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+hipError_t launch_bin_sweep(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw, bool masked,
                             hipStream_t st) {
-  const int n = w.n;
-  if (n <= 0) return hipSuccess;
-  if (!(p.writeback && p.out_gets == p.has) || !sw.keys) return hipErrorInvalidValue;
-  const dim3 lg((unsigned)std::max(1, std::min(n, sw.list_grid)));
-  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
-    constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    k_fixed_sweep<<<dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, st>>>(p, w.items, n, sw.keys, sw.list, sw.lcnt,
-                                                                              sw.lpar);
-    k_block_dense_list<G, R><<<lg, dim3(G), 0, st>>>(p, w.items, n, sw.list, sw.lcnt, sw.lpar, sw.host_count, sw.epoch,
-                                                     a.queue, a.qcnt, a.par, a.glist, a.gcount, sw.keys);
-  });
-  return known ? hipGetLastError() : hipErrorInvalidValue;
+  if (masked) return launch_list_masked(false, w, p, a, sw, nullptr, true, 0u, false, st);
+  return launch_list_build<false, false>(w, p, a, sw, nullptr, true, 0u, false, st);
 }
 
-// The cycle form (k_cycle_sweep): a steady writeback tick on the alternate column.  The first
-// such launch of a part (use_keys false) lists and rewrites every item through the same two
-// kernels; the rest launch follows either.
-hipError_t launch_bin_cycle(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw,
+hipError_t launch_bin_cycle(const BinItems& w, const DevParams& p, const SplitArgs& a, const SweepArgs& sw, bool masked,
                             CycAux* aux, bool use_keys, unsigned stamp, bool tell, hipStream_t st) {
-  const int n = w.n;
-  if (n <= 0) return hipSuccess;
-  if (!(p.writeback && p.out_gets != p.has) || !sw.keys || !aux) return hipErrorInvalidValue;
-  const dim3 lg((unsigned)std::max(1, std::min(n, use_keys ? sw.list_grid : n)));
-  const bool known = with_bin_shape(w.bin, [&](auto g, auto r) {
-    constexpr int G = decltype(g)::value, R = decltype(r)::value;
-    k_cycle_sweep<<<dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, st>>>(p, w.items, n, sw.keys, aux, sw.list,
-                                                                              sw.lcnt, sw.lpar, use_keys ? 1 : 0);
-    k_block_cycle_list<G, R><<<lg, dim3(G), 0, st>>>(p, w.items, n, sw.list, sw.lcnt, sw.lpar, sw.host_count, sw.epoch,
-                                                     a.queue, a.qcnt, a.par, a.glist, a.gcount, sw.keys, aux, stamp,
-                                                     tell ? 1 : 0);
-  });
-  return known ? hipGetLastError() : hipErrorInvalidValue;
+  if (masked) return launch_list_masked(true, w, p, a, sw, aux, use_keys, stamp, tell, st);
+  return launch_list_build<true, false>(w, p, a, sw, aux, use_keys, stamp, tell, st);
 }
 
 // dm_store_stats for a part in the cycle form: out[0] the keys in state 2, out[1] those of

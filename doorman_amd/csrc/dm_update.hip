@@ -66,7 +66,7 @@ __global__ void k_clear_rows(int64_t n, const int64_t* __restrict__ rows, int64_
 // DM_KEEP_UPDATES while some part has keys in use (dm_row_epoch.h); they store an invalid key
 // for every workgroup-bin resource of which the call writes a row.  The tick kernels would
 // not trust such a resource's key anyway (the stale hint, the mask bit: group_segment STEADY,
-// k_fixed_sweep); cleared here, a valid key keeps meaning what dm_device.h FixKey says.
+// k_sweep); cleared here, a valid key keeps meaning what dm_device.h FixKey says.
 __global__ void k_upsert(int64_t n, const int64_t* __restrict__ rows, const double* __restrict__ has,
                          const double* __restrict__ wants, const int64_t* __restrict__ sub,
                          const int32_t* __restrict__ sub32, const int64_t* __restrict__ expiry,

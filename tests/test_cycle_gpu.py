@@ -1,4 +1,4 @@
-"""The cycle form of the dense tick (dm_tick_group.hip k_cycle_sweep / k_block_cycle_list,
+"""The cycle form of the dense tick (dm_tick_steady.h: the cycle builds of k_sweep / k_block_list,
 dm_device.h CycAux): a steady writeback tick on the alternate column
 moves no row of a resource whose tick provably reproduces its state of two ticks ago, which
 the destination column still holds; only its record alternates.

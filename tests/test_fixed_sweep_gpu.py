@@ -1,10 +1,10 @@
-"""The sweep in front of the FIXED build of the dense tick kernel (dm_tick_group.hip
-k_fixed_sweep / k_block_dense_list): a FIXED launch with keys in use runs as
+"""The sweep in front of the FIXED build of the dense tick kernel (dm_tick_steady.h
+k_sweep / k_block_list): a FIXED launch with keys in use runs as
 one lane per item, which finishes every item whose key holds (the write_resource call the
 workgroup made) and lists the others with their keys cleared, then the FIXED build over the
 list alone, its grid sized from the count the device last told the host.
 
-Nothing a caller can read may depend on it: engine A (DM_SWEEP=0: k_block_dense_fixed over
+Nothing a caller can read may depend on it: engine A (DM_SWEEP=0: k_block_dense's kFixed build over
 every item, as before) and engine B (the default) hold identical bits after every tick, B
 matches the oracle, and dm_plan_info's "sweep_parts" is 0 for A and positive for B exactly
 when "fixed_parts" is.

@@ -1,7 +1,7 @@
 """dm_keep_keys' DM_KEEP_FREE_SLOTS: with bit 4 set a dense workgroup-bin
 resource that holds released rows (free slots), with no pending arrival and a live row, is an
 item of the steady, FIXED, sweep and cycle forms like any other (the kernels' masked builds:
-dm_tick_masked.hip, dm_tick_group.h group_segment MASKED): it keeps a fixed-point key and is
+dm_tick_masked.hip, dm_tick_group.h group_segment kMasked): it keeps a fixed-point key and is
 skipped at its fixed point or in its proven two-tick cycle.
 
 As in tests/test_keep_keys_gpu.py and tests/test_keep_updates_gpu.py, whose store, Pair and

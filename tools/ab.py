@@ -105,7 +105,8 @@ def main():
         t = res[p]["tick_us"]
         print(f"{os.path.basename(p):34s} kernel med {statistics.median(k):8.2f} us min {min(k):8.2f} "
               f"({alg / min(k) / 1e3:7.1f} GB/s best) | tick med {statistics.median(t):8.2f} us | "
-              f"unprofiled tick med {statistics.median(res[p]['plain_us']):8.2f} min {min(res[p]['plain_us']):8.2f} us")
+              f"unprofiled tick med {statistics.median(res[p]['plain_us']):8.2f} min {min(res[p]['plain_us']):8.2f} "
+              f"max {max(res[p]['plain_us']):8.2f} us")
         if args.per_kernel:
             print("    " + "  ".join(f"{n} {statistics.median(v):.1f}" for n, v in sorted(res[p]["cls"].items())))
     for e in engines:

@@ -2,7 +2,7 @@
 store of which a share of the resources holds a free slot.
 
   python tools/free_slots_ab.py [--resources 100000] [--runs 10] [--shares 0.01,0.3,1.0]
-                                [--parent tools/ab_libs/parent.so] [--out profiles/free_slots_ab.md]
+                                [--parent tools/ab_libs/parent.so [--parent-mode 7]] [--out profiles/free_slots_ab.md]
 
 A store of configs[3]'s shape (R resources x 1,000 rows, FairShare, every resource under
 capacity with wants multiples of 2^-10: tools/sweep_share.py's) is loaded into two engines in
@@ -49,18 +49,18 @@ def state(e):
         "fixed_items": st["fixed_items"], "mode": e.keep_stats()["mode"]}
 
 
-def one_share(snap, f, runs, parent, rng):
+def one_share(snap, f, runs, parent, rng, parent_mode=3):
     from doorman_amd.engine import Engine
     R = len(snap["seg_off"]) - 1
     clients = len(snap["wants"]) // R
     k = max(1, int(round(f * R)))
     res = np.sort(rng.choice(R, k, replace=False).astype(np.int64))
     rows = res * clients + rng.integers(0, clients, k)
-    names = ["mode3", "mode7"] + (["parent_mode3"] if parent else [])
+    names = ["mode3", "mode7"] + (["parent_mode%d" % parent_mode] if parent else [])
     engs = [Engine(0), Engine(0)] + ([Engine(0, parent)] if parent else [])
     out = {"share": f, "holders": k}
     try:
-        for e, m in zip(engs, (3, 7, 3)):
+        for e, m in zip(engs, (3, 7, parent_mode)):
             e.keep_keys(m)
             e.load(snap)
             e.release(rows)
@@ -110,7 +110,8 @@ def markdown(out):
     for c in out["cases"]:
         for col in ("inplace", "alternate"):
             v = c[col]
-            m7, m3, par = v["mode7"]["tick_us"], v["mode3"]["tick_us"], v.get("parent_mode3", {}).get("tick_us")
+            m7, m3 = v["mode7"]["tick_us"], v["mode3"]["tick_us"]
+            par = next((x["tick_us"] for n, x in v.items() if n.startswith("parent_mode")), None)
             L.append("| %g | %s | %s | %s | %s |"
                      % (c["share"], col, "yes" if m7["max"] < m3["min"] else "no",
                         ("yes" if m7["max"] < par["min"] else "no") if par else "-",
@@ -124,6 +125,7 @@ if __name__ == "__main__":
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--shares", default="0.01,0.3,1.0")
     ap.add_argument("--parent", default=None, help="the parent commit's build of the library, for a third engine")
+    ap.add_argument("--parent-mode", type=int, default=3, help="the third engine's dm_keep_keys mode (7: the masked builds of both libraries side by side)")
     ap.add_argument("--out")
     a = ap.parse_args()
     rng = np.random.default_rng(3)
@@ -132,7 +134,7 @@ if __name__ == "__main__":
     out = {"resources": a.resources, "rows": int(len(snap["wants"])), "runs": a.runs, "parent": bool(a.parent),
            "cases": []}
     for f in (float(x) for x in a.shares.split(",") if x):
-        out["cases"].append(one_share(snap, f, a.runs, a.parent, rng))
+        out["cases"].append(one_share(snap, f, a.runs, a.parent, rng, a.parent_mode))
     out["seconds"] = round(time.perf_counter() - t0, 1)
     print(json.dumps(out))
     if a.out:

@@ -20,11 +20,12 @@ CLASS = [
     (r"k_block_dense(_fixed)?<128, 4(, \w+)*>", "block128x4_dense"), (r"k_block_dense(_fixed)?<128, 8(, \w+)*>", "block128x8_dense"), (r"k_block_dense(_fixed)?<64, 16(, \w+)*>", "block128x8_dense"),
     (r"k_block_dense(_fixed)?<256, 8(, \w+)*>", "block256x8_dense"), (r"k_block_dense(_fixed)?<512, 8(, \w+)*>", "block2k4k_dense"),
     (r"k_block_dense(_fixed)?<256, 16(, \w+)*>", "block2k4k_dense"),
-    # the sweeps and the row kernels over their worklists (timed inside the dense class by the library)
-    (r"k_fixed_sweep\b", "fixed_sweep"), (r"k_cycle_sweep\b", "cycle_sweep"),
-    (r"k_block_(dense|cycle)_list<128, 4>", "block128x4_list"), (r"k_block_(dense|cycle)_list<128, 8>", "block128x8_list"),
-    (r"k_block_(dense|cycle)_list<64, 16>", "block128x8_list"), (r"k_block_(dense|cycle)_list<256, 8>", "block256x8_list"),
-    (r"k_block_(dense|cycle)_list<(512, 8|256, 16)>", "block2k4k_list"),
+    # the sweeps and the row kernels over their worklists (timed inside the dense class by the library);
+    # k_sweep<CYCLE, MASKED>, k_block_list<G, R, CYCLE, MASKED>, and their names in older traces
+    (r"k_fixed_sweep\b|k_sweep<false(, \w+)*>", "fixed_sweep"), (r"k_cycle_sweep\b|k_sweep<true(, \w+)*>", "cycle_sweep"),
+    (r"k_block_((dense|cycle)_)?list<128, 4(, \w+)*>", "block128x4_list"), (r"k_block_((dense|cycle)_)?list<128, 8(, \w+)*>", "block128x8_list"),
+    (r"k_block_((dense|cycle)_)?list<64, 16(, \w+)*>", "block128x8_list"), (r"k_block_((dense|cycle)_)?list<256, 8(, \w+)*>", "block256x8_list"),
+    (r"k_block_((dense|cycle)_)?list<(512, 8|256, 16)(, \w+)*>", "block2k4k_list"),
     (r"k_publish\b", "hier_publish"), (r"k_hier_tick\b", "hier_root"),
     (r"k_tick_done\b", "tick_done"), (r"k_count_undense\b", "count_undense"),
     (r"k_large_spec\b", "large_spec"), (r"k_large_redo(_team)?\b", "large_redo"),
