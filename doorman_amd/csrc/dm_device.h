@@ -235,7 +235,7 @@ struct Partials {
 };
 constexpr int kSegTotBytes = 128;
 
-// The speculative chain (k_large_spec / k_large_redo, dm_tick_large.hip): per large
+// The speculative chain (k_large_spec / k_large_redo, dm_tick_large_spec.h): per large
 // resource, the round-1 / round-2 totals and the live rows' count its last tick
 // verified (or redid), used as this tick's speculation; the redo's inputs and meeting
 // points.  Reductions over a resource's chunk partials here all take one fixed tree

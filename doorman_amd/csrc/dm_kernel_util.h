@@ -489,6 +489,7 @@ __device__ __forceinline__ void st_wt(uint64_t* a, uint64_t v) {
 }
 __device__ __forceinline__ void st_wt(double* a, double v) { st_wt((uint64_t*)a, __builtin_bit_cast(uint64_t, v)); }
 __device__ __forceinline__ void st_wt(int64_t* a, int64_t v) { st_wt((uint64_t*)a, (uint64_t)v); }
+__device__ __forceinline__ void st_wt(long long* a, long long v) { st_wt((uint64_t*)a, (uint64_t)v); }
 __device__ __forceinline__ void st_wt(int32_t* a, int32_t v) {
   __hip_atomic_store((gu32*)a, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -497,6 +498,7 @@ __device__ __forceinline__ uint64_t ld_wt(const uint64_t* a) {
 }
 __device__ __forceinline__ double ld_wt(const double* a) { return __builtin_bit_cast(double, ld_wt((const uint64_t*)a)); }
 __device__ __forceinline__ int64_t ld_wt(const int64_t* a) { return (int64_t)ld_wt((const uint64_t*)a); }
+__device__ __forceinline__ long long ld_wt(const long long* a) { return (long long)ld_wt((const uint64_t*)a); }
 __device__ __forceinline__ int32_t ld_wt(const int32_t* a) {
   return (int32_t)__hip_atomic_load((gu32*)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

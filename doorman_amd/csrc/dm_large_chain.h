@@ -1,4 +1,5 @@
-// dm_large_chain.h — the host half of the large-resource chain (dm_tick_large.hip): the one
+// dm_large_chain.h — the host half of the large-resource chain (the device half: the unit
+// dm_tick_large.hip, its forms in dm_tick_large.h, _spec.h and _het.h): the one
 // owner of what the chain keeps from tick to tick.  dm_large_form.h decides the form of a
 // tick's launches (plain C++, tested on the CPU); LargeChain holds the buffers and the words
 // the device tells the host, and Tick::large_chain (dm_tick.cpp) asks, then launches.

@@ -14,7 +14,7 @@
 
 namespace dm {
 
-// The chain's launches (dm_tick_large.hip has a kernel for each), named in launch order.
+// The chain's launches (the unit dm_tick_large.hip has a kernel for each), named in launch order.
 enum class LargePhase : uint8_t { A, B, T, C, C_HET, E, MAP, MAP_HET, FIN, SPEC, REDO_FULL, REDO_LIGHT };
 constexpr int kLargePhases = 12;
 

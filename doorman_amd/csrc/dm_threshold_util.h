@@ -1,5 +1,5 @@
 // dm_threshold_util.h — FairShare round 2 by sorted thresholds: the helpers k_general
-// (dm_tick_general.hip) and the chain's heterogeneous kernels (dm_tick_large.hip) share.
+// (dm_tick_general.hip) and the chain's heterogeneous kernels (dm_tick_large_het.h) share.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -29,8 +29,8 @@ enum { kMixed = 0, kDenseOnly = 1, kRest = 2 };
 // spans: whole lines); plain for the sub-wave groups, whose spans are short and
 // unaligned, so that L2 merges the partial sectors two groups write at a resource
 // boundary (C2 112.2-112.5 -> 109.6-111.1 us, three interleaved rounds; the chain's
-// stores plain: no change; profiles/r05_ab/c2_gets_stores.txt; the chain's switch is
-// kSpecNT, dm_tick_large.hip)
+// stores plain: no change; profiles/r05_ab/c2_gets_stores.txt; the chain's maps take
+// put_live's default, map_row in dm_tick_large.h)
 template <int G> constexpr bool kGroupNT = G >= 128;
 
 // One live row's gets in the skipping map of group_segment: the resource's algorithm on

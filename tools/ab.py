@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--per-kernel", action="store_true", help="median us per tick of every kernel class")
+    ap.add_argument("--values", action="store_true", help="every round's unprofiled tick, us")
     args = ap.parse_args()
     if args.workload.startswith("u") and "x" in args.workload:  # uRxC: R resources x C clients, FairShare
         nr, nc = (int(v) for v in args.workload[1:].split("x"))
@@ -107,6 +108,8 @@ def main():
               f"({alg / min(k) / 1e3:7.1f} GB/s best) | tick med {statistics.median(t):8.2f} us | "
               f"unprofiled tick med {statistics.median(res[p]['plain_us']):8.2f} min {min(res[p]['plain_us']):8.2f} "
               f"max {max(res[p]['plain_us']):8.2f} us")
+        if args.values:
+            print("    unprofiled tick per round: " + " ".join(f"{v:.2f}" for v in res[p]["plain_us"]))
         if args.per_kernel:
             print("    " + "  ".join(f"{n} {statistics.median(v):.1f}" for n, v in sorted(res[p]["cls"].items())))
     for e in engines:
