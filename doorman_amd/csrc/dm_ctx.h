@@ -797,6 +797,10 @@ struct dm_ctx {
   RootRound carried_round{};
   dm_ctx* carry_root = nullptr;
   int64_t rounds_in_tick = 0;
+  // Root side: the round stores a word of the root's rows and sums only where its bits differ
+  // from what the lane loaded there (dm_hier_round.h; HierArgs::store_all is its negation).
+  // DM_ROUND_STORES=0: every word, as before.
+  int round_stores = 1;
   // a stream part's auxiliary stream (part 0: the bin's class stream).  Part 1 beside
   // bins 4-6's stream 1: stream 2 or 0 run C1 at 40.6-40.8 us per tick, stream 3 at
   // 61.6-64.2 us (which hardware queues pair well: take_aux; profiles/r05_parts_ab.txt)

@@ -608,7 +608,7 @@ struct HierArgs {
   int G;                    // servers
   int K;                    // root rows per resource: G (replicated) or 1 (sharded: its owner's)
   int server;
-  int pad;
+  int store_all;            // DM_ROUND_STORES=0: the round stores every word it decides, changed or not
 };
 
 }  // namespace dm

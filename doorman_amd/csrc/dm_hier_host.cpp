@@ -224,6 +224,7 @@ static int root_round(dm_ctx* root, const void* gathered, int n_servers, int64_t
   ha.G = n_servers;
   ha.K = K;
   ha.server = server;
+  ha.store_all = root->round_stores ? 0 : 1;
   if (carry) {
     root->carried_round = RootRound{p, ha};
     root->carried = true;

@@ -2,7 +2,7 @@
 // (dm_hier.hip has the account of the round and of its layouts), in two steps so that a caller
 // can put loads of its own between them: hier_round_load issues every load the lane needs,
 // hier_round_decide consumes them (Clean, the K decisions in server order, the Assigns, the
-// root row and sums stores, this server's template).
+// root row and sums stores where a word's bits changed, this server's template).
 //
 // ONE: K = 1 fixed at compile time, one server (G = 1, so g = 0 and the record of resource r
 // is record 1 + r of block 0): a lane is a whole resource, the shuffles are identities, the
@@ -242,27 +242,47 @@ __device__ __forceinline__ void hier_round_decide(const DevParams& p, const Hier
 
   // the round's rows: the requests' leases, and the rows this round's Clean released
   const int64_t exp_new = rs_cfg.exp_out;
+  // The root store is written in place (out_* alias its columns, res its sums), so the words
+  // this lane loaded (ld, as loaded: not w / h / s, which Clean zeroed) are the words it would
+  // store over, and in a steady exchange most hold the round's result already.  A word is
+  // stored only where its bits differ (bits, not ==: a -0.0 in memory gives way to a computed
+  // +0.0, and a NaN equals itself); a word left alone stays clean in the cache, and the next
+  // kernel's boundary has that much less to write back.  The aliasing is tested here, once and
+  // uniformly, so that a caller without it stores everything; store_all (DM_ROUND_STORES=0)
+  // does so too.  Nothing is remembered across launches.
+  const bool keep = !ha.store_all && p.out_gets == p.has && p.out_wants == p.wants && p.out_sub == p.sub &&
+                    p.out_expiry == p.expiry && p.res == p.agg;
+  auto put_d = [&](double* at, double v, double had) {
+    if (!keep || __double_as_longlong(v) != __double_as_longlong(had)) *at = v;
+  };
   if (valid) {
-    if (req) {  // the root store is written in place (out_* alias its columns)
-      p.out_gets[row] = my_gets;
-      p.out_wants[row] = rw;
-      p.out_sub[row] = (int32_t)((uint32_t)rs | kSubExplicit);
-      p.out_expiry[row] = exp_new;
+    if (req) {
+      const int32_t sub_new = (int32_t)((uint32_t)rs | kSubExplicit);
+      put_d(p.out_gets + row, my_gets, ld.h);
+      put_d(p.out_wants + row, rw, ld.w);
+      if (!keep || sub_new != ld.raw) p.out_sub[row] = sub_new;
+      if (!keep || exp_new != ld.xe) p.out_expiry[row] = exp_new;
     } else if (expired) {
-      p.out_gets[row] = 0.0;
-      p.out_wants[row] = 0.0;
-      p.out_sub[row] = (int32_t)kSubReleased;
-      p.out_expiry[row] = kReleased;
+      put_d(p.out_gets + row, 0.0, ld.h);
+      put_d(p.out_wants + row, 0.0, ld.w);
+      if (!keep || (int32_t)kSubReleased != ld.raw) p.out_sub[row] = (int32_t)kSubReleased;
+      if (!keep || kReleased != ld.xe) p.out_expiry[row] = kReleased;
     }
   }
   if (valid && g0 == 0) {  // the resource's first lane
-    ResAgg a;
-    a.count = count;
-    a.sum_has = sh;
-    a.sum_wants = sw;
-    a.follow_exp = rs_cfg.follow_exp;
-    p.res[rr] = a;
-    p.expl[rr] = 1;  // the rows this tick writes carry explicit expiries
+    // (load_res zeroes the sums it returns under recompute: then they are not the memory's)
+    const bool same = keep && !p.recompute && count == rs_cfg.agg_count &&
+                      __double_as_longlong(sh) == __double_as_longlong(rs_cfg.agg_has) &&
+                      __double_as_longlong(sw) == __double_as_longlong(rs_cfg.agg_wants);
+    if (!same) {  // (follow_exp is copied through: it never differs)
+      ResAgg a;
+      a.count = count;
+      a.sum_has = sh;
+      a.sum_wants = sw;
+      a.follow_exp = rs_cfg.follow_exp;
+      p.res[rr] = a;
+    }
+    if (!keep || rs_cfg.xstate != 1) p.expl[rr] = 1;  // the rows this tick writes carry explicit expiries
   }
 
   // this server's new template for the resource (server.go:279-313)

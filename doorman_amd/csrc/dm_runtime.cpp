@@ -176,6 +176,7 @@ int dm_create(int device, dm_ctx** out) {
   if (const char* fu = getenv("DM_FUSED")) c->fused_ok = atoi(fu);
   if (const char* cb = getenv("DM_CYCLE_BYTES")) c->cycle_bytes = atoll(cb);
   if (const char* cr = getenv("DM_CARRY_ROUND")) c->carry_ok = atoi(cr) != 0;
+  if (const char* rs = getenv("DM_ROUND_STORES")) c->round_stores = atoi(rs) != 0;
   e = hipSuccess;
   // The auxiliary streams are created with a full CU mask, which gives each its own
   // hardware queue.  Plain streams share the process's GPU_MAX_HW_QUEUES (4) queues

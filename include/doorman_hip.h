@@ -561,7 +561,15 @@ int dm_hier_status(dm_ctx* root, uint32_t* status, int n_servers);
  * dm_config_load, the store updates, a plain dm_apportion, dm_set_stream, dm_set_profiling,
  * dm_destroy of either context among them).  A foreign stream that reads what the round
  * writes orders itself with dm_stream_wait, as it did.  DM_CARRY_ROUND=0 in the environment,
- * read when the context is created, launches every round behind its tick as before. */
+ * read when the context is created, launches every round behind its tick as before.
+ * The round's in-place stores: the root's rows and sums are written in place, and in a steady
+ * exchange most words already hold what the round decides.  The round (in either place it
+ * runs) stores a word of a root row (has, wants, subclients, expiry), a resource's running
+ * sums or its row-state byte only where the bits differ from what the same lane loaded from
+ * that address in the same launch; nothing is remembered from launch to launch, and the staged
+ * templates are always stored.  Every result is bit for bit what storing everything gave.
+ * DM_ROUND_STORES=0 in the environment, read when the root's context is created, stores
+ * every word as before. */
 int dm_hier_attach(dm_ctx* leaf, dm_ctx* root, int server, void* const* ring, int nring, void* gathered,
                    void* exchange_stream);
 int dm_hier_step(dm_ctx* leaf, dm_ctx* root, int64_t now_ns);
