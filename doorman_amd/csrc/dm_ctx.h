@@ -4,11 +4,11 @@
 // cross-stream order (StreamOrder, TickDone, TemplatePipe, QueueCalibration: they carry out
 // what dm_tick_order.h decides), the large-resource chain's owner (dm_large_chain.h), the
 // store updates' staging (dm_update_stage.h: UpdateStage, RowBitmap; what their flags mean:
-// dm_update_outcome.h), the entry macros of the C-ABI calls, and the functions that cross a
-// unit boundary.  The only definition of
-// dm_ctx; the units around it are dm_runtime.cpp (context life, streams, profiling),
-// dm_plan.cpp, dm_tick.cpp, dm_decide.cpp, dm_store.cpp, dm_store_update.cpp and
-// dm_hier_host.cpp.  See DESIGN.md §3-§5.
+// dm_update_outcome.h), the owner of a round of requests' buffers (dm_decide_round.h, sized
+// by dm_decide_plan.h's plan), the entry macros of the C-ABI calls, and the functions that
+// cross a unit boundary.  The only definition of dm_ctx; the units around it are
+// dm_runtime.cpp (context life, streams, profiling), dm_plan.cpp, dm_tick.cpp, dm_decide.cpp,
+// dm_store.cpp, dm_store_update.cpp and dm_hier_host.cpp.  See DESIGN.md §3-§5.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded when the first communicator is made
@@ -459,6 +459,7 @@ struct QueueCalibration {
 
 }  // namespace dm
 
+#include "dm_decide_round.h"
 #include "dm_large_chain.h"
 #include "dm_update_stage.h"
 
@@ -742,25 +743,9 @@ struct dm_ctx {
   int64_t cl_n = 0;
   // dm_store_load_device: the flags its kernels raise (dm_launch.h kLdBadSub, kLdNotOne, kLdGeneral)
   DBuf<uint32_t> ld_flags;
-  // dm_decide: a round's requests (grouped by resource), per-resource work items, results
-  DBuf<int64_t> rq_rows, rq_sub, rq_exp;
-  DBuf<double> rq_has, rq_wants, rq_gets;
-  DBuf<ReqItem> rq_items;
-  DBuf<double> rq_sc_has, rq_sc_wants;  // the round's working copy of the requested resources' rows
-  DBuf<int32_t> rq_sc_sub;
-  // dm_decide's fast path (dm_decide_fast.hip); DM_DECIDE_FAST=0 turns it off
-  bool decide_fast = true;
-  DBuf<FastItem> fd_items;
-  DBuf<FastRes> fd_res;
-  DBuf<int64_t> fd_prev, fd_bounds;
-  DBuf<double> fd_pw, fd_v, fd_keys, fd_keys_s, fd_ev_in, fd_ev;
-  DBuf<FdScan> fd_sc, fd_ps, fd_part;
-  DBuf<int32_t> fd_evs_in, fd_evs, fd_ecnt, fd_bdc;
-  DBuf<double2> fd_esum, fd_bds;
-  DBuf<FdClean> fd_pc;
-  DBuf<FdScan> fd_pt;
-  DBuf<FdLind> fd_ld;
-  DBuf<uint8_t> fd_tmp;
+  // dm_decide: a round's device buffers and the fast path's switch (dm_decide_round.h; the
+  // round's plan and every buffer's count: dm_decide_plan.h)
+  DecideRound round;
   // dm_publish_totals: the workgroups' validation flags and their arrival counter
   // (k_publish; both return to zero after each launch)
   DBuf<uint32_t> pub_sync;

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "dm_decide_plan.h"
 #include "dm_update_outcome.h"
 
 namespace dm {
@@ -486,12 +487,8 @@ __host__ __device__ inline void bin_shape(int bin, int bin4_wave, int bin6_wide,
   *R = bin == 3 ? 4 : bin == 4 ? (bin4_wave ? 16 : 8) : bin == 5 ? 8 : (bin6_wide ? 8 : 16);
 }
 
-struct ReqItem {
-  int32_t seg;
-  int32_t fast;  // 1 + its slot of the fast path (FastItem), 0: decided by k_decide only
-  int64_t qlo, qhi;
-  int64_t scr;
-};
+// dm_decide's round (dm_round.hip): the columns of its requests, grouped by resource; a
+// resource's work item is ReqItem (dm_decide_plan.h)
 struct ReqArgs {
   const int64_t* rows;  // the row the request's lease is written to (its client's row, or a free row)
   const double* has;    // Request.Has (read by Learn only)
@@ -514,23 +511,10 @@ struct ReqArgs {
 // a count / sum of the wants between deservedShare and T over the store as the earlier
 // Assigns left it (sorted wants + sorted per-block Assign events), and only
 // sumHas's recurrence (and ProportionalShare's sumWants test) stays sequential.
-constexpr int kFdMin = 64;       // requests on one resource before the fast path is tried
-constexpr int kFdBlock = 2048;   // requests per Assign-event block (2 events each)
-constexpr int kFdRows = 4096;    // rows per workgroup of the fast path's row passes
+// The work items (ReqItem, FastItem), the sizes the kernels are built for (kFdMin, kFdBlock,
+// kFdRows, kFdChunk) and the element count of every buffer below are the host's plan of the
+// round: dm_decide_plan.h, included above.  What remains here is what only the device fills.
 constexpr double kFdMaxAbs = 1e300;  // |wants| and |capacity| bound: no overflow in the sums
-constexpr int kFdChunk = 1024;   // scan elements per workgroup (4 per thread)
-struct FastItem {
-  int32_t item;  // index of the resource's ReqItem
-  int32_t nblk;  // event blocks: ceil(K / kFdBlock)
-  int64_t k0, K; // its requests [k0, k0 + K) of the round (grouped order)
-  int64_t m0;    // offset of its sorted-wants area (n + 1 entries)
-  int64_t e0;    // offset of its events (2 K)
-  int64_t b0;    // first event block (global block index)
-  int64_t n;     // rows of the resource
-  int64_t c0;    // first row chunk (kFdRows rows each; global chunk index)
-  int32_t nch;   // row chunks
-  int32_t repeats;  // 1: some row is requested twice (the grants then need the sequential recurrence)
-};
 struct FdScan {  // one scanned element: double-double sums and an integer count
   double xh, xl;  // FairShare: extra (sum of d - w for w < d); ProportionalShare: extraCapacity
   double yh, yl;  // ProportionalShare: extraNeed
@@ -561,9 +545,8 @@ struct FdLind {  // the available-capacity recurrence a' = max(a + c, 0) compose
   double ah, al;
   double bh, bl;
 };
-struct FastArgs {
-  const FastItem* fi;
-  FastRes* fr;
+struct FastArgs {  // (each buffer's element count: dm_decide_plan.h round_count)
+  FastRes* fr;          // [fast items]
   const int64_t* prev;  // [n requests] the previous request of the round on the same row, or -1
   double* pw;           // [n requests] the row's wants before the request
   double* v;            // [n requests] the request's grant before the avail cap (FS), or PS's round-1 grant

@@ -158,7 +158,7 @@ int dm_create(int device, dm_ctx** out) {
   // Test hooks: each forces one of two product paths that the
   // library chooses between by itself, so that a test can compare the two on the same
   // ticks.  No other environment switch exists (round 5 retired the A/B probes).
-  if (const char* df = getenv("DM_DECIDE_FAST")) c->decide_fast = atoi(df) != 0;
+  if (const char* df = getenv("DM_DECIDE_FAST")) c->round.fast = atoi(df) != 0;
   if (const char* sc = getenv("DM_SPEC_CHAIN")) c->chain.spec_chain = atoi(sc) != 0;
   if (const char* rl = getenv("DM_REDO_LIGHT")) c->chain.redo_light = atoi(rl);
   if (const char* qc = getenv("DM_QUEUE_CALIB")) {  // 0: keep the creation-order queue assignment; 2: log

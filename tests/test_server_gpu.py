@@ -577,3 +577,68 @@ def test_decide_100k_requests_on_a_100k_client_resource():
     np.testing.assert_array_equal(ef, es)
     ok = float_close(gf, gs, np.full(k, cap))
     assert ok.all(), np.flatnonzero(~ok)[:10]
+
+
+OWNER_SIZES = np.array([4097, 70, 65], dtype=np.int64)
+OWNER_KINDS = [W.FAIR_SHARE, W.FAIR_SHARE, W.PROPORTIONAL_SHARE]
+OWNER_S0 = [1, 3, 1]
+
+
+def _owner_rounds(rng, snap):
+    """Three rounds of refreshing clients on _fast_round_snapshot(OWNER_SIZES, ...), as
+    (rows, has, wants, sub) in the caller's order, the resources' requests interleaved:
+      1. 2049 distinct clients of resource 0 (two event blocks, the second with one request)
+         and 64 requests (the fast path's threshold) on resource 1, some rows twice;
+      2. ten requests over the three resources: no fast item;
+      3. every one of resource 0's 4097 rows once (two row chunks, three event blocks, five
+         scan chunks) and 130 requests on resource 2's 65 rows, some rows twice."""
+    so = snap["seg_off"]
+
+    def asks(r, local):
+        rr = so[r] + np.asarray(local, dtype=np.int64)
+        K, n = len(rr), OWNER_SIZES[r]
+        fresh = rng.uniform(0.0, 3.0, K) * snap["capacity"][r] / n * OWNER_S0[r]
+        w = np.where(rng.random(K) < 0.4, snap["wants"][rr], fresh)
+        t = rng.random(K) < 0.1
+        w[t] = np.round(w[t])
+        return rr, w, np.full(K, OWNER_S0[r], np.int64)
+
+    def mixed(parts):
+        rows, wants, sub = (np.concatenate(c) for c in zip(*parts))
+        order = rng.permutation(len(rows))
+        return rows[order], rng.uniform(0, 1, len(rows)), wants[order], sub[order]
+
+    return [
+        mixed([asks(0, rng.choice(4097, 2049, replace=False)), asks(1, rng.integers(0, 70, 64))]),
+        mixed([asks(0, [0, 2048, 4096, 17]), asks(1, [0, 69, 33]), asks(2, [64, 0, 64])]),
+        mixed([asks(0, rng.permutation(4097)), asks(2, rng.integers(0, 65, 130))]),
+    ]
+
+
+def test_decide_rounds_grow_shrink_and_reuse_their_buffers():
+    """One engine decides a large fast round, a round of ten requests without a fast item
+    (the fast path's buffers stay as the first round left them) and a larger fast round on
+    other resources (every buffer grows, the areas move): each round against the oracle's
+    literal replay, against an engine with DM_DECIDE_FAST=0 that decides the same rounds, and
+    for exact expiries.  dm_decide leaves the store as it is, so every round starts from the
+    loaded store."""
+    rng = np.random.default_rng(77)
+    snap = _fast_round_snapshot(rng, OWNER_SIZES, OWNER_KINDS, OWNER_S0)
+    rounds = _owner_rounds(rng, snap)
+    assert [len(r[0]) for r in rounds] == [2049 + 64, 10, 4097 + 130]
+    fast, slow = _decide_engine(True), _decide_engine(False)
+    try:
+        fast.load(snap)
+        slow.load(snap)
+        got = [(fast.decide(NOW, *r), slow.decide(NOW, *r)) for r in rounds]
+    finally:
+        fast.close()
+        slow.close()
+    cap_row = np.repeat(snap["capacity"], np.diff(snap["seg_off"]))
+    for i, ((rows, has, wants, sub), ((fg, fe), (sg, se))) in enumerate(zip(rounds, got)):
+        ref_g, ref_e = _oracle_round(snap, rows, has, wants, sub, NOW)
+        np.testing.assert_array_equal(fe, ref_e)
+        np.testing.assert_array_equal(se, ref_e)
+        for a, b, label in ((fg, ref_g, "fast"), (sg, ref_g, "one-workgroup replay"), (fg, sg, "fast against replay")):
+            ok = float_close(a, b, cap_row[rows])
+            assert ok.all(), (i, label, np.flatnonzero(~ok)[:8], a[~ok][:4], b[~ok][:4])
