@@ -150,6 +150,16 @@ _SIGS = {
                                   + [ctypes.c_void_p] * 3),
     "dm_read_leases_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    # store updates from device memory (every column pointer a device pointer; the batch struct is host memory)
+    "dm_store_upsert_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    "dm_store_update_wants_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "dm_store_update_wants_mask_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "dm_store_release_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "dm_store_apply_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "dm_store_apply_device_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "dm_store_refresh_wants_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                                     ctypes.POINTER(ctypes.c_int64)]),
     # round-oriented GetCapacity dispatch (dm_server.cpp)
     "dm_server_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.POINTER(ResourceCfg), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),

@@ -958,6 +958,8 @@ int update_bin4_shape(dm_ctx* c, hipStream_t st);
 int set_parts_ok(dm_ctx* c, bool ok);
 // dm_tick.cpp
 int ready(dm_ctx* c);
+// dm_store.cpp
+int check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what);
 // dm_store_update.cpp
 void async_drain(dm_ctx* c);
 int async_retire_all(dm_ctx* c);

@@ -139,6 +139,8 @@ hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_
                                     int64_t n_values, const double* wants, int64_t* block_sums, int32_t* word_pre,
                                     const StoreCols& s, uint32_t* flags, int phase, int64_t vlo, int64_t vhi,
                                     const KeyClear* kc, hipStream_t st);
+hipError_t launch_refresh_dense(int64_t n, int64_t first_row, const double* wants, const StoreCols& s, uint32_t* flags,
+                                unsigned long long* count, const KeyClear* kc, hipStream_t st);
 hipError_t launch_carry_reject(const uint32_t* from, uint32_t* to, hipStream_t st);
 // dm_hier.hip
 hipError_t launch_publish(int64_t R, const ResAgg* agg, void* dst, uint32_t* sync, hipStream_t st);

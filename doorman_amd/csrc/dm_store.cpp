@@ -334,10 +334,11 @@ int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants,
 
 // ---- the store from and into device memory (dm_load.hip) ----
 
-// A caller's device column, for the four calls below: p must be device memory of the
-// context's device, and where the runtime knows p's allocation, that allocation must hold
-// `bytes` bytes from p.  Asked of the runtime before any kernel or copy is given p.
-static int check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what) {
+// A caller's device column, for the four calls below and the device twins of the update
+// calls (dm_store_update.cpp): p must be device memory of the context's device, and where
+// the runtime knows p's allocation, that allocation must hold `bytes` bytes from p.  Asked
+// of the runtime before any kernel or copy is given p.
+int dm::check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what) {
   hipPointerAttribute_t at{};
   if (hipPointerGetAttributes(&at, p) != hipSuccess) {
     (void)hipGetLastError();  // (a pointer the runtime does not know: plain host memory on older runtimes)

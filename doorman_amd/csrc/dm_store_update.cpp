@@ -21,6 +21,55 @@ struct StageCol {
 };
 static constexpr int64_t kStageChunk = 1 << 22;  // rows per copy/validate step of a single call
 
+// Where a part's kernels read its columns: one parameter of row_part and mask_kernels (which
+// apply_enqueue makes from its `device` argument), so that the host calls and their device twins (dm_store_*_device) are one
+// sequence of launches.
+//   - staged (the host calls): set S's columns, which the copy stream fills; the context
+//     stream waits for each copy's event before the kernels that read it.
+//   - in place (the device twins): the caller's own device columns, read on the context
+//     stream where they lie.  No copy, no event, no column of S allocated: of S only the flags
+//     words, their mirror and the masked refresh's blk / wpre scratch are used.  The caller
+//     has ordered the columns' producer before the call, so every value is there: a single
+//     call's rows are one step, a refresh's values one chunk.
+struct UpdSrc {
+  bool in_place = false;
+  const uint64_t* mask = nullptr;  // a masked refresh: the mask and its packed values
+  const double* mwants = nullptr;
+  const int64_t *rows = nullptr, *rel = nullptr;  // row parts: an upsert's or refresh's rows, a release's
+  const double *has = nullptr, *wants = nullptr;  // (has, exp: nullptr for narrow arrivals)
+  const void* sub = nullptr;                      // int64, or int32 for narrow arrivals
+  const int64_t* exp = nullptr;
+};
+// The staged source of set S: a single call's columns (b == nullptr: every column it copies is
+// there), or batch b's, whose arrivals may be narrow.
+static UpdSrc staged(const UpdateStage& S, const dm_store_batch* b) {
+  UpdSrc u;
+  u.mask = S.mask.p, u.mwants = S.mwants.p;
+  u.rows = S.rows.p, u.rel = b ? S.rel.p : S.rows.p;
+  u.has = !b || b->upsert_has ? S.has.p : nullptr;
+  u.wants = S.wants.p, u.sub = S.sub.p;
+  u.exp = !b || b->upsert_expiry_ns ? S.exp.p : nullptr;
+  return u;
+}
+// The in-place source of batch b, every pointer the caller's.
+static UpdSrc in_place(const dm_store_batch* b) {
+  UpdSrc u;
+  u.in_place = true;
+  u.mask = b->wants_mask, u.mwants = b->wants;
+  u.rows = b->upsert_rows, u.rel = b->release_rows;
+  u.has = b->upsert_has, u.wants = b->upsert_wants;
+  u.sub = b->upsert_subclients32 ? (const void*)b->upsert_subclients32 : b->upsert_subclients;
+  u.exp = b->upsert_expiry_ns;
+  return u;
+}
+// A caller's device column of `bytes` bytes, when given: dm_ctx.h check_device_ptr, before
+// any kernel is given it.
+#define DM_DEVICE_COL(ctx, p, bytes, what)                                       \
+  do {                                                                           \
+    if (p)                                                                       \
+      if (int _rc = check_device_ptr(ctx, p, (size_t)(bytes), what)) return _rc; \
+  } while (0)
+
 // How a call that dm_keep_keys may keep ends (dm_row_epoch.h): a wants refresh, and with
 // DM_KEEP_UPDATES a release, an upsert or a synchronous batch.  Where the mode does not cover
 // the call (an asynchronous batch never is) it starts a row epoch before it launches, as every
@@ -65,32 +114,34 @@ static int copy_cols(dm_ctx* c, const StageCol* cols, int ncols, int64_t off, in
 }
 
 // A part that names rows (an upsert, a row refresh, a release; alone or in a batch), its
-// columns staged in S: the device sequence on the context stream.  Its rows in range and unique
+// columns at src (staged in S, or the caller's in place): the device sequence on the context stream.  Its rows in range and unique
 // (a bitmap over the table, O(n + N/64)) once they have landed, the rejection of the part
 // before carried into its word, the apply kernel (which finds each row's resource, and returns
 // at once from a rejected word), the bitmap cleared again.  cols: a single call's host columns,
 // copied here chunk by chunk; b: a batch, whose part is already on its way and whose arrivals
 // may be narrow (subclients of 4 B, no has: 0, no expiry: now + the resource's lease length).
-static int row_part(dm_ctx* c, UpdateStage& S, const WriteEnd& we, UpdPart part, int64_t n, const StageCol* cols,
-                    int ncols, const dm_store_batch* b) {
+static int row_part(dm_ctx* c, UpdateStage& S, const UpdSrc& src, const WriteEnd& we, UpdPart part, int64_t n,
+                    const StageCol* cols, int ncols, const dm_store_batch* b) {
   hipStream_t st = c->stream;
   const int word = flags_word(part);
   uint32_t* F = S.flag(word);
-  const int64_t* rows = part == UpdPart::batch_release ? S.rel.p : S.rows.p;
-  const double* wants = writes_wants(part) ? S.wants.p : nullptr;
+  const int64_t* rows = writes_wants(part) ? src.rows : src.rel;
+  const double* wants = writes_wants(part) ? src.wants : nullptr;
   const bool sub32 = b && b->upsert_subclients32;
-  const int64_t* sub = writes_subclients(part) && !sub32 ? S.sub.p : nullptr;
-  const int32_t* s32 = writes_subclients(part) && sub32 ? (const int32_t*)S.sub.p : nullptr;
-  const int64_t step = b ? n : kStageChunk;
+  const int64_t* sub = writes_subclients(part) && !sub32 ? (const int64_t*)src.sub : nullptr;
+  const int32_t* s32 = writes_subclients(part) && sub32 ? (const int32_t*)src.sub : nullptr;
+  const int64_t step = b || src.in_place ? n : kStageChunk;
   int k = 0;
   for (int64_t off = 0; off < n; off += step, ++k) {
     const int64_t m = std::min(step, n - off);
-    hipEvent_t ev = S.ev_bat[b ? word : k & 1];
-    if (!b) {
-      if (int rc = copy_cols(c, cols, ncols, off, m)) return rc;
-      DM_HIP(c, hipEventRecord(ev, c->cpy), "stage update");
+    if (!src.in_place) {
+      hipEvent_t ev = S.ev_bat[b ? word : k & 1];
+      if (!b) {
+        if (int rc = copy_cols(c, cols, ncols, off, m)) return rc;
+        DM_HIP(c, hipEventRecord(ev, c->cpy), "stage update");
+      }
+      DM_HIP(c, hipStreamWaitEvent(st, ev, 0), "stage update");
     }
-    DM_HIP(c, hipStreamWaitEvent(st, ev, 0), "stage update");
     DM_HIP(c, launch_check_rows(m, rows + off, c->N, c->row_bits.bits.p, wants ? wants + off : nullptr,
                                 sub ? sub + off : nullptr, s32 ? s32 + off : nullptr, F, st),
            "check rows");
@@ -102,8 +153,7 @@ static int row_part(dm_ctx* c, UpdateStage& S, const WriteEnd& we, UpdPart part,
   else if (!writes_subclients(part))
     DM_HIP(c, launch_update_wants(n, rows, wants, sc, F, we.keys(), st), "update wants");
   else
-    DM_HIP(c, launch_upsert(n, rows, !b || b->upsert_has ? S.has.p : nullptr, wants, sub, s32,
-                            !b || b->upsert_expiry_ns ? S.exp.p : nullptr, b ? b->upsert_now_ns : 0, sc, F, c->dense_upd(),
+    DM_HIP(c, launch_upsert(n, rows, src.has, wants, sub, s32, src.exp, b ? b->upsert_now_ns : 0, sc, F, c->dense_upd(),
                             we.keys(), st),
            "upsert");
   DM_HIP(c, launch_clear_rows(n, rows, c->N, c->row_bits.bits.p, st), "clear rows");
@@ -129,14 +179,15 @@ static int mask_copies(dm_ctx* c, UpdateStage& S, int64_t nwords, const uint64_t
   return DM_OK;
 }
 
-static int mask_kernels(dm_ctx* c, UpdateStage& S, int64_t first_row, int64_t nwords, int64_t n, uint32_t* flags,
-                        int nchunk, const KeyClear* kc) {
+// (In place: mask and values are there, so nchunk is 0 and no event is waited for.)
+static int mask_kernels(dm_ctx* c, UpdateStage& S, const UpdSrc& src, int64_t first_row, int64_t nwords, int64_t n,
+                        uint32_t* flags, int nchunk, const KeyClear* kc) {
   hipStream_t st = c->stream;
   auto launch = [&](int phase, int64_t v0, int64_t v1) {
-    return launch_update_wants_mask(nwords, S.mask.p, first_row, c->N, n, S.mwants.p, S.blk.p, S.wpre.p, c->store_cols(),
+    return launch_update_wants_mask(nwords, src.mask, first_row, c->N, n, src.mwants, S.blk.p, S.wpre.p, c->store_cols(),
                                     flags, phase, v0, v1, kc, st);
   };
-  DM_HIP(c, hipStreamWaitEvent(st, S.ev_bat[0], 0), "stage update");
+  if (!src.in_place) DM_HIP(c, hipStreamWaitEvent(st, S.ev_bat[0], 0), "stage update");
   DM_HIP(c, launch(nchunk ? 0 : 2, 0, INT64_MAX), "masked update");
   for (int k = 0; k < nchunk; ++k) {
     const int64_t v0 = n * k / nchunk, v1 = n * (k + 1) / nchunk;
@@ -161,10 +212,12 @@ static int single_end(dm_ctx* c, UpdateStage& S, UpdPart part, WriteEnd& we, int
 }
 
 // A single call that names rows: bitmap and flags word ready, the part, the end.
-static int single_rows(dm_ctx* c, UpdateStage& S, WriteEnd& we, UpdPart part, int64_t n, const StageCol* cols, int ncols) {
+// (src: staged(S), whose columns `cols` fill; or the caller's in place, and no cols.)
+static int single_rows(dm_ctx* c, UpdateStage& S, const UpdSrc& src, WriteEnd& we, UpdPart part, int64_t n,
+                       const StageCol* cols, int ncols) {
   DM_HIP(c, c->row_bits.ensure(c->N, c->stream), "row bitmap");
   DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
-  if (int rc = row_part(c, S, we, part, n, cols, ncols, nullptr)) return rc;
+  if (int rc = row_part(c, S, src, we, part, n, cols, ncols, nullptr)) return rc;
   return single_end(c, S, part, we, n);
 }
 
@@ -180,7 +233,7 @@ int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has
   UpdateStage& S = c->stage[0];
   DM_HIP(c, S.ensure_upsert(n), "stage upsert");
   const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}, {S.sub.p, sub, 8}, {S.has.p, has, 8}, {S.exp.p, exp, 8}};
-  return single_rows(c, S, we, UpdPart::upsert, n, cols, 5);
+  return single_rows(c, S, staged(S, nullptr), we, UpdPart::upsert, n, cols, 5);
 }
 
 int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
@@ -193,7 +246,7 @@ int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const doubl
   UpdateStage& S = c->stage[0];
   DM_HIP(c, S.ensure_each(n, S.rows, S.wants), "stage refresh");
   const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}};
-  return single_rows(c, S, re, UpdPart::refresh, n, cols, 2);
+  return single_rows(c, S, staged(S, nullptr), re, UpdPart::refresh, n, cols, 2);
 }
 
 // The same narrow Assign with the rows as a bit mask (one bit per row of
@@ -213,7 +266,7 @@ int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, con
   DM_HIP(c, S.ensure_mask(nwords, n), "stage mask");
   DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
   if (int rc = mask_copies(c, S, nwords, mask, n, wants, 0)) return rc;
-  if (int rc = mask_kernels(c, S, first_row, nwords, n, S.flag(0), 0, re.keys())) return rc;
+  if (int rc = mask_kernels(c, S, staged(S, nullptr), first_row, nwords, n, S.flag(0), 0, re.keys())) return rc;
   return single_end(c, S, UpdPart::refresh_mask, re, n);
 }
 
@@ -227,7 +280,115 @@ int dm_store_release(dm_ctx* c, int64_t n, const int64_t* rows) {
   UpdateStage& S = c->stage[0];
   DM_HIP(c, S.rows.ensure((size_t)n), "stage rows");
   const StageCol cols[] = {{S.rows.p, rows, 8}};
-  return single_rows(c, S, we, UpdPart::release, n, cols, 1);
+  return single_rows(c, S, staged(S, nullptr), we, UpdPart::release, n, cols, 1);
+}
+
+// ---- the single calls on device columns (dm_store_*_device) ----
+// The argument checks, messages and WriteEnd kinds are the host twins'; then the pointer
+// checks; then the twin's kernels with the caller's pointers (UpdSrc in place).
+
+int dm_store_upsert_device(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                           const int64_t* sub, const int64_t* exp) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  if (n < 0 || (n > 0 && (!rows || !has || !wants || !sub || !exp))) return c->fail(DM_E_INVAL, "bad upsert");
+  if (n == 0) return DM_OK;
+  DM_DEVICE_COL(c, rows, n * 8, "rows");
+  DM_DEVICE_COL(c, has, n * 8, "has");
+  DM_DEVICE_COL(c, wants, n * 8, "wants");
+  DM_DEVICE_COL(c, sub, n * 8, "subclients");
+  DM_DEVICE_COL(c, exp, n * 8, "expiry_ns");
+  c->expl_rows = true;  // (kept or not: the rows take explicit expiries)
+  WriteEnd we(c, RowWrite::upsert);
+  UpdSrc src;
+  src.in_place = true;
+  src.rows = rows, src.has = has, src.wants = wants, src.sub = sub, src.exp = exp;
+  return single_rows(c, c->stage[0], src, we, UpdPart::upsert, n, nullptr, 0);
+}
+
+int dm_store_update_wants_device(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  if (n < 0 || (n > 0 && (!rows || !wants))) return c->fail(DM_E_INVAL, "bad update");
+  if (n == 0) return DM_OK;
+  DM_DEVICE_COL(c, rows, n * 8, "rows");
+  DM_DEVICE_COL(c, wants, n * 8, "wants");
+  WriteEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
+  UpdSrc src;
+  src.in_place = true;
+  src.rows = rows, src.wants = wants;
+  return single_rows(c, c->stage[0], src, re, UpdPart::refresh, n, nullptr, 0);
+}
+
+int dm_store_update_wants_mask_device(dm_ctx* c, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n,
+                                      const double* wants) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  if (first_row < 0 || (first_row & 63) || nwords < 0 || n < 0 || (nwords > 0 && !mask) || (n > 0 && !wants))
+    return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
+  if (nwords == 0) return n == 0 ? DM_OK : c->fail(DM_E_INVAL, "packed values without a mask");
+  if (first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
+  DM_DEVICE_COL(c, mask, nwords * 8, "mask");
+  if (n > 0) DM_DEVICE_COL(c, wants, n * 8, "wants");
+  WriteEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
+  UpdateStage& S = c->stage[0];
+  DM_HIP(c, S.ensure_scan(nwords), "mask scratch");
+  DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
+  UpdSrc src;
+  src.in_place = true;
+  src.mask = mask, src.mwants = wants;
+  if (int rc = mask_kernels(c, S, src, first_row, nwords, n, S.flag(0), 0, re.keys())) return rc;
+  return single_end(c, S, UpdPart::refresh_mask, re, n);
+}
+
+int dm_store_release_device(dm_ctx* c, int64_t n, const int64_t* rows) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad release");
+  if (n == 0) return DM_OK;
+  DM_DEVICE_COL(c, rows, n * 8, "rows");
+  WriteEnd we(c, RowWrite::release);
+  UpdSrc src;
+  src.in_place = true;
+  src.rel = rows;
+  return single_rows(c, c->stage[0], src, we, UpdPart::release, n, nullptr, 0);
+}
+
+// A wants refresh from a dense device column: wants[i] is the new wants of row first_row + i.
+// One kernel (k_refresh_dense, dm_update.hip) finds the rows that are not released and whose
+// bits differ from the stored wants, and applies exactly those as dm_store_update_wants_mask
+// would for that mask: no mask, no packed values, no count or scan pass.  It ends as a masked
+// refresh does (RowWrite::refresh_mask, UpdPart::refresh_mask for its flags word: only kUpdNaN
+// can be set, the range was checked here).  Over PCIe: the flags word and the 8-B count.
+int dm_store_refresh_wants_device(dm_ctx* c, int64_t first_row, int64_t n, const double* wants, int64_t* n_changed) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+  if (first_row < 0 || (first_row & 63) || n < 0 || (n > 0 && !wants))
+    return c->fail(DM_E_INVAL, "bad dense refresh (first_row must be a multiple of 64)");
+  if (first_row > c->N || n > c->N - first_row) return c->fail(DM_E_RANGE, "rows past the store's end");
+  if (n_changed) *n_changed = 0;
+  if (n == 0) return DM_OK;
+  DM_DEVICE_COL(c, wants, n * 8, "wants");
+  WriteEnd re(c, RowWrite::refresh_mask);  // a changed NaN wants ends a resource's dense state
+  UpdateStage& S = c->stage[0];
+  DM_HIP(c, S.reset_flags(kFlagWords, c->stream), "update flags");
+  DM_HIP(c, launch_refresh_dense(n, first_row, wants, c->store_cols(), S.flag(0), S.count(), re.keys(), c->stream),
+         "dense refresh");
+  DM_HIP(c, S.fetch_flags(kFlagWords, c->stream), "update flags");
+  if (int rs = c->synced("update")) return rs;
+  const uint32_t f = S.h_flags.p[0];
+  int64_t changed = 0;
+  memcpy(&changed, S.h_flags.p + kCountWord, sizeof changed);
+  update_values(UpdPart::refresh_mask, f, c->maybe_general, c->all_sub_one);
+  re.end(false, f & kUpdNaN, changed);
+  c->have_result = false;
+  if (n_changed) *n_changed = changed;
+  return DM_OK;
 }
 
 // One round of updates: every part's columns cross PCIe back to back on the copy
@@ -259,10 +420,32 @@ static int batch_args(dm_ctx* c, const dm_store_batch* b) {
   return DM_OK;
 }
 
+// A device batch's columns (the struct itself is host memory): every pointer a part reads
+// passes check_device_ptr with the part's bytes before any kernel is given it.
+static int batch_device_ptrs(dm_ctx* c, const dm_store_batch* b) {
+  const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
+  if (nw > 0) DM_DEVICE_COL(c, b->wants_mask, nw * 8, "wants_mask");
+  if (nw > 0 && nm > 0) DM_DEVICE_COL(c, b->wants, nm * 8, "wants");
+  if (nr > 0) DM_DEVICE_COL(c, b->release_rows, nr * 8, "release_rows");
+  if (nu > 0) {
+    DM_DEVICE_COL(c, b->upsert_rows, nu * 8, "upsert_rows");
+    DM_DEVICE_COL(c, b->upsert_has, nu * 8, "upsert_has");
+    DM_DEVICE_COL(c, b->upsert_wants, nu * 8, "upsert_wants");
+    if (b->upsert_subclients32)
+      DM_DEVICE_COL(c, b->upsert_subclients32, nu * 4, "upsert_subclients32");
+    else
+      DM_DEVICE_COL(c, b->upsert_subclients, nu * 8, "upsert_subclients");
+    DM_DEVICE_COL(c, b->upsert_expiry_ns, nu * 8, "upsert_expiry_ns");
+  }
+  return DM_OK;
+}
+
 // The batch's copies (copy stream), its three parts' kernels (context stream) and the
 // flags' copy back into S.h_flags; nothing waits for them here.  we: the call's end (its
-// key-clearing builds, and the row epoch it has started or will decide on).
-static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, UpdateStage& S, const WriteEnd& we) {
+// key-clearing builds, and the row epoch it has started or will decide on).  device: the batch's
+// columns are device memory, read in place (no copies); else they are staged in S, and the
+// kernels' source is taken from S once its columns are allocated (ensure_* may move them).
+static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, UpdateStage& S, bool device, const WriteEnd& we) {
   const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
   const bool sub32 = b->upsert_subclients32 != nullptr;
   if (nu > 0) c->expl_rows = true;  // arrivals take explicit expiries
@@ -274,19 +457,22 @@ static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, UpdateStage& S, con
   // that the synchronous call's apply overlaps its own copies; an asynchronous batch's
   // apply overlaps the next batch's copies anyway, and one copy costs less than four
   // (C4 2.95 -> 2.91 ms per step, alternated: tools/archive/gpu_r6_c4chunk.sh)
-  const int nchunk = we.w == RowWrite::apply_async ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(kWChunks, nm >> 21));
+  const int nchunk = device                          ? 0
+                     : we.w == RowWrite::apply_async ? 1
+                                                     : (int)std::max<int64_t>(1, std::min<int64_t>(kWChunks, nm >> 21));
   // copies, back to back
-  if (nw > 0) {
+  if (nw > 0 && device) DM_HIP(c, S.ensure_scan(nw), "mask scratch");
+  if (nw > 0 && !device) {
     DM_HIP(c, S.ensure_mask(nw, nm), "stage mask");
     if (int rc = mask_copies(c, S, nw, b->wants_mask, nm, b->wants, nchunk)) return rc;
   }
-  if (nr > 0) {
+  if (nr > 0 && !device) {
     DM_HIP(c, S.rel.ensure((size_t)nr), "stage release rows");
     const StageCol col{S.rel.p, b->release_rows, 8};
     if (int rc = copy_cols(c, &col, 1, 0, nr)) return rc;
     DM_HIP(c, hipEventRecord(S.ev_bat[1], c->cpy), "stage update");
   }
-  if (nu > 0) {
+  if (nu > 0 && !device) {
     DM_HIP(c, S.ensure_upsert(nu), "stage upsert");
     const StageCol cols[] = {{S.rows.p, b->upsert_rows, 8},
                              {S.wants.p, b->upsert_wants, 8},
@@ -296,18 +482,19 @@ static int apply_enqueue(dm_ctx* c, const dm_store_batch* b, UpdateStage& S, con
     if (int rc = copy_cols(c, cols, 5, 0, nu)) return rc;
     DM_HIP(c, hipEventRecord(S.ev_bat[2], c->cpy), "stage update");
   }
+  const UpdSrc src = device ? in_place(b) : staged(S, b);
   // part 1: wants refresh (validated by its count/scan passes over the mask)
   if (nw > 0)
-    if (int rc = mask_kernels(c, S, b->wants_first_row, nw, nm, S.flag(0), nchunk, we.keys())) return rc;
+    if (int rc = mask_kernels(c, S, src, b->wants_first_row, nw, nm, S.flag(0), nchunk, we.keys())) return rc;
   // part 2: departures
   if (nr > 0) {
-    if (int rc = row_part(c, S, we, UpdPart::batch_release, nr, nullptr, 0, b)) return rc;
+    if (int rc = row_part(c, S, src, we, UpdPart::batch_release, nr, nullptr, 0, b)) return rc;
   } else {
     DM_HIP(c, launch_carry_reject(S.flag(0), S.flag(1), st), "carry");
   }
   // part 3: arrivals / full refreshes
   if (nu > 0)
-    if (int rc = row_part(c, S, we, UpdPart::batch_upsert, nu, nullptr, 0, b)) return rc;
+    if (int rc = row_part(c, S, src, we, UpdPart::batch_upsert, nu, nullptr, 0, b)) return rc;
   DM_HIP(c, S.fetch_flags(3, st), "batch flags");
   c->have_result = false;
   return DM_OK;
@@ -320,19 +507,25 @@ static int apply_check(dm_ctx* c, const UpdateStage& S, bool late) {
   return o.code != DM_OK ? c->fail(o.code, o.msg) : DM_OK;
 }
 
-int dm_store_apply(dm_ctx* c, const dm_store_batch* b) {
+// The synchronous batch, host (dm_store_apply) or device columns (dm_store_apply_device).
+static int apply_sync(dm_ctx* c, const dm_store_batch* b, bool device) {
   DM_ENTER(c);
   DM_STORE_OK(c);
   if (int rc = batch_args(c, b)) return rc;
+  if (device)
+    if (int rc = batch_device_ptrs(c, b)) return rc;
   if (b->wants_nwords == 0 && b->release_n == 0 && b->upsert_n == 0) return DM_OK;
   UpdateStage& S = c->stage[0];
   WriteEnd we(c, RowWrite::apply);
-  if (int rc = apply_enqueue(c, b, S, we)) return rc;
+  if (int rc = apply_enqueue(c, b, S, device, we)) return rc;
   if (int rs = c->synced("batch")) return rs;
   if (int rc = apply_check(c, S, false)) return rc;  // (a rejected part: a row epoch, ~WriteEnd)
   we.end(false, (S.h_flags.p[0] | S.h_flags.p[2]) & kUpdNaN, b->wants_n + b->release_n + b->upsert_n);
   return DM_OK;
 }
+
+int dm_store_apply(dm_ctx* c, const dm_store_batch* b) { return apply_sync(c, b, false); }
+int dm_store_apply_device(dm_ctx* c, const dm_store_batch* b) { return apply_sync(c, b, true); }
 
 // Retire asynchronous set S: wait for its batch, then its flags.
 static int async_retire(dm_ctx* c, UpdateStage& S) {
@@ -343,10 +536,13 @@ static int async_retire(dm_ctx* c, UpdateStage& S) {
   return apply_check(c, S, true);
 }
 
-int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) {
+// The asynchronous batch, host or device columns: one sequence and the same sets for both.
+static int apply_async(dm_ctx* c, const dm_store_batch* b, bool device) {
   DM_ENTER(c);
   DM_STORE_OK(c);
   if (int rc = batch_args(c, b)) return rc;
+  if (device)
+    if (int rc = batch_device_ptrs(c, b)) return rc;
   if (b->wants_nwords == 0 && b->release_n == 0 && b->upsert_n == 0) return DM_OK;
   UpdateStage& S = c->stage[1 + (int)(c->async_seq % kAsyncSets)];
   // the set's previous batch (kAsyncSets batches back) first: its flags, and its
@@ -357,12 +553,15 @@ int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) {
   // (wants refreshes too start a row epoch: a NaN wants ends a resource's dense state, and
   // the batch's flags are read two batches later)
   WriteEnd we(c, RowWrite::apply_async);
-  if (int rc = apply_enqueue(c, b, S, we)) return rc;
+  if (int rc = apply_enqueue(c, b, S, device, we)) return rc;
   DM_HIP(c, hipEventRecord(S.ev_done, c->stream), "batch done");
   S.pending = true;
   c->async_seq += 1;
   return DM_OK;
 }
+
+int dm_store_apply_async(dm_ctx* c, const dm_store_batch* b) { return apply_async(c, b, false); }
+int dm_store_apply_device_async(dm_ctx* c, const dm_store_batch* b) { return apply_async(c, b, true); }
 
 // Every set is retired (the flags of sets after a rejected one still count); the first
 // failure and its message are returned.

@@ -240,6 +240,42 @@ __global__ __launch_bounds__(256) void k_mask_apply_keys(int64_t nwords, const u
 #include "dm_mask_apply.inc"
 }
 
+// ---- a wants refresh from a dense column (dm_store_refresh_wants_device) ----
+// wants[i] is the new wants of row first_row + i (first_row a multiple of 64, checked with
+// the range on the host; n any value).  The kernel acts as k_mask_apply would for the mask of
+// the rows that are not released and whose new value differs from the stored one as 64-bit
+// patterns, without that mask ever existing: k_mask_apply's shape (one lane per row,
+// kMaskWords 64-row runs a wave, four waves a workgroup), every new and stored value loaded
+// before the first use, and a run's changed mask is the wave's ballot -- so no count pass, no
+// scan and no packed-value index.  The subclients word is loaded only by the lanes whose bits
+// differ (the released test: the released mark, or an explicit row whose expiry is DM_RELEASED,
+// which a load leaves until the first tick marks it); a run whose ballot is empty does nothing
+// more; unchanged rows are not stored.  Deltas leave as k_mask_apply's do (`cur` / `acc`, wave_seg_add for a run
+// that spans resources), so a resource none of whose rows changed sees no atomic and, in the
+// key-clearing build, no key store: every flush there follows a changed row, and clears.
+// kUpdNaN (a changed value that is NaN) and the count of rows written are reduced per wave
+// and per workgroup: one atomic per workgroup on each word at most.
+// About 16 B per row read, 8 B more per differing row, 8 B per changed row written.
+__global__ __launch_bounds__(256) void k_refresh_dense(int64_t n, int64_t first_row,
+                                                       const double* __restrict__ wants, RowIndex ix,
+                                                       const int32_t* __restrict__ s_sub,
+                                                       const int64_t* __restrict__ s_exp, double* s_wants,
+                                                       ResAgg* agg, uint32_t* flags, unsigned long long* count) {
+  constexpr bool kKeys = false;
+  const KeyClear kc{};
+#include "dm_refresh_dense.inc"
+}
+
+__global__ __launch_bounds__(256) void k_refresh_dense_keys(int64_t n, int64_t first_row,
+                                                            const double* __restrict__ wants, RowIndex ix,
+                                                            const int32_t* __restrict__ s_sub,
+                                                            const int64_t* __restrict__ s_exp, double* s_wants,
+                                                            ResAgg* agg, uint32_t* flags, unsigned long long* count,
+                                                            KeyClear kc) {
+  constexpr bool kKeys = true;
+#include "dm_refresh_dense.inc"
+}
+
 // dm_store_apply: a part is applied only if no earlier part was rejected.
 __global__ void k_carry_reject(const uint32_t* __restrict__ from, uint32_t* to) { *to |= *from & kUpdReject; }
 
@@ -361,6 +397,19 @@ hipError_t launch_update_wants_mask(int64_t nwords, const uint64_t* mask, int64_
       k_mask_apply<<<grid, 256, 0, st>>>(nwords, mask, first_row, block_sums, word_pre, wants, s.ix, s.sub, s.wants, s.agg,
                                          flags, vlo, vhi);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_refresh_dense(int64_t n, int64_t first_row, const double* wants, const StoreCols& s, uint32_t* flags,
+                                unsigned long long* count, const KeyClear* kc, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int64_t waves = (((n + 63) >> 6) + kMaskWords - 1) / kMaskWords;
+  const unsigned grid = (unsigned)((waves + 3) / 4);
+  if (kc)
+    k_refresh_dense_keys<<<grid, 256, 0, st>>>(n, first_row, wants, s.ix, s.sub, s.expiry, s.wants, s.agg, flags, count,
+                                               *kc);
+  else
+    k_refresh_dense<<<grid, 256, 0, st>>>(n, first_row, wants, s.ix, s.sub, s.expiry, s.wants, s.agg, flags, count);
   return hipGetLastError();
 }
 

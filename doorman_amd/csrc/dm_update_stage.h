@@ -9,6 +9,10 @@ namespace dm {
 
 constexpr int kWChunks = 4;    // dm_store_apply: the refresh values' copy chunks
 constexpr int kAsyncSets = 2;  // asynchronous batches in flight at most
+// A set's flags words: one per part of a batch (words 0-2), and behind them the 8-B count of
+// rows a dense refresh wrote (dm_store_refresh_wants_device; words kCountWord and the next,
+// 8-B aligned), which only that call clears and fetches.
+constexpr int kFlagWords = 6, kCountWord = 4;
 
 // One set of staging.  A context has 1 + kAsyncSets (dm_ctx::stage):
 //   - set 0 serves every call that is synchronous on return: the single updates, the
@@ -54,17 +58,23 @@ struct UpdateStage {
     if (e == hipSuccess) e = blk.ensure((size_t)((nwords + 255) / 256));
     return e == hipSuccess ? mwants.ensure((size_t)std::max<int64_t>(n_values, 1)) : e;
   }
+  // A masked refresh of device columns: the count pass' scratch alone, no column.
+  hipError_t ensure_scan(int64_t nwords) {
+    const hipError_t e = wpre.ensure((size_t)nwords);
+    return e == hipSuccess ? blk.ensure((size_t)((nwords + 255) / 256)) : e;
+  }
   // The first `words` flags words cleared on stream st (the first call allocates them and
   // the mirror); flag(k): the device address of part k's word.
   hipError_t reset_flags(int words, hipStream_t st) {
     hipError_t e = hipSuccess;
     if (!flags.p) {
-      e = flags.ensure(3);
-      if (e == hipSuccess) e = h_flags.alloc(3, hipHostMallocDefault);
+      e = flags.ensure(kFlagWords);
+      if (e == hipSuccess) e = h_flags.alloc(kFlagWords, hipHostMallocDefault);
     }
     return e == hipSuccess ? hipMemsetAsync(flags.p, 0, words * sizeof(uint32_t), st) : e;
   }
   uint32_t* flag(int k) const { return flags.p + k; }
+  unsigned long long* count() const { return reinterpret_cast<unsigned long long*>(flags.p + kCountWord); }
   hipError_t fetch_flags(int words, hipStream_t st) {
     return hipMemcpyAsync(h_flags.p, flags.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
   }

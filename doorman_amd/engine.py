@@ -383,6 +383,126 @@ class Engine:
         st.update(agg_count=sums["count"], agg_sum_has=sums["sum_has"], agg_sum_wants=sums["sum_wants"])
         other.load_store_device(st)
 
+    # -- store updates from device memory (no column over PCIe) --
+    def _device_cols(self, *cols):
+        """Update columns in device memory, checked without a context or a library call, by
+        load_store_device's rules: cols are (name, column, dtype or tuple of dtypes); each
+        column a CUDA tensor of torch (or any object with data_ptr(), dtype, device and a
+        length) on this engine's device, of (one of) its dtype(s), one contiguous dimension,
+        and all of one length.  Returns that length (0 without columns)."""
+        import torch
+        want = torch.device("cuda", self.device)
+        n = None
+        for name, t, dts in cols:
+            dts = (dts,) if isinstance(dts, str) else dts
+            if not hasattr(t, "data_ptr") or not hasattr(t, "device"):
+                raise ValueError(f"{name} must be a tensor on {want} (data_ptr(), dtype, device and a length)")
+            dev = torch.device(t.device)
+            if dev.type != "cuda":
+                raise ValueError(f"{name} is on {dev}: a device update's columns live on {want}")
+            if dev.index is not None and dev.index != self.device:
+                raise ValueError(f"{name} is on {dev}, the engine on {want}")
+            if str(t.dtype).replace("torch.", "") not in dts:
+                raise ValueError(f"{name} must be {' or '.join(dts)}, not {t.dtype}")
+            if getattr(t, "ndim", 1) != 1 or (hasattr(t, "is_contiguous") and not t.is_contiguous()):
+                raise ValueError(f"{name} must be one contiguous column")
+            if n is None:
+                n = len(t)
+            elif len(t) != n:
+                raise ValueError(f"{name} has {len(t)} entries, {cols[0][0]} has {n}")
+        return n or 0
+
+    def upsert_device(self, rows, has, wants, subclients, expiry_ns):
+        """dm_store_upsert_device: upsert from columns in this device's memory (torch CUDA
+        tensors: rows, subclients, expiry_ns int64; has, wants float64), read where they lie."""
+        n = self._device_cols(("rows", rows, "int64"), ("has", has, "float64"), ("wants", wants, "float64"),
+                              ("subclients", subclients, "int64"), ("expiry_ns", expiry_ns, "int64"))
+        self._torch_ready()
+        self._chk(self._L.dm_store_upsert_device(self._ctx, n, *[t.data_ptr() or None for t in
+                                                                 (rows, has, wants, subclients, expiry_ns)]))
+
+    def update_wants_device(self, rows, wants):
+        """dm_store_update_wants_device: update_wants from device columns."""
+        n = self._device_cols(("rows", rows, "int64"), ("wants", wants, "float64"))
+        self._torch_ready()
+        self._chk(self._L.dm_store_update_wants_device(self._ctx, n, rows.data_ptr() or None, wants.data_ptr() or None))
+
+    def update_wants_mask_device(self, mask, wants, first_row: int = 0):
+        """dm_store_update_wants_mask_device: update_wants_mask from device columns (the mask's
+        words as int64 or uint64 tensors: the bits are what counts)."""
+        nw = self._device_cols(("mask", mask, ("int64", "uint64")))
+        n = self._device_cols(("wants", wants, "float64"))
+        self._torch_ready()
+        self._chk(self._L.dm_store_update_wants_mask_device(self._ctx, int(first_row), nw, mask.data_ptr() or None, n,
+                                                            wants.data_ptr() or None))
+
+    def release_device(self, rows):
+        """dm_store_release_device: release from a device column of rows."""
+        n = self._device_cols(("rows", rows, "int64"))
+        self._torch_ready()
+        self._chk(self._L.dm_store_release_device(self._ctx, n, rows.data_ptr() or None))
+
+    def apply_device(self, wants_mask=None, wants=None, release_rows=None, upsert=None, wants_first_row: int = 0,
+                     now_ns: int | None = None, asynchronous: bool = False):
+        """dm_store_apply_device: apply() with every column in this device's memory (the mask's
+        words int64 or uint64; narrow arrivals: has None, subclients int32, expiry_ns None with
+        now_ns).  asynchronous: dm_store_apply_device_async -- the library reads the tensors
+        until the batch is retired (apply_wait, or two asynchronous batches later, host or
+        device); they are kept alive here until then."""
+        if upsert is not None and upsert[4] is None and now_ns is None:
+            raise ValueError("arrivals without expiries need now_ns (their expiry is now_ns + lease length)")
+        # every column is checked before the first pointer is taken
+        if wants_mask is None and wants is not None:
+            raise ValueError("packed wants without a mask")
+        nw = self._device_cols(("wants_mask", wants_mask, ("int64", "uint64"))) if wants_mask is not None else 0
+        nm = self._device_cols(("wants", wants, "float64")) if wants is not None else 0
+        nr = self._device_cols(("release_rows", release_rows, "int64")) if release_rows is not None else 0
+        nu = 0
+        if upsert is not None:
+            rows, has, wv, sub, exp = upsert
+            cols = [("upsert rows", rows, "int64"), ("upsert wants", wv, "float64"),
+                    ("upsert subclients", sub, ("int64", "int32"))]
+            cols += [("upsert has", has, "float64")] if has is not None else []
+            cols += [("upsert expiry_ns", exp, "int64")] if exp is not None else []
+            nu = self._device_cols(*cols)
+
+        def ptr(t):
+            return None if t is None else t.data_ptr() or None
+
+        b = _lib.StoreBatch()
+        keep = [t for t in (wants_mask, wants, release_rows) + tuple(upsert or ()) if t is not None]
+        if wants_mask is not None:
+            b.wants_first_row, b.wants_nwords, b.wants_mask = int(wants_first_row), nw, ptr(wants_mask)
+            b.wants_n, b.wants = nm, ptr(wants)
+        if release_rows is not None:
+            b.release_n, b.release_rows = nr, ptr(release_rows)
+        if upsert is not None:
+            b.upsert_n, b.upsert_rows, b.upsert_has, b.upsert_wants = nu, ptr(rows), ptr(has), ptr(wv)
+            if str(sub.dtype).replace("torch.", "") == "int32":
+                b.upsert_subclients32 = ptr(sub)
+            else:
+                b.upsert_subclients = ptr(sub)
+            b.upsert_expiry_ns = ptr(exp)
+            b.upsert_now_ns = int(now_ns or 0)
+        self._torch_ready()
+        if not asynchronous:
+            self._chk(self._L.dm_store_apply_device(self._ctx, ctypes.byref(b)))
+            return
+        self._chk(self._L.dm_store_apply_device_async(self._ctx, ctypes.byref(b)))
+        self._async_keep = (getattr(self, "_async_keep", []) + [keep])[-3:]
+
+    def refresh_wants_device(self, wants, first_row: int = 0) -> int:
+        """dm_store_refresh_wants_device: wants[i] becomes the wants of row first_row + i
+        wherever that row is not released and the value's bits differ from the stored ones
+        (a float64 tensor on this device; first_row a multiple of 64).  Returns the number of
+        rows written."""
+        n = self._device_cols(("wants", wants, "float64"))
+        self._torch_ready()
+        changed = ctypes.c_int64(0)
+        self._chk(self._L.dm_store_refresh_wants_device(self._ctx, int(first_row), n, wants.data_ptr() or None,
+                                                        ctypes.byref(changed)))
+        return int(changed.value)
+
     # -- the batch algorithm --
     def apportion(self, now_ns: int, writeback: bool = False, recompute: bool = False, asynchronous: bool = False,
                   wb_columns: str = "auto", defer_join: bool = False):

@@ -442,6 +442,53 @@ int dm_read_store_sums_device(dm_ctx* ctx, int64_t r0, int64_t n, int64_t* count
                               double* sum_wants);
 int dm_read_leases_device(dm_ctx* ctx, int64_t off, int64_t n, double* gets, int64_t* expiry_ns);
 
+/* ---- store updates from device memory: no column over PCIe ---- */
+/* The device twins of dm_store_upsert, dm_store_update_wants, dm_store_update_wants_mask,
+   dm_store_release, dm_store_apply and dm_store_apply_async: the same arguments, every
+   non-NULL column pointer device memory of the context's device -- the pointers inside
+   dm_store_batch included (the struct itself is host memory; narrow upsert_subclients32,
+   NULL upsert_has and NULL upsert_expiry_ns mean what they mean in dm_store_apply).
+     The twin's kernels run on the caller's columns where they lie: no column is copied and
+       no column staging is allocated (a round made on the GPU, or batched into device
+       buffers by a front end, never crosses PCIe; two or three flag words come back).
+     The columns are read on the context stream; the caller orders their producer before the
+       call.  The synchronous calls wait before they return.  dm_store_apply_device_async
+       reads the caller's columns until its batch is retired: by dm_store_apply_wait, by
+       dm_config_load, or by the asynchronous call two batches later, host or device -- host
+       and device asynchronous batches share the two sets and one sequence, rejections are
+       reported late exactly as for host batches, and while a batch is in flight ticks are
+       prepared for k_general.
+     After a call the context is in exactly the state its host twin leaves for the same
+       values: rows, running sums, dense state, what later ticks launch, what dm_keep_keys
+       keeps; the same error code and dm_last_error text for every rejection the twin makes,
+       a rejected call leaving the store untouched.
+     DM_E_INVAL, no kernel launched, for a column pointer that fails the checks of
+       dm_store_load_device: not device memory of the context's device, or an allocation,
+       where hipMemGetAddressRange reports one, that does not hold the column's bytes. */
+int dm_store_upsert_device(dm_ctx* ctx, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                           const int64_t* subclients, const int64_t* expiry_ns);
+int dm_store_update_wants_device(dm_ctx* ctx, int64_t n, const int64_t* rows, const double* wants);
+int dm_store_update_wants_mask_device(dm_ctx* ctx, int64_t first_row, int64_t nwords, const uint64_t* mask,
+                                      int64_t n, const double* wants);
+int dm_store_release_device(dm_ctx* ctx, int64_t n, const int64_t* rows);
+int dm_store_apply_device(dm_ctx* ctx, const dm_store_batch* batch);
+int dm_store_apply_device_async(dm_ctx* ctx, const dm_store_batch* batch);
+/* A wants refresh from a dense device column: wants[i] is the new wants of row first_row + i
+   (first_row a multiple of 64; n any value; wants device memory as above).  The call acts
+   exactly as dm_store_update_wants_mask would when it names precisely the rows of the range
+   that are not released and whose new value differs from the stored wants as int64 bits
+   (-0.0 against +0.0 differs; a NaN equal in bits to the stored NaN does not): released
+   rows (every row dm_read_store reports as DM_RELEASED, a row loaded that way included) are
+   free slots and their entries are ignored, unchanged rows are not stored, a
+   resource none of whose rows changed is not touched (under dm_keep_keys its key stays), a
+   changed value that is NaN has the twin's consequences.  The caller diffs nothing, builds
+   no mask and packs no values: one kernel does, at about 16 B per row.  *n_changed (host
+   memory, or NULL) receives the number of rows written.  Synchronous on return.
+   DM_E_RANGE when first_row + n exceeds the store; DM_E_INVAL for a misaligned or negative
+   argument or a pointer that fails the checks; DM_E_STATE without a store. */
+int dm_store_refresh_wants_device(dm_ctx* ctx, int64_t first_row, int64_t n, const double* wants,
+                                  int64_t* n_changed);
+
 /* ---- hierarchy (intermediate servers) ---- */
 /* server.go:850-879: wants_total = sum(wants), subclients_total = sum(num_clients);
  * DM_E_ARGUMENT when some num_clients < 1 */
