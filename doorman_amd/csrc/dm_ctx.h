@@ -8,7 +8,7 @@
 // by dm_decide_plan.h's plan), the entry macros of the C-ABI calls, and the functions that
 // cross a unit boundary.  The only definition of dm_ctx; the units around it are
 // dm_runtime.cpp (context life, streams, profiling), dm_plan.cpp, dm_tick.cpp, dm_decide.cpp,
-// dm_store.cpp, dm_store_update.cpp and dm_hier_host.cpp.  See DESIGN.md §3-§5.
+// dm_store.cpp, dm_store_update.cpp, dm_store_layout.cpp and dm_hier_host.cpp.  See DESIGN.md §3-§5.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded when the first communicator is made
@@ -934,10 +934,12 @@ static hipError_t upload(DBuf<T>& b, const T* src, size_t n, hipStream_t st) {
   return hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st);
 }
 
+// (kind: into host memory, or hipMemcpyDeviceToDevice into a caller's device column)
 template <typename T>
-static hipError_t download(T* dst, const T* src, int64_t off, int64_t n, hipStream_t st) {
+static hipError_t download(T* dst, const T* src, int64_t off, int64_t n, hipStream_t st,
+                           hipMemcpyKind kind = hipMemcpyDeviceToHost) {
   if (!dst || n == 0) return hipSuccess;
-  return hipMemcpyAsync(dst, src + off, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st);
+  return hipMemcpyAsync(dst, src + off, (size_t)n * sizeof(T), kind, st);
 }
 
 static inline int check_range(dm_ctx* c, int64_t off, int64_t n, int64_t total) {
@@ -960,7 +962,14 @@ int set_parts_ok(dm_ctx* c, bool ok);
 int ready(dm_ctx* c);
 // dm_store.cpp
 int check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what);
-// dm_store_update.cpp
+// A caller's device column of `bytes` bytes, when given: check_device_ptr, before any kernel or
+// copy is given it.
+#define DM_DEVICE_PTR(ctx, p, bytes, what)                                           \
+  do {                                                                               \
+    if (p)                                                                           \
+      if (int _rc = dm::check_device_ptr(ctx, p, (size_t)(bytes), what)) return _rc; \
+  } while (0)
+// dm_store_update.cpp (its callers: the loads, dm_config_load, dm_store_layout.cpp)
 void async_drain(dm_ctx* c);
 int async_retire_all(dm_ctx* c);
 // dm_hier_host.cpp

@@ -5,7 +5,7 @@
 // stream, synchronisation, pinned-memory, profiling and introspection calls.  The plan
 // is built in dm_plan.cpp, a tick launched in dm_tick.cpp, a round of requests in
 // dm_decide.cpp; the store is loaded and read in dm_store.cpp, updated in
-// dm_store_update.cpp; the hierarchy's host side is dm_hier_host.cpp.  See DESIGN.md §3-§5.
+// dm_store_update.cpp, re-laid out and cleaned in dm_store_layout.cpp; the hierarchy's host side is dm_hier_host.cpp.  See DESIGN.md §3-§5.
 #include <mutex>
 
 #include "dm_ctx.h"

@@ -181,24 +181,42 @@ int dm_config_load(dm_ctx* c, int64_t R, const dm_resource_cfg* cfg) {
   return DM_OK;
 }
 
-int dm_read_leases(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
+// The two range reads, each one body for both destinations.  Host memory (device false): the
+// plain columns are downloaded straight from the store or the tick's outputs, the resolved ones
+// go through set 0's exp / sub and are downloaded from there.  The caller's device columns
+// (checked by check_device_ptr, below): the same columns copied in HBM, the resolved ones
+// written by the kernel where the caller wants them.
+static int read_leases(dm_ctx* c, bool device, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
   DM_ENTER(c);
   UpdateStage& S = c->stage[0];  // synchronous on return: set 0 (dm_update_stage.h)
   DM_STORE_READABLE(c);
   if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
   int rc = check_range(c, off, n, c->N);
   if (rc) return rc;
-  DM_HIP(c, download(gets, c->last_writeback ? c->has.p : c->out_gets.p, off, n, c->stream), "read gets");
+  if (device) {
+    DM_DEVICE_PTR(c, gets, n * 8, "gets");
+    DM_DEVICE_PTR(c, expiry_ns, n * 8, "expiry_ns");
+  }
+  hipStream_t st = c->stream;
+  const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  DM_HIP(c, download(gets, c->last_writeback ? c->has.p : c->out_gets.p, off, n, st, kind), "read gets");
   if (expiry_ns && c->last_writeback) {  // the store's encoding, resolved on the device
-    DM_HIP(c, S.exp.ensure((size_t)std::max<int64_t>(n, 1)), "stage expiry");
-    DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, S.exp.p,
-                                  nullptr, c->stream),
+    if (!device) DM_HIP(c, S.exp.ensure((size_t)std::max<int64_t>(n, 1)), "stage expiry");
+    DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p,
+                                  device ? expiry_ns : S.exp.p, nullptr, st),
            "resolve expiry");
-    DM_HIP(c, download(expiry_ns, (const int64_t*)S.exp.p, 0, n, c->stream), "read expiry");
+    if (!device) DM_HIP(c, download(expiry_ns, (const int64_t*)S.exp.p, 0, n, st), "read expiry");
   } else {
-    DM_HIP(c, download(expiry_ns, (const int64_t*)c->out_expiry.p, off, n, c->stream), "read expiry");
+    DM_HIP(c, download(expiry_ns, (const int64_t*)c->out_expiry.p, off, n, st, kind), "read expiry");
   }
   return c->synced("read leases");
+}
+
+int dm_read_leases(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
+  return read_leases(c, false, off, n, gets, expiry_ns);
+}
+int dm_read_leases_device(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
+  return read_leases(c, true, off, n, gets, expiry_ns);
 }
 
 int dm_read_leases_rows(dm_ctx* c, int64_t n, const int64_t* rows, double* gets, int64_t* expiry_ns) {
@@ -311,33 +329,53 @@ int dm_read_config(dm_ctx* c, int64_t r0, int64_t n, int32_t* kind, double* capa
   return DM_OK;
 }
 
-int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
+static int read_store(dm_ctx* c, bool device, int64_t off, int64_t n, double* has, double* wants, int64_t* sub,
+                      int64_t* exp) {
   DM_ENTER(c);
   UpdateStage& S = c->stage[0];  // synchronous on return: set 0 (dm_update_stage.h)
   DM_STORE_READABLE(c);
   if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   int rc = check_range(c, off, n, c->N);
   if (rc) return rc;
-  DM_HIP(c, download(has, (const double*)c->has.p, off, n, c->stream), "read has");
-  DM_HIP(c, download(wants, (const double*)c->wants.p, off, n, c->stream), "read wants");
+  if (device) {
+    DM_DEVICE_PTR(c, has, n * 8, "has");
+    DM_DEVICE_PTR(c, wants, n * 8, "wants");
+    DM_DEVICE_PTR(c, sub, n * 8, "subclients");
+    DM_DEVICE_PTR(c, exp, n * 8, "expiry_ns");
+  }
+  hipStream_t st = c->stream;
+  const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  DM_HIP(c, download(has, (const double*)c->has.p, off, n, st, kind), "read has");
+  DM_HIP(c, download(wants, (const double*)c->wants.p, off, n, st, kind), "read wants");
   if ((sub || exp) && n > 0) {  // subclients and expiry from the column encoding (dm_device.h)
-    DM_HIP(c, S.exp.ensure((size_t)n), "stage expiry");
-    DM_HIP(c, S.sub.ensure((size_t)n), "stage subclients");
+    if (!device) {
+      DM_HIP(c, S.exp.ensure((size_t)n), "stage expiry");
+      DM_HIP(c, S.sub.ensure((size_t)n), "stage subclients");
+    }
     DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p,
-                                  exp ? S.exp.p : nullptr, sub ? S.sub.p : nullptr, c->stream),
+                                  device || !exp ? exp : S.exp.p, device || !sub ? sub : S.sub.p, st),
            "resolve rows");
-    DM_HIP(c, download(exp, (const int64_t*)S.exp.p, 0, n, c->stream), "read expiry");
-    DM_HIP(c, download(sub, (const int64_t*)S.sub.p, 0, n, c->stream), "read subclients");
+    if (!device) {
+      DM_HIP(c, download(exp, (const int64_t*)S.exp.p, 0, n, st), "read expiry");
+      DM_HIP(c, download(sub, (const int64_t*)S.sub.p, 0, n, st), "read subclients");
+    }
   }
   return c->synced("read store");
 }
 
+int dm_read_store(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
+  return read_store(c, false, off, n, has, wants, sub, exp);
+}
+int dm_read_store_device(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
+  return read_store(c, true, off, n, has, wants, sub, exp);
+}
+
 // ---- the store from and into device memory (dm_load.hip) ----
 
-// A caller's device column, for the four calls below and the device twins of the update
-// calls (dm_store_update.cpp): p must be device memory of the context's device, and where
-// the runtime knows p's allocation, that allocation must hold `bytes` bytes from p.  Asked
-// of the runtime before any kernel or copy is given p.
+// A caller's device column (dm_ctx.h DM_DEVICE_PTR), for the device calls of this unit and the
+// device twins of the update calls (dm_store_update.cpp): p must be device memory of the
+// context's device, and where the runtime knows p's allocation, that allocation must hold
+// `bytes` bytes from p.  Asked of the runtime before any kernel or copy is given p.
 int dm::check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what) {
   hipPointerAttribute_t at{};
   if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -357,12 +395,6 @@ int dm::check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* wha
     return c->fail(DM_E_INVAL, std::string(what) + ": its allocation does not hold the column");
   return DM_OK;
 }
-// every non-NULL pointer of a call, each with its bytes
-#define DM_DEVICE_PTR(ctx, p, count, what)                                                    \
-  do {                                                                                        \
-    if (p)                                                                                    \
-      if (int _rc = check_device_ptr(ctx, p, (size_t)(count) * 8, what)) return _rc;          \
-  } while (0)
 
 int dm_store_load_device(dm_ctx* c, const dm_snapshot* s) {
   DM_ENTER(c);
@@ -375,14 +407,14 @@ int dm_store_load_device(dm_ctx* c, const dm_snapshot* s) {
   const bool have_agg = s->agg_count && s->agg_sum_has && s->agg_sum_wants;
   if ((s->agg_count || s->agg_sum_has || s->agg_sum_wants) && !have_agg)
     return c->fail(DM_E_INVAL, "give all three running sums or none");
-  DM_DEVICE_PTR(c, s->seg_off, R + 1, "seg_off");
-  DM_DEVICE_PTR(c, s->wants, N, "wants");
-  DM_DEVICE_PTR(c, s->has, N, "has");
-  DM_DEVICE_PTR(c, s->subclients, N, "subclients");
-  DM_DEVICE_PTR(c, s->expiry_ns, N, "expiry_ns");
-  DM_DEVICE_PTR(c, s->agg_count, R, "agg_count");
-  DM_DEVICE_PTR(c, s->agg_sum_has, R, "agg_sum_has");
-  DM_DEVICE_PTR(c, s->agg_sum_wants, R, "agg_sum_wants");
+  DM_DEVICE_PTR(c, s->seg_off, (R + 1) * 8, "seg_off");
+  DM_DEVICE_PTR(c, s->wants, N * 8, "wants");
+  DM_DEVICE_PTR(c, s->has, N * 8, "has");
+  DM_DEVICE_PTR(c, s->subclients, N * 8, "subclients");
+  DM_DEVICE_PTR(c, s->expiry_ns, N * 8, "expiry_ns");
+  DM_DEVICE_PTR(c, s->agg_count, R * 8, "agg_count");
+  DM_DEVICE_PTR(c, s->agg_sum_has, R * 8, "agg_sum_has");
+  DM_DEVICE_PTR(c, s->agg_sum_wants, R * 8, "agg_sum_wants");
   hipStream_t st = c->stream;
   DM_HIP(c, hipStreamSynchronize(st), "sync");
   // Validation reads the caller's columns only: the layout on the host (the plan is built
@@ -422,60 +454,15 @@ int dm_store_load_device(dm_ctx* c, const dm_snapshot* s) {
   return store_loaded(c, R, N, off.data(), s->seg_off, (f & kLdGeneral) != 0, !(f & kLdNotOne));
 }
 
-int dm_read_store_device(dm_ctx* c, int64_t off, int64_t n, double* has, double* wants, int64_t* sub, int64_t* exp) {
-  DM_ENTER(c);
-  DM_STORE_READABLE(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  int rc = check_range(c, off, n, c->N);
-  if (rc) return rc;
-  DM_DEVICE_PTR(c, has, n, "has");
-  DM_DEVICE_PTR(c, wants, n, "wants");
-  DM_DEVICE_PTR(c, sub, n, "subclients");
-  DM_DEVICE_PTR(c, exp, n, "expiry_ns");
-  if (n > 0) {
-    hipStream_t st = c->stream;
-    if (has) DM_HIP(c, hipMemcpyAsync(has, c->has.p + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st), "read has");
-    if (wants)
-      DM_HIP(c, hipMemcpyAsync(wants, c->wants.p + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st), "read wants");
-    if (sub || exp)  // subclients and expiry from the column encoding (dm_device.h), into the caller's columns
-      DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, exp, sub, st),
-             "resolve rows");
-  }
-  return c->synced("read store");
-}
-
 int dm_read_store_sums_device(dm_ctx* c, int64_t r0, int64_t n, int64_t* count, double* sum_has, double* sum_wants) {
   DM_ENTER(c);
   DM_STORE_READABLE(c);
   int rc = check_range(c, r0, n, c->R);
   if (rc) return rc;
-  DM_DEVICE_PTR(c, count, n, "count");
-  DM_DEVICE_PTR(c, sum_has, n, "sum_has");
-  DM_DEVICE_PTR(c, sum_wants, n, "sum_wants");
+  DM_DEVICE_PTR(c, count, n * 8, "count");
+  DM_DEVICE_PTR(c, sum_has, n * 8, "sum_has");
+  DM_DEVICE_PTR(c, sum_wants, n * 8, "sum_wants");
   // always the store's running sums (agg), never a non-writeback tick's view (res)
   if (n > 0) DM_HIP(c, launch_unpack_sums(c->agg.p + r0, n, count, sum_has, sum_wants, c->stream), "read sums");
   return c->synced("read sums");
-}
-
-int dm_read_leases_device(dm_ctx* c, int64_t off, int64_t n, double* gets, int64_t* expiry_ns) {
-  DM_ENTER(c);
-  DM_STORE_READABLE(c);
-  if (!c->have_result) return c->fail(DM_E_STATE, "no dm_apportion result");
-  int rc = check_range(c, off, n, c->N);
-  if (rc) return rc;
-  DM_DEVICE_PTR(c, gets, n, "gets");
-  DM_DEVICE_PTR(c, expiry_ns, n, "expiry_ns");
-  if (n > 0) {
-    hipStream_t st = c->stream;
-    const double* g = c->last_writeback ? c->has.p : c->out_gets.p;
-    if (gets) DM_HIP(c, hipMemcpyAsync(gets, g + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st), "read gets");
-    if (expiry_ns && c->last_writeback)  // the store's encoding, resolved on the device
-      DM_HIP(c, launch_resolve_rows(n, nullptr, off, c->sub.p, c->expiry.p, c->row_index(), c->agg.p, expiry_ns,
-                                    nullptr, st),
-             "resolve expiry");
-    else if (expiry_ns)
-      DM_HIP(c, hipMemcpyAsync(expiry_ns, c->out_expiry.p + off, (size_t)n * 8, hipMemcpyDeviceToDevice, st),
-             "read expiry");
-  }
-  return c->synced("read leases");
 }

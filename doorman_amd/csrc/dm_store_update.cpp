@@ -1,6 +1,7 @@
-// dm_store_update.cpp — the calls that change a loaded store: staged updates (upsert,
-// wants refreshes, release), a round's batch (dm_store_apply, synchronous and
-// asynchronous), the re-layout and Clean on the device.
+// dm_store_update.cpp — the calls that write rows of a loaded store from columns the caller
+// gives, in host memory (staged) or device memory (read in place): the single updates (upsert,
+// wants refreshes, release), the dense wants refresh, and a round's batch (dm_store_apply,
+// synchronous and asynchronous) with its retirement.
 #include "dm_ctx.h"
 
 // An update's columns are staged in an UpdateStage (dm_update_stage.h: set 0 for every call
@@ -21,9 +22,9 @@ struct StageCol {
 };
 static constexpr int64_t kStageChunk = 1 << 22;  // rows per copy/validate step of a single call
 
-// Where a part's kernels read its columns: one parameter of row_part and mask_kernels (which
-// apply_enqueue makes from its `device` argument), so that the host calls and their device twins (dm_store_*_device) are one
-// sequence of launches.
+// Where a part's kernels read its columns: one parameter of row_part and mask_kernels, made from
+// a call's `device` argument by the builders below, so that the host calls and their device
+// twins (dm_store_*_device) are one sequence of launches.
 //   - staged (the host calls): set S's columns, which the copy stream fills; the context
 //     stream waits for each copy's event before the kernels that read it.
 //   - in place (the device twins): the caller's own device columns, read on the context
@@ -62,13 +63,22 @@ static UpdSrc in_place(const dm_store_batch* b) {
   u.exp = b->upsert_expiry_ns;
   return u;
 }
-// A caller's device column of `bytes` bytes, when given: dm_ctx.h check_device_ptr, before
-// any kernel is given it.
-#define DM_DEVICE_COL(ctx, p, bytes, what)                                       \
-  do {                                                                           \
-    if (p)                                                                       \
-      if (int _rc = check_device_ptr(ctx, p, (size_t)(bytes), what)) return _rc; \
-  } while (0)
+// The in-place source of a single call that names rows (a release's rows too are `rows`, as in
+// staged()), and of a single masked refresh.
+static UpdSrc in_place(const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
+                       const int64_t* exp) {
+  UpdSrc u;
+  u.in_place = true;
+  u.rows = u.rel = rows;
+  u.has = has, u.wants = wants, u.sub = sub, u.exp = exp;
+  return u;
+}
+static UpdSrc in_place(const uint64_t* mask, const double* mwants) {
+  UpdSrc u;
+  u.in_place = true;
+  u.mask = mask, u.mwants = mwants;
+  return u;
+}
 
 // How a call that dm_keep_keys may keep ends (dm_row_epoch.h): a wants refresh, and with
 // DM_KEEP_UPDATES a release, an upsert or a synchronous batch.  Where the mode does not cover
@@ -114,8 +124,8 @@ static int copy_cols(dm_ctx* c, const StageCol* cols, int ncols, int64_t off, in
 }
 
 // A part that names rows (an upsert, a row refresh, a release; alone or in a batch), its
-// columns at src (staged in S, or the caller's in place): the device sequence on the context stream.  Its rows in range and unique
-// (a bitmap over the table, O(n + N/64)) once they have landed, the rejection of the part
+// columns at src (staged in S, or the caller's in place): the device sequence on the context
+// stream.  Its rows in range and unique (a bitmap over the table, O(n + N/64)) once they have landed, the rejection of the part
 // before carried into its word, the apply kernel (which finds each row's resource, and returns
 // at once from a rejected word), the bitmap cleared again.  cols: a single call's host columns,
 // copied here chunk by chunk; b: a batch, whose part is already on its way and whose arrivals
@@ -211,152 +221,138 @@ static int single_end(dm_ctx* c, UpdateStage& S, UpdPart part, WriteEnd& we, int
   return DM_OK;
 }
 
-// A single call that names rows: bitmap and flags word ready, the part, the end.
-// (src: staged(S), whose columns `cols` fill; or the caller's in place, and no cols.)
-static int single_rows(dm_ctx* c, UpdateStage& S, const UpdSrc& src, WriteEnd& we, UpdPart part, int64_t n,
-                       const StageCol* cols, int ncols) {
+
+// ---- the parts' argument rules, stated once for the single calls and batch_args ----
+
+static bool block_aligned(int64_t first_row) { return first_row >= 0 && !(first_row & 63); }
+
+// A masked refresh's scalars.  The single call checks them all; as a batch's part, a refresh
+// without mask words is absent, and only packed values it may still bring are looked at.
+static int mask_args(dm_ctx* c, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n, const double* wants,
+                     bool batch_part) {
+  if ((!batch_part || nwords > 0) &&
+      (!block_aligned(first_row) || nwords < 0 || n < 0 || (nwords > 0 && !mask) || (n > 0 && !wants)))
+    return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
+  if (nwords == 0 && n > 0) return c->fail(DM_E_INVAL, "packed values without a mask");
+  if (nwords > 0 && first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
+  return DM_OK;
+}
+static int release_args(dm_ctx* c, int64_t n, const int64_t* rows) {
+  return n < 0 || (n > 0 && !rows) ? c->fail(DM_E_INVAL, "bad release") : DM_OK;
+}
+// (narrow: a batch's arrivals, which may come without has and expiry; sub: of either width)
+static int upsert_args(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants, const void* sub,
+                       const int64_t* exp, bool narrow) {
+  const bool missing = !rows || !wants || !sub || (!narrow && (!has || !exp));
+  return n < 0 || (n > 0 && missing) ? c->fail(DM_E_INVAL, "bad upsert") : DM_OK;
+}
+
+// ---- the single calls, each one body for host columns and device columns ----
+// The steps of every body: the entry, the argument checks, nothing to do; (device) the pointer
+// checks; the call's WriteEnd; (host) set 0's columns and what is copied into them; the kernels
+// from staged(S) or from the caller's columns in place; single_end.
+
+// Every update call's entry (a batch's too).
+static int update_enter(dm_ctx* c) {
+  DM_ENTER(c);
+  DM_STORE_OK(c);
+  return c->store_loaded ? DM_OK : c->fail(DM_E_STATE, "no store loaded");
+}
+
+// A single call that names n > 0 rows, from its pointer checks on (a column the call does not
+// take: nullptr, which every step passes over; stage: the staging's name in a failure).
+static int single_rows(dm_ctx* c, bool device, UpdPart part, RowWrite kind, const char* stage, int64_t n,
+                       const int64_t* rows, const double* has, const double* wants, const int64_t* sub, const int64_t* exp) {
+  if (device) {
+    DM_DEVICE_PTR(c, rows, n * 8, "rows");
+    DM_DEVICE_PTR(c, has, n * 8, "has");
+    DM_DEVICE_PTR(c, wants, n * 8, "wants");
+    DM_DEVICE_PTR(c, sub, n * 8, "subclients");
+    DM_DEVICE_PTR(c, exp, n * 8, "expiry_ns");
+  }
+  if (part == UpdPart::upsert) c->expl_rows = true;  // (kept or not: the rows take explicit expiries)
+  WriteEnd we(c, kind);  // (a refresh: a NaN wants ends a resource's dense state)
+  UpdateStage& S = c->stage[0];
+  if (!device)
+    DM_HIP(c, !wants ? S.rows.ensure((size_t)n) : !sub ? S.ensure_each(n, S.rows, S.wants) : S.ensure_upsert(n), stage);
+  const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}, {S.sub.p, sub, 8}, {S.has.p, has, 8}, {S.exp.p, exp, 8}};
+  const UpdSrc src = device ? in_place(rows, has, wants, sub, exp) : staged(S, nullptr);
   DM_HIP(c, c->row_bits.ensure(c->N, c->stream), "row bitmap");
   DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
-  if (int rc = row_part(c, S, src, we, part, n, cols, ncols, nullptr)) return rc;
+  if (int rc = row_part(c, S, src, we, part, n, cols, 5, nullptr)) return rc;
   return single_end(c, S, part, we, n);
 }
 
-int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
-                    const int64_t* sub, const int64_t* exp) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (n < 0 || (n > 0 && (!rows || !has || !wants || !sub || !exp))) return c->fail(DM_E_INVAL, "bad upsert");
+static int upsert(dm_ctx* c, bool device, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                  const int64_t* sub, const int64_t* exp) {
+  if (int rc = update_enter(c)) return rc;
+  if (int rc = upsert_args(c, n, rows, has, wants, sub, exp, false)) return rc;
   if (n == 0) return DM_OK;
-  c->expl_rows = true;  // (kept or not: the rows take explicit expiries)
-  WriteEnd we(c, RowWrite::upsert);
-  UpdateStage& S = c->stage[0];
-  DM_HIP(c, S.ensure_upsert(n), "stage upsert");
-  const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}, {S.sub.p, sub, 8}, {S.has.p, has, 8}, {S.exp.p, exp, 8}};
-  return single_rows(c, S, staged(S, nullptr), we, UpdPart::upsert, n, cols, 5);
+  return single_rows(c, device, UpdPart::upsert, RowWrite::upsert, "stage upsert", n, rows, has, wants, sub, exp);
 }
 
-int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
+static int update_wants(dm_ctx* c, bool device, int64_t n, const int64_t* rows, const double* wants) {
+  if (int rc = update_enter(c)) return rc;
   if (n < 0 || (n > 0 && (!rows || !wants))) return c->fail(DM_E_INVAL, "bad update");
   if (n == 0) return DM_OK;
-  WriteEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
-  UpdateStage& S = c->stage[0];
-  DM_HIP(c, S.ensure_each(n, S.rows, S.wants), "stage refresh");
-  const StageCol cols[] = {{S.rows.p, rows, 8}, {S.wants.p, wants, 8}};
-  return single_rows(c, S, staged(S, nullptr), re, UpdPart::refresh, n, cols, 2);
+  return single_rows(c, device, UpdPart::refresh, RowWrite::refresh, "stage refresh", n, rows, nullptr, wants, nullptr, nullptr);
 }
+
 
 // The same narrow Assign with the rows as a bit mask (one bit per row of
 // [first_row, first_row + 64 nwords)) and the values packed in row order: at
 // more than ~3% of the rows updated the mask is smaller than 8-B row indices.
-int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n,
-                               const double* wants) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (first_row < 0 || (first_row & 63) || nwords < 0 || n < 0 || (nwords > 0 && !mask) || (n > 0 && !wants))
-    return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
-  if (nwords == 0) return n == 0 ? DM_OK : c->fail(DM_E_INVAL, "packed values without a mask");
-  if (first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
+static int update_wants_mask(dm_ctx* c, bool device, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n,
+                             const double* wants) {
+  if (int rc = update_enter(c)) return rc;
+  if (int rc = mask_args(c, first_row, nwords, mask, n, wants, false)) return rc;
+  if (nwords == 0) return DM_OK;
+  if (device) {
+    DM_DEVICE_PTR(c, mask, nwords * 8, "mask");
+    if (n > 0) DM_DEVICE_PTR(c, wants, n * 8, "wants");
+  }
   WriteEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
   UpdateStage& S = c->stage[0];
-  DM_HIP(c, S.ensure_mask(nwords, n), "stage mask");
+  DM_HIP(c, device ? S.ensure_scan(nwords) : S.ensure_mask(nwords, n), device ? "mask scratch" : "stage mask");
   DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
-  if (int rc = mask_copies(c, S, nwords, mask, n, wants, 0)) return rc;
-  if (int rc = mask_kernels(c, S, staged(S, nullptr), first_row, nwords, n, S.flag(0), 0, re.keys())) return rc;
-  return single_end(c, S, UpdPart::refresh_mask, re, n);
-}
-
-int dm_store_release(dm_ctx* c, int64_t n, const int64_t* rows) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad release");
-  if (n == 0) return DM_OK;
-  WriteEnd we(c, RowWrite::release);
-  UpdateStage& S = c->stage[0];
-  DM_HIP(c, S.rows.ensure((size_t)n), "stage rows");
-  const StageCol cols[] = {{S.rows.p, rows, 8}};
-  return single_rows(c, S, staged(S, nullptr), we, UpdPart::release, n, cols, 1);
-}
-
-// ---- the single calls on device columns (dm_store_*_device) ----
-// The argument checks, messages and WriteEnd kinds are the host twins'; then the pointer
-// checks; then the twin's kernels with the caller's pointers (UpdSrc in place).
-
-int dm_store_upsert_device(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
-                           const int64_t* sub, const int64_t* exp) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (n < 0 || (n > 0 && (!rows || !has || !wants || !sub || !exp))) return c->fail(DM_E_INVAL, "bad upsert");
-  if (n == 0) return DM_OK;
-  DM_DEVICE_COL(c, rows, n * 8, "rows");
-  DM_DEVICE_COL(c, has, n * 8, "has");
-  DM_DEVICE_COL(c, wants, n * 8, "wants");
-  DM_DEVICE_COL(c, sub, n * 8, "subclients");
-  DM_DEVICE_COL(c, exp, n * 8, "expiry_ns");
-  c->expl_rows = true;  // (kept or not: the rows take explicit expiries)
-  WriteEnd we(c, RowWrite::upsert);
-  UpdSrc src;
-  src.in_place = true;
-  src.rows = rows, src.has = has, src.wants = wants, src.sub = sub, src.exp = exp;
-  return single_rows(c, c->stage[0], src, we, UpdPart::upsert, n, nullptr, 0);
-}
-
-int dm_store_update_wants_device(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (n < 0 || (n > 0 && (!rows || !wants))) return c->fail(DM_E_INVAL, "bad update");
-  if (n == 0) return DM_OK;
-  DM_DEVICE_COL(c, rows, n * 8, "rows");
-  DM_DEVICE_COL(c, wants, n * 8, "wants");
-  WriteEnd re(c, RowWrite::refresh);  // a NaN wants ends a resource's dense state
-  UpdSrc src;
-  src.in_place = true;
-  src.rows = rows, src.wants = wants;
-  return single_rows(c, c->stage[0], src, re, UpdPart::refresh, n, nullptr, 0);
-}
-
-int dm_store_update_wants_mask_device(dm_ctx* c, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n,
-                                      const double* wants) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (first_row < 0 || (first_row & 63) || nwords < 0 || n < 0 || (nwords > 0 && !mask) || (n > 0 && !wants))
-    return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
-  if (nwords == 0) return n == 0 ? DM_OK : c->fail(DM_E_INVAL, "packed values without a mask");
-  if (first_row + 64 * (nwords - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
-  DM_DEVICE_COL(c, mask, nwords * 8, "mask");
-  if (n > 0) DM_DEVICE_COL(c, wants, n * 8, "wants");
-  WriteEnd re(c, RowWrite::refresh_mask);  // a NaN wants ends a resource's dense state
-  UpdateStage& S = c->stage[0];
-  DM_HIP(c, S.ensure_scan(nwords), "mask scratch");
-  DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
-  UpdSrc src;
-  src.in_place = true;
-  src.mask = mask, src.mwants = wants;
+  if (!device)
+    if (int rc = mask_copies(c, S, nwords, mask, n, wants, 0)) return rc;
+  const UpdSrc src = device ? in_place(mask, wants) : staged(S, nullptr);
   if (int rc = mask_kernels(c, S, src, first_row, nwords, n, S.flag(0), 0, re.keys())) return rc;
   return single_end(c, S, UpdPart::refresh_mask, re, n);
 }
 
-int dm_store_release_device(dm_ctx* c, int64_t n, const int64_t* rows) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (n < 0 || (n > 0 && !rows)) return c->fail(DM_E_INVAL, "bad release");
+static int release(dm_ctx* c, bool device, int64_t n, const int64_t* rows) {
+  if (int rc = update_enter(c)) return rc;
+  if (int rc = release_args(c, n, rows)) return rc;
   if (n == 0) return DM_OK;
-  DM_DEVICE_COL(c, rows, n * 8, "rows");
-  WriteEnd we(c, RowWrite::release);
-  UpdSrc src;
-  src.in_place = true;
-  src.rel = rows;
-  return single_rows(c, c->stage[0], src, we, UpdPart::release, n, nullptr, 0);
+  return single_rows(c, device, UpdPart::release, RowWrite::release, "stage rows", n, rows, nullptr, nullptr, nullptr, nullptr);
 }
+
+int dm_store_upsert(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                    const int64_t* sub, const int64_t* exp) {
+  return upsert(c, false, n, rows, has, wants, sub, exp);
+}
+int dm_store_upsert_device(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                           const int64_t* sub, const int64_t* exp) {
+  return upsert(c, true, n, rows, has, wants, sub, exp);
+}
+int dm_store_update_wants(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
+  return update_wants(c, false, n, rows, wants);
+}
+int dm_store_update_wants_device(dm_ctx* c, int64_t n, const int64_t* rows, const double* wants) {
+  return update_wants(c, true, n, rows, wants);
+}
+int dm_store_update_wants_mask(dm_ctx* c, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n,
+                               const double* wants) {
+  return update_wants_mask(c, false, first_row, nwords, mask, n, wants);
+}
+int dm_store_update_wants_mask_device(dm_ctx* c, int64_t first_row, int64_t nwords, const uint64_t* mask, int64_t n,
+                                      const double* wants) {
+  return update_wants_mask(c, true, first_row, nwords, mask, n, wants);
+}
+int dm_store_release(dm_ctx* c, int64_t n, const int64_t* rows) { return release(c, false, n, rows); }
+int dm_store_release_device(dm_ctx* c, int64_t n, const int64_t* rows) { return release(c, true, n, rows); }
 
 // A wants refresh from a dense device column: wants[i] is the new wants of row first_row + i.
 // One kernel (k_refresh_dense, dm_update.hip) finds the rows that are not released and whose
@@ -365,15 +361,13 @@ int dm_store_release_device(dm_ctx* c, int64_t n, const int64_t* rows) {
 // refresh does (RowWrite::refresh_mask, UpdPart::refresh_mask for its flags word: only kUpdNaN
 // can be set, the range was checked here).  Over PCIe: the flags word and the 8-B count.
 int dm_store_refresh_wants_device(dm_ctx* c, int64_t first_row, int64_t n, const double* wants, int64_t* n_changed) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  if (first_row < 0 || (first_row & 63) || n < 0 || (n > 0 && !wants))
+  if (int rc = update_enter(c)) return rc;
+  if (!block_aligned(first_row) || n < 0 || (n > 0 && !wants))
     return c->fail(DM_E_INVAL, "bad dense refresh (first_row must be a multiple of 64)");
   if (first_row > c->N || n > c->N - first_row) return c->fail(DM_E_RANGE, "rows past the store's end");
   if (n_changed) *n_changed = 0;
   if (n == 0) return DM_OK;
-  DM_DEVICE_COL(c, wants, n * 8, "wants");
+  DM_DEVICE_PTR(c, wants, n * 8, "wants");
   WriteEnd re(c, RowWrite::refresh_mask);  // a changed NaN wants ends a resource's dense state
   UpdateStage& S = c->stage[0];
   DM_HIP(c, S.reset_flags(kFlagWords, c->stream), "update flags");
@@ -397,22 +391,14 @@ int dm_store_refresh_wants_device(dm_ctx* c, int64_t first_row, int64_t n, const
 // departures, arrivals.  A part whose validation fails is not applied, nor is any
 // later part (k_carry_reject); earlier parts stay applied.
 static int batch_args(dm_ctx* c, const dm_store_batch* b) {
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
   if (!b) return c->fail(DM_E_INVAL, "null batch");
   const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
   if (nw < 0 || nm < 0 || nr < 0 || nu < 0) return c->fail(DM_E_INVAL, "negative batch sizes");
-  if (nw == 0 && nm > 0) return c->fail(DM_E_INVAL, "packed values without a mask");
-  if (nw > 0) {
-    const int64_t fr = b->wants_first_row;
-    if (fr < 0 || (fr & 63) || !b->wants_mask || (nm > 0 && !b->wants))
-      return c->fail(DM_E_INVAL, "bad masked update (first_row must be a multiple of 64)");
-    if (fr + 64 * (nw - 1) >= c->N) return c->fail(DM_E_RANGE, "mask words past the store's end");
-  }
-  if (nr > 0 && !b->release_rows) return c->fail(DM_E_INVAL, "bad release");
+  if (int rc = mask_args(c, b->wants_first_row, nw, b->wants_mask, nm, b->wants, true)) return rc;
+  if (int rc = release_args(c, nr, b->release_rows)) return rc;
   // narrow arrivals: subclients as int32, has NULL (= 0), expiry NULL (= now + lease length)
-  const bool sub32 = b->upsert_subclients32 != nullptr;
-  if (nu > 0 && (!b->upsert_rows || !b->upsert_wants || (!b->upsert_subclients && !sub32)))
-    return c->fail(DM_E_INVAL, "bad upsert");
+  const void* sub = b->upsert_subclients32 ? (const void*)b->upsert_subclients32 : b->upsert_subclients;
+  if (int rc = upsert_args(c, nu, b->upsert_rows, b->upsert_has, b->upsert_wants, sub, b->upsert_expiry_ns, true)) return rc;
   if (nu > 0 && !b->upsert_expiry_ns && !c->cfg_loaded)
     return c->fail(DM_E_STATE, "arrivals without expiries take the resource's lease length: load a configuration");
   if (nu > 0 && !b->upsert_expiry_ns && b->upsert_now_ns <= 0)  // an unset clock would insert lapsed leases
@@ -424,18 +410,18 @@ static int batch_args(dm_ctx* c, const dm_store_batch* b) {
 // passes check_device_ptr with the part's bytes before any kernel is given it.
 static int batch_device_ptrs(dm_ctx* c, const dm_store_batch* b) {
   const int64_t nw = b->wants_nwords, nm = b->wants_n, nr = b->release_n, nu = b->upsert_n;
-  if (nw > 0) DM_DEVICE_COL(c, b->wants_mask, nw * 8, "wants_mask");
-  if (nw > 0 && nm > 0) DM_DEVICE_COL(c, b->wants, nm * 8, "wants");
-  if (nr > 0) DM_DEVICE_COL(c, b->release_rows, nr * 8, "release_rows");
+  if (nw > 0) DM_DEVICE_PTR(c, b->wants_mask, nw * 8, "wants_mask");
+  if (nw > 0 && nm > 0) DM_DEVICE_PTR(c, b->wants, nm * 8, "wants");
+  if (nr > 0) DM_DEVICE_PTR(c, b->release_rows, nr * 8, "release_rows");
   if (nu > 0) {
-    DM_DEVICE_COL(c, b->upsert_rows, nu * 8, "upsert_rows");
-    DM_DEVICE_COL(c, b->upsert_has, nu * 8, "upsert_has");
-    DM_DEVICE_COL(c, b->upsert_wants, nu * 8, "upsert_wants");
+    DM_DEVICE_PTR(c, b->upsert_rows, nu * 8, "upsert_rows");
+    DM_DEVICE_PTR(c, b->upsert_has, nu * 8, "upsert_has");
+    DM_DEVICE_PTR(c, b->upsert_wants, nu * 8, "upsert_wants");
     if (b->upsert_subclients32)
-      DM_DEVICE_COL(c, b->upsert_subclients32, nu * 4, "upsert_subclients32");
+      DM_DEVICE_PTR(c, b->upsert_subclients32, nu * 4, "upsert_subclients32");
     else
-      DM_DEVICE_COL(c, b->upsert_subclients, nu * 8, "upsert_subclients");
-    DM_DEVICE_COL(c, b->upsert_expiry_ns, nu * 8, "upsert_expiry_ns");
+      DM_DEVICE_PTR(c, b->upsert_subclients, nu * 8, "upsert_subclients");
+    DM_DEVICE_PTR(c, b->upsert_expiry_ns, nu * 8, "upsert_expiry_ns");
   }
   return DM_OK;
 }
@@ -509,8 +495,7 @@ static int apply_check(dm_ctx* c, const UpdateStage& S, bool late) {
 
 // The synchronous batch, host (dm_store_apply) or device columns (dm_store_apply_device).
 static int apply_sync(dm_ctx* c, const dm_store_batch* b, bool device) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
+  if (int rc = update_enter(c)) return rc;
   if (int rc = batch_args(c, b)) return rc;
   if (device)
     if (int rc = batch_device_ptrs(c, b)) return rc;
@@ -538,8 +523,7 @@ static int async_retire(dm_ctx* c, UpdateStage& S) {
 
 // The asynchronous batch, host or device columns: one sequence and the same sets for both.
 static int apply_async(dm_ctx* c, const dm_store_batch* b, bool device) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
+  if (int rc = update_enter(c)) return rc;
   if (int rc = batch_args(c, b)) return rc;
   if (device)
     if (int rc = batch_device_ptrs(c, b)) return rc;
@@ -594,207 +578,4 @@ void dm::async_drain(dm_ctx* c) {
 int dm_store_apply_wait(dm_ctx* c) {
   DM_ENTER(c);
   return async_retire_all(c);
-}
-
-// The store re-laid out in HBM (dm_relayout.hip): fresh columns take every row that
-// stays, the kernels flag what the new layout cannot hold, and the fresh columns become
-// the store's only when nothing was flagged -- a rejected call leaves the old columns,
-// index, sums and plan as they were.  What crosses PCIe: the new seg_off, two flag words
-// and, when asked for, the row map.
-int dm_store_relayout(dm_ctx* c, int64_t n_resources, const int64_t* new_seg_off, uint32_t flags, int64_t* row_map) {
-  DM_ENTER(c);
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  (void)c->check_device();
-  if (c->store_lost)
-    return c->fail(DM_E_STATE, "the store is lost (" + c->lost_msg + "): reload it (dm_store_load), a re-layout would carry its rows over");
-  // in-flight batches name rows of the old layout: they finish first, and a rejected one's
-  // error is returned before anything moves (as dm_config_load)
-  if (int ra = async_retire_all(c)) return ra;
-  const int64_t R = c->R, N = c->N, Rn = n_resources;
-  if (!new_seg_off || (flags & ~DM_RELAYOUT_COMPACT)) return c->fail(DM_E_INVAL, "bad re-layout arguments");
-  if (Rn < R) return c->fail(DM_E_INVAL, "a re-layout keeps every resource: n_resources below the store's count");
-  if (Rn > INT32_MAX - 1) return c->fail(DM_E_INVAL, "too many resources for one context (max 2^31-2)");
-  if (new_seg_off[0] != 0) return c->fail(DM_E_INVAL, "new_seg_off must start at 0");
-  for (int64_t r = 0; r < Rn; ++r)
-    if (new_seg_off[r + 1] < new_seg_off[r]) return c->fail(DM_E_INVAL, "new_seg_off must be non-decreasing");
-  if (Rn != R && (!c->pub_ring.empty() || c->hs_leaf))
-    return c->fail(DM_E_STATE, "a publish ring or hierarchy pair is bound to this store (blocks of 1 + R records): "
-                               "the number of resources cannot change");
-  const int64_t Nn = new_seg_off[Rn];
-  const bool compact = flags & DM_RELAYOUT_COMPACT;
-  DM_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  hipStream_t st = c->stream;
-  DBuf<int64_t> n_off, n_exp;
-  DBuf<int32_t> n_blk, n_sub;
-  DBuf<double> n_wants, n_has;
-  DBuf<ResAgg> n_agg;
-  DBuf<uint8_t> n_expl;
-  // (a failure waits for what the stream still holds before the fresh columns go with the return)
-#define RL_HIP(expr, what)                 \
-  do {                                     \
-    const hipError_t _e = (expr);          \
-    if (_e != hipSuccess) {                \
-      (void)hipStreamSynchronize(st);      \
-      return c->hip_fail(_e, what);        \
-    }                                      \
-  } while (0)
-  RL_HIP(upload(n_off, new_seg_off, (size_t)Rn + 1, st), "upload seg_off");
-  RL_HIP(n_blk.ensure((size_t)((Nn >> kRowBlkShift) + 2)), "alloc row index");
-  RL_HIP(n_wants.ensure((size_t)Nn), "alloc wants");
-  RL_HIP(n_has.ensure((size_t)Nn), "alloc has");
-  RL_HIP(n_sub.ensure((size_t)Nn), "alloc subclients");
-  RL_HIP(n_exp.ensure((size_t)Nn), "alloc expiry");
-  RL_HIP(n_agg.ensure((size_t)Rn), "alloc running sums");
-  RL_HIP(n_expl.ensure((size_t)std::max<int64_t>(Rn, 1)), "alloc explicit flags");
-  RL_HIP(hipMemsetAsync(n_expl.p, 1, n_expl.n, st), "explicit flags");  // every row leaves with an expiry of its own
-  RL_HIP(c->rl_flags.ensure(1), "re-layout flags");
-  RL_HIP(c->rl_bad.ensure(1), "re-layout flags");
-  const int64_t nb = (N + kRlBlkRows - 1) / kRlBlkRows;
-  if (compact) {
-    RL_HIP(c->rl_blk_pre.ensure((size_t)nb + 1), "block prefix");
-    RL_HIP(c->rl_seg_local.ensure((size_t)std::max<int64_t>(R, 1)), "resource bases");
-  }
-  if (row_map && N > 0) RL_HIP(c->rl_map.ensure((size_t)N), "row map");
-  RelayoutArgs a{};
-  a.N = N;
-  a.R = R;
-  a.ix = c->row_index();
-  a.wants = c->wants.p;
-  a.has = c->has.p;
-  a.sub = c->sub.p;
-  a.expiry = c->expiry.p;
-  a.agg = c->agg.p;
-  a.Nn = Nn;
-  a.Rn = Rn;
-  a.new_off = n_off.p;
-  a.n_wants = n_wants.p;
-  a.n_has = n_has.p;
-  a.n_sub = n_sub.p;
-  a.n_expiry = n_exp.p;
-  a.blk_pre = compact ? c->rl_blk_pre.p : nullptr;
-  a.seg_local = compact ? c->rl_seg_local.p : nullptr;
-  a.row_map = row_map && N > 0 ? c->rl_map.p : nullptr;
-  a.flags = c->rl_flags.p;
-  a.bad = c->rl_bad.p;
-  RL_HIP(launch_relayout(a, n_blk.p, n_agg.p, compact, st), "re-layout");
-  uint32_t f = 0;
-  unsigned long long bad = 0;
-  RL_HIP(hipMemcpyAsync(&f, c->rl_flags.p, sizeof f, hipMemcpyDeviceToHost, st), "re-layout flags");
-  RL_HIP(hipMemcpyAsync(&bad, c->rl_bad.p, sizeof bad, hipMemcpyDeviceToHost, st), "re-layout flags");
-  RL_HIP(hipStreamSynchronize(st), "re-layout");
-  if (f & kRlReject) {
-    char buf[160];
-    if (f & kRlInternal) {
-      snprintf(buf, sizeof buf, "re-layout: inconsistent ranks at resource %llu", bad);
-      return c->fail(DM_E_INTERNAL, buf);
-    }
-    if (f & kRlDrop)
-      snprintf(buf, sizeof buf, "resource %llu: the new segment would drop a row that is not released", bad);
-    else
-      snprintf(buf, sizeof buf, "resource %llu: more live rows than its new segment holds", bad);
-    return c->fail(DM_E_RANGE, buf);
-  }
-  if (row_map && N > 0) {
-    RL_HIP(hipMemcpyAsync(row_map, c->rl_map.p, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, st), "row map");
-    RL_HIP(hipStreamSynchronize(st), "row map");
-  }
-#undef RL_HIP
-  // the fresh table becomes the store; the old one is freed when the call returns
-  std::swap(c->seg_off, n_off);
-  std::swap(c->blk_seg, n_blk);
-  std::swap(c->wants, n_wants);
-  std::swap(c->has, n_has);
-  std::swap(c->sub, n_sub);
-  std::swap(c->expiry, n_exp);
-  std::swap(c->agg, n_agg);
-  std::swap(c->expl, n_expl);
-  if (Nn != N) {  // the alternate columns and lease outputs follow N at the next tick that needs them
-    c->out_gets.release();
-    c->out_expiry.release();
-  }
-  c->R = Rn;
-  c->N = Nn;
-  c->h_seg_off.assign(new_seg_off, new_seg_off + Rn + 1);
-  c->seg_uniform = uniform_rows(new_seg_off, Rn);
-  // maybe_general / all_sub_one are carried: no live row was added.  One case the rows
-  // themselves decide (kRlGeneral): a resource of the small tiles, which the load's scan
-  // never looked at, now in a bin that hands heterogeneous rows to k_general.
-  if (f & kRlGeneral) c->maybe_general = true;
-  build_plan(c);
-  if (int rc = upload_plan(c)) return rc;  // (with R unchanged: bin 4's shape by the kept kinds, update_bin4_shape)
-  DM_HIP(c, hipStreamSynchronize(st), "re-layout");
-  c->expl_rows = true;
-  c->rows_changed();
-  c->have_result = false;
-  c->hints_set = false;
-  c->cl_valid = false;  // the last clean's list named rows of the old layout
-  if (Rn != R) c->cfg_loaded = false;  // the caller loads a configuration for the new count
-  return DM_OK;
-}
-
-// Clean (store.go:169-181) on the device (dm_clean.hip): a count pass, the 16-B result to
-// the host (which sizes the list from it), then the apply pass.  What crosses PCIe: that
-// result, and 8 B per listed row when dm_read_cleaned asks for them.
-int dm_store_clean(dm_ctx* c, int64_t now_ns, uint32_t flags, dm_clean_result* out) {
-  DM_ENTER(c);
-  DM_STORE_OK(c);
-  if (flags & ~DM_CLEAN_PEEK) return c->fail(DM_E_INVAL, "unknown clean flags");
-  if (!c->store_loaded) return c->fail(DM_E_STATE, "no store loaded");
-  // in-flight batches change which rows are live: they finish first, and a rejected one's
-  // error is returned before anything is cleaned (as dm_config_load)
-  if (int ra = async_retire_all(c)) return ra;
-  const bool peek = flags & DM_CLEAN_PEEK;
-  hipStream_t st = c->stream;
-  const int64_t nb = (c->N + kRlBlkRows - 1) / kRlBlkRows;
-  c->cl_valid = false;
-  c->cl_n = 0;
-  int64_t res[2] = {0, DM_NO_EXPIRY};
-  CleanArgs a{};
-  if (nb > 0) {
-    DM_HIP(c, c->cl_blk_pre.ensure((size_t)nb + 2), "clean block prefix");
-    DM_HIP(c, c->cl_blk_min.ensure((size_t)nb), "clean block minima");
-    a.N = c->N;
-    a.ix = c->row_index();
-    a.has = c->has.p;
-    a.wants = c->wants.p;
-    a.sub = c->sub.p;
-    a.expiry = c->expiry.p;
-    a.agg = c->agg.p;
-    a.expl = c->expl.p;
-    a.now = now_ns;
-    a.blk_pre = c->cl_blk_pre.p;
-    a.blk_min = c->cl_blk_min.p;
-    DM_HIP(c, c->timed(KC_RELEASE, st, [&] { return launch_clean_count(a, st); }), "clean count");
-    DM_HIP(c, hipMemcpyAsync(res, c->cl_blk_pre.p + nb, sizeof res, hipMemcpyDeviceToHost, st), "clean result");
-    if (int rs = c->synced("clean")) return rs;
-  }
-  const int64_t total = res[0];
-  if (total < 0 || total > c->N) return c->fail(DM_E_INTERNAL, "clean: inconsistent count of lapsed rows");
-  if (total > 0) {
-    DM_HIP(c, c->cl_list.ensure((size_t)total), "clean list");
-    a.list = c->cl_list.p;
-    a.list_n = total;
-    if (!peek) c->rows_changed();
-    DM_HIP(c, c->timed(KC_RELEASE, st, [&] { return launch_clean_apply(a, c->dense_upd(), peek, st); }),
-           "clean apply");
-    if (!peek) c->have_result = false;
-    if (int rs = c->synced("clean")) return rs;
-  }
-  c->cl_valid = true;
-  c->cl_n = total;
-  if (out) {
-    out->released = total;
-    out->next_expiry_ns = res[1];
-  }
-  return DM_OK;
-}
-
-int dm_read_cleaned(dm_ctx* c, int64_t off, int64_t n, int64_t* rows) {
-  DM_ENTER(c);
-  if (!c->cl_valid) return c->fail(DM_E_STATE, "no dm_store_clean list (none yet, or the store was loaded or re-laid out since)");
-  if (int rc = check_range(c, off, n, c->cl_n)) return rc;
-  if (n > 0 && !rows) return c->fail(DM_E_INVAL, "null rows");
-  DM_HIP(c, download(rows, (const int64_t*)c->cl_list.p, off, n, c->stream), "read cleaned rows");
-  DM_HIP(c, hipStreamSynchronize(c->stream), "read cleaned rows");
-  return DM_OK;
 }

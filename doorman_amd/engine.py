@@ -31,6 +31,75 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+def _host_col(a, dts):
+    """A host column for _fill_batch: contiguous, of dtype dts[0] or, where it has it already,
+    of dts[1]."""
+    dt = dts[1] if len(dts) > 1 and np.asarray(a).dtype == dts[1] else dts[0]
+    a = np.ascontiguousarray(a, dtype=dt)
+    return a.ctypes.data, len(a), a
+
+
+def _device_col(t, dts):
+    """A device column for _fill_batch (checked by _check_device_col before)."""
+    return t.data_ptr() or None, len(t), t
+
+
+def _check_device_col(name, t, dts, noun, device):
+    """One column of a device snapshot or a device update (the noun), checked without a context
+    or a library call: a CUDA tensor of torch (or any object with data_ptr(), dtype, device and
+    a length) on `device`, of one of the dtypes dts, one contiguous dimension."""
+    import torch
+    want = torch.device("cuda", device)
+    if not hasattr(t, "data_ptr") or not hasattr(t, "device"):
+        raise ValueError(f"{name} must be a tensor on {want} (data_ptr(), dtype, device and a length)")
+    dev = torch.device(t.device)
+    if dev.type != "cuda":
+        raise ValueError(f"{name} is on {dev}: a device {noun}'s columns live on {want}")
+    if dev.index is not None and dev.index != device:
+        raise ValueError(f"{name} is on {dev}, the engine on {want}")
+    if str(t.dtype).replace("torch.", "") not in dts:
+        raise ValueError(f"{name} must be {' or '.join(dts)}, not {t.dtype}")
+    if getattr(t, "ndim", 1) != 1 or (hasattr(t, "is_contiguous") and not t.is_contiguous()):
+        raise ValueError(f"{name} must be one contiguous column")
+
+
+def _fill_batch(col, wants_mask, wants, release_rows, upsert, wants_first_row, now_ns):
+    """The StoreBatch of apply() and apply_device().  col(column, dtypes) gives a column's
+    (pointer, length, object to keep alive while the library reads it): _host_col or
+    _device_col.  Returns the batch and the kept objects."""
+    if upsert is not None and upsert[4] is None and now_ns is None:
+        raise ValueError("arrivals without expiries need now_ns (their expiry is now_ns + lease length)")
+    b, keep = _lib.StoreBatch(), []
+
+    def put(a, *dts):
+        p, n, k = col(a, dts)
+        keep.append(k)
+        return p, n, k
+
+    if wants_mask is not None:
+        b.wants_mask, b.wants_nwords, _ = put(wants_mask, "uint64", "int64")
+        b.wants_first_row = int(wants_first_row)
+        if wants is not None:
+            b.wants, b.wants_n, _ = put(wants, "float64")
+    if release_rows is not None:
+        b.release_rows, b.release_n, _ = put(release_rows, "int64")
+    if upsert is not None:
+        rows, has, wv, sub, exp = upsert
+        b.upsert_rows, b.upsert_n, _ = put(rows, "int64")
+        if has is not None:
+            b.upsert_has = put(has, "float64")[0]
+        b.upsert_wants = put(wv, "float64")[0]
+        p, _, k = put(sub, "int64", "int32")
+        if str(k.dtype).replace("torch.", "") == "int32":
+            b.upsert_subclients32 = p
+        else:
+            b.upsert_subclients = p
+        if exp is not None:
+            b.upsert_expiry_ns = put(exp, "int64")[0]
+        b.upsert_now_ns = int(now_ns or 0)
+    return b, keep
+
+
 class Engine:
     """One GPU context owning a device-resident columnar lease store."""
 
@@ -186,35 +255,7 @@ class Engine:
         asynchronous: dm_store_apply_async -- enqueued, not waited for; the arrays are kept
         alive here until the batch is retired (apply_wait, or two batches later), and a
         rejected batch raises from the call that retires it."""
-        if upsert is not None and upsert[4] is None and now_ns is None:
-            raise ValueError("arrivals without expiries need now_ns (their expiry is now_ns + lease length)")
-        keep = []
-
-        def col(a, dt):
-            a = _c(a, dt)
-            keep.append(a)
-            return a
-
-        b = _lib.StoreBatch()
-        if wants_mask is not None:
-            m, w = col(wants_mask, np.uint64), col(wants if wants is not None else [], np.float64)
-            b.wants_first_row, b.wants_nwords, b.wants_mask = int(wants_first_row), len(m), _ptr(m)
-            b.wants_n, b.wants = len(w), _ptr(w)
-        if release_rows is not None:
-            r = col(release_rows, np.int64)
-            b.release_n, b.release_rows = len(r), _ptr(r)
-        if upsert is not None:
-            rows, has, wv, sub, exp = upsert
-            rows = col(rows, np.int64)
-            b.upsert_n, b.upsert_rows = len(rows), _ptr(rows)
-            b.upsert_has = None if has is None else _ptr(col(has, np.float64))
-            b.upsert_wants = _ptr(col(wv, np.float64))
-            if np.asarray(sub).dtype == np.int32:
-                b.upsert_subclients32 = _ptr(col(sub, np.int32))
-            else:
-                b.upsert_subclients = _ptr(col(sub, np.int64))
-            b.upsert_expiry_ns = None if exp is None else _ptr(col(exp, np.int64))
-            b.upsert_now_ns = int(now_ns or 0)
+        b, keep = _fill_batch(_host_col, wants_mask, wants, release_rows, upsert, wants_first_row, now_ns)
         if not asynchronous:
             self._chk(self._L.dm_store_apply(self._ctx, ctypes.byref(b)))
             return
@@ -271,26 +312,14 @@ class Engine:
     _DEV_AGG = (("agg_count", "int64"), ("agg_sum_has", "float64"), ("agg_sum_wants", "float64"))
 
     def _device_snapshot(self, snap: dict):
-        """The columns of a device snapshot, checked without a context or a library call:
-        each a CUDA tensor of torch (or any object with data_ptr(), dtype, device and a
-        length) on this engine's device, of its dtype, contiguous, the row columns as long as
-        seg_off says.  Returns (n_resources, n_leases, {name: column})."""
-        import torch
-        want = torch.device("cuda", self.device)
+        """The columns of a device snapshot, checked without a context or a library call: each
+        by _check_device_col, the row columns of one length, the sums one per resource.
+        Returns (n_resources, n_leases, {name: column})."""
         have_agg = snap.get("agg_count") is not None
         cols = {}
         for name, dt in self._DEV_COLS + (self._DEV_AGG if have_agg else ()):
-            t = snap[name]
-            dev = torch.device(t.device)
-            if dev.type != "cuda":
-                raise ValueError(f"{name} is on {dev}: a device snapshot's columns live on {want}")
-            if dev.index is not None and dev.index != self.device:
-                raise ValueError(f"{name} is on {dev}, the engine on {want}")
-            if str(t.dtype).replace("torch.", "") != dt:
-                raise ValueError(f"{name} must be {dt}, not {t.dtype}")
-            if getattr(t, "ndim", 1) != 1 or (hasattr(t, "is_contiguous") and not t.is_contiguous()):
-                raise ValueError(f"{name} must be one contiguous column")
-            cols[name] = t
+            _check_device_col(name, snap[name], (dt,), "snapshot", self.device)
+            cols[name] = snap[name]
         if len(cols["seg_off"]) < 1:
             raise ValueError("seg_off must hold n_resources + 1 offsets")
         R, N = len(cols["seg_off"]) - 1, len(cols["wants"])
@@ -385,27 +414,12 @@ class Engine:
 
     # -- store updates from device memory (no column over PCIe) --
     def _device_cols(self, *cols):
-        """Update columns in device memory, checked without a context or a library call, by
-        load_store_device's rules: cols are (name, column, dtype or tuple of dtypes); each
-        column a CUDA tensor of torch (or any object with data_ptr(), dtype, device and a
-        length) on this engine's device, of (one of) its dtype(s), one contiguous dimension,
-        and all of one length.  Returns that length (0 without columns)."""
-        import torch
-        want = torch.device("cuda", self.device)
+        """Update columns in device memory, checked without a context or a library call: cols
+        are (name, column, dtype or tuple of dtypes), each checked by _check_device_col and all
+        of one length.  Returns that length (0 without columns)."""
         n = None
         for name, t, dts in cols:
-            dts = (dts,) if isinstance(dts, str) else dts
-            if not hasattr(t, "data_ptr") or not hasattr(t, "device"):
-                raise ValueError(f"{name} must be a tensor on {want} (data_ptr(), dtype, device and a length)")
-            dev = torch.device(t.device)
-            if dev.type != "cuda":
-                raise ValueError(f"{name} is on {dev}: a device update's columns live on {want}")
-            if dev.index is not None and dev.index != self.device:
-                raise ValueError(f"{name} is on {dev}, the engine on {want}")
-            if str(t.dtype).replace("torch.", "") not in dts:
-                raise ValueError(f"{name} must be {' or '.join(dts)}, not {t.dtype}")
-            if getattr(t, "ndim", 1) != 1 or (hasattr(t, "is_contiguous") and not t.is_contiguous()):
-                raise ValueError(f"{name} must be one contiguous column")
+            _check_device_col(name, t, (dts,) if isinstance(dts, str) else dts, "update", self.device)
             if n is None:
                 n = len(t)
             elif len(t) != n:
@@ -449,41 +463,21 @@ class Engine:
         now_ns).  asynchronous: dm_store_apply_device_async -- the library reads the tensors
         until the batch is retired (apply_wait, or two asynchronous batches later, host or
         device); they are kept alive here until then."""
-        if upsert is not None and upsert[4] is None and now_ns is None:
-            raise ValueError("arrivals without expiries need now_ns (their expiry is now_ns + lease length)")
-        # every column is checked before the first pointer is taken
+        # every column is checked before the first pointer is taken (_fill_batch: the now_ns rule first)
         if wants_mask is None and wants is not None:
             raise ValueError("packed wants without a mask")
-        nw = self._device_cols(("wants_mask", wants_mask, ("int64", "uint64"))) if wants_mask is not None else 0
-        nm = self._device_cols(("wants", wants, "float64")) if wants is not None else 0
-        nr = self._device_cols(("release_rows", release_rows, "int64")) if release_rows is not None else 0
-        nu = 0
+        for name, t, dts in (("wants_mask", wants_mask, ("int64", "uint64")), ("wants", wants, "float64"),
+                             ("release_rows", release_rows, "int64")):
+            if t is not None:
+                self._device_cols((name, t, dts))
         if upsert is not None:
             rows, has, wv, sub, exp = upsert
             cols = [("upsert rows", rows, "int64"), ("upsert wants", wv, "float64"),
                     ("upsert subclients", sub, ("int64", "int32"))]
             cols += [("upsert has", has, "float64")] if has is not None else []
             cols += [("upsert expiry_ns", exp, "int64")] if exp is not None else []
-            nu = self._device_cols(*cols)
-
-        def ptr(t):
-            return None if t is None else t.data_ptr() or None
-
-        b = _lib.StoreBatch()
-        keep = [t for t in (wants_mask, wants, release_rows) + tuple(upsert or ()) if t is not None]
-        if wants_mask is not None:
-            b.wants_first_row, b.wants_nwords, b.wants_mask = int(wants_first_row), nw, ptr(wants_mask)
-            b.wants_n, b.wants = nm, ptr(wants)
-        if release_rows is not None:
-            b.release_n, b.release_rows = nr, ptr(release_rows)
-        if upsert is not None:
-            b.upsert_n, b.upsert_rows, b.upsert_has, b.upsert_wants = nu, ptr(rows), ptr(has), ptr(wv)
-            if str(sub.dtype).replace("torch.", "") == "int32":
-                b.upsert_subclients32 = ptr(sub)
-            else:
-                b.upsert_subclients = ptr(sub)
-            b.upsert_expiry_ns = ptr(exp)
-            b.upsert_now_ns = int(now_ns or 0)
+            self._device_cols(*cols)
+        b, keep = _fill_batch(_device_col, wants_mask, wants, release_rows, upsert, wants_first_row, now_ns)
         self._torch_ready()
         if not asynchronous:
             self._chk(self._L.dm_store_apply_device(self._ctx, ctypes.byref(b)))

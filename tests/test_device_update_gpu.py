@@ -444,6 +444,93 @@ def test_host_pointers_and_short_tensors_are_refused(engines):
     _same(A, B, "refused pointers")
 
 
+BAD_MASK = "bad masked update (first_row must be a multiple of 64)"
+NO_MASK = "packed values without a mask"
+PAST_END = "mask words past the store's end"
+
+
+def _scalar_faults(W1):
+    """(call, arguments, code, message) of the argument checks that the host runs before it
+    looks at a pointer.  A letter stands for a valid column (host memory for the host call,
+    device memory for its twin; upper case: host memory for both); W1: the mask words of the
+    whole store.  Single calls take their arguments in the C order; a batch is the fields that
+    differ from an empty one."""
+    INV, RNG, OK = _lib.DM_E_INVAL, _lib.DM_E_RANGE, _lib.DM_OK
+    up = ("r", "h", "w", "s", "e")
+    yield "upsert", (-1,) + up, INV, "bad upsert"
+    for k in range(5):
+        yield "upsert", (64,) + up[:k] + (None,) + up[k + 1:], INV, "bad upsert"
+    yield "upsert", (0, "R", "H", "W", "S", "E"), OK, None
+    yield "update_wants", (-1, "r", "w"), INV, "bad update"
+    yield "update_wants", (64, None, "w"), INV, "bad update"
+    yield "update_wants", (64, "r", None), INV, "bad update"
+    yield "update_wants", (0, "R", "W"), OK, None
+    yield "release", (-1, "r"), INV, "bad release"
+    yield "release", (64, None), INV, "bad release"
+    yield "release", (0, "R"), OK, None
+    # (first_row, nwords, mask, n, wants)
+    yield "update_wants_mask", (0, W1, "m", -1, "w"), INV, BAD_MASK
+    yield "update_wants_mask", (0, W1, None, 64, "w"), INV, BAD_MASK
+    yield "update_wants_mask", (0, W1, "m", 64, None), INV, BAD_MASK
+    yield "update_wants_mask", (-64, 1, "m", 64, "w"), INV, BAD_MASK
+    yield "update_wants_mask", (32, 1, "m", 64, "w"), INV, BAD_MASK
+    yield "update_wants_mask", (0, -1, "m", 0, "w"), INV, BAD_MASK
+    yield "update_wants_mask", (0, 0, "m", 64, "w"), INV, NO_MASK
+    yield "update_wants_mask", (0, W1 + 1, "m", 64, "w"), RNG, PAST_END
+    yield "update_wants_mask", (0, 0, "M", 0, "W"), OK, None
+    for k in ("wants_nwords", "wants_n", "release_n", "upsert_n"):
+        yield "apply", {k: -1}, INV, "negative batch sizes"
+    yield "apply", dict(release_n=64), INV, "bad release"
+    arrivals = dict(upsert_n=64, upsert_rows="r", upsert_has="h", upsert_wants="w", upsert_subclients="s",
+                    upsert_expiry_ns="e")
+    for k in ("upsert_rows", "upsert_wants", "upsert_subclients"):
+        yield "apply", {**arrivals, k: None}, INV, "bad upsert"
+    refresh = dict(wants_first_row=0, wants_nwords=W1, wants_mask="m", wants_n=64, wants="w")
+    yield "apply", {**refresh, "wants_mask": None}, INV, BAD_MASK
+    yield "apply", {**refresh, "wants": None}, INV, BAD_MASK
+    yield "apply", {**refresh, "wants_first_row": -64, "wants_nwords": 1}, INV, BAD_MASK
+    yield "apply", {**refresh, "wants_first_row": 32, "wants_nwords": 1}, INV, BAD_MASK
+    yield "apply", {**refresh, "wants_nwords": 0}, INV, NO_MASK
+    yield "apply", {**refresh, "wants_nwords": W1 + 1}, RNG, PAST_END
+    yield "apply", dict(wants_mask="M", wants="W", release_rows="R", upsert_rows="R", upsert_wants="W"), OK, None
+
+
+def test_scalar_argument_checks_are_the_twins(engines):
+    """The argument checks that come before the pointer checks, through ctypes on both twins
+    with the same scalars: the same code and dm_last_error text on both, equal to the table
+    above; with nothing to do the device twin returns DM_OK before it looks at a pointer (host
+    pointers pass); neither store changes."""
+    A, B, snap = _load(engines)
+    N = len(snap["wants"])
+    W1 = (N + 63) // 64
+    before = _state(A), _state(B)
+    host = {"r": np.arange(64, dtype=np.int64), "h": np.full(64, 2.0), "w": np.full(64, 3.0),
+            "s": np.ones(64, np.int64), "e": np.full(64, NOW + 600 * W.NS, np.int64), "m": np.zeros(W1 + 1, np.uint64)}
+    dev = {k: _t(v) for k, v in host.items()}
+    hp = {k: v.ctypes.data for k, v in host.items()}
+    ptrs = {False: {**hp, **{k.upper(): p for k, p in hp.items()}},
+            True: {**{k: t.data_ptr() for k, t in dev.items()}, **{k.upper(): p for k, p in hp.items()}}}
+    wrong = []
+    for call, args, code, msg in _scalar_faults(W1):
+        got = []
+        for e, device in ((A, False), (B, True)):
+            fn = getattr(e._L, f"dm_store_{call}_device" if device else f"dm_store_{call}")
+            if call == "apply":
+                b = _lib.StoreBatch()
+                for k, v in args.items():
+                    setattr(b, k, ptrs[device].get(v, v) if isinstance(v, str) else v)
+                rc = fn(e._ctx, ctypes.byref(b))
+            else:
+                rc = fn(e._ctx, *[ptrs[device][a] if isinstance(a, str) else a for a in args])
+            got.append((rc, e._L.dm_last_error(e._ctx).decode() if rc != _lib.DM_OK else None))
+        print(call, args, got)
+        if got != [(code, msg)] * 2:
+            wrong.append((call, args, got, (code, msg)))
+    assert not wrong, wrong
+    _assert_state(_state(A), before[0], "refused scalars: A untouched")
+    _assert_state(_state(B), before[1], "refused scalars: B untouched")
+
+
 # ---------------------------------------------------------------------------------------
 # asynchronous device batches
 # ---------------------------------------------------------------------------------------
