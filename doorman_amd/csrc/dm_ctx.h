@@ -19,12 +19,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/doorman_hip.h"
 #include "dm_carry_rule.h"
+#include "dm_decide_assign.h"
 #include "dm_device.h"
 #include "dm_large_form.h"
 #include "dm_launch.h"
@@ -972,6 +974,16 @@ int check_device_ptr(dm_ctx* c, const void* p, size_t bytes, const char* what);
 // dm_store_update.cpp (its callers: the loads, dm_config_load, dm_store_layout.cpp)
 void async_drain(dm_ctx* c);
 int async_retire_all(dm_ctx* c);
+// dm_store_update.cpp (its caller: dm_decide_assign): the upsert of device columns as the end
+// of a call that has more on the context stream.  enqueue: what the call's one wait also
+// covers, put on the stream behind the upsert's kernels; landed: called once that wait is
+// over, before the upsert's flags word is judged (a rejected upsert still calls it).
+struct UpsertTail {
+  std::function<int()> enqueue;
+  std::function<void()> landed;
+};
+int upsert_round(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants, const int64_t* sub,
+                 const int64_t* exp, const UpsertTail& tail);
 // dm_hier_host.cpp
 struct RcclApi;
 const RcclApi* rccl_api();

@@ -1,6 +1,7 @@
-// dm_decide.cpp — dm_decide: the host side of a round of requests (dm_round.hip,
-// dm_decide_fast.hip).  The round's plan is dm_decide_plan.h's, its device buffers
-// dm_decide_round.h's (dm_ctx::round); this unit carries the plan out.
+// dm_decide.cpp — dm_decide and dm_decide_assign: the host side of a round of requests
+// (dm_round.hip, dm_decide_fast.hip) and of the Assign that may end it (dm_decide_assign.hip).
+// The round's plan is dm_decide_plan.h's, the Assign's selection dm_decide_assign.h's, their
+// device buffers dm_decide_round.h's (dm_ctx::round); this unit carries the plan out.
 #include "dm_ctx.h"
 
 // The device work of a planned and staged round, in stream order: per fast item Clean, the
@@ -35,8 +36,15 @@ static hipError_t launch_round(const DecideRound& r, const RoundPlan& plan, cons
 // (dm_round.hip).  Requests are ordered by resource on the host (stable: a
 // resource's requests keep the caller's order); one workgroup per resource with
 // requests, over a scratch copy of its rows.
-int dm_decide(dm_ctx* c, int64_t now_ns, int64_t n, const int64_t* rows, const double* has, const double* wants,
-              const int64_t* subclients, double* gets, int64_t* expiry_ns) {
+// One body with two endings.  dm_decide (assign false): the decisions cross PCIe, the host
+// waits, the store is as it was.  dm_decide_assign: behind the round, on the context stream,
+// the selected requests' values are gathered into the round's compact columns
+// (dm_decide_assign.h, dm_decide_assign.hip) and assigned by the upsert's row step
+// (dm_store_update.cpp upsert_round: dm_store_upsert_device's body), whose end carries the
+// call's one wait; the safe capacities (when asked for) and the decisions' copies are
+// enqueued before that wait and taken after it.
+static int decide(dm_ctx* c, bool assign, int64_t now_ns, int64_t n, const int64_t* rows, const double* has,
+                  const double* wants, const int64_t* subclients, double* gets, int64_t* expiry_ns, double* safe) {
   DM_ENTER(c);
   int rc = ready(c);
   if (rc) return rc;
@@ -86,12 +94,52 @@ int dm_decide(dm_ctx* c, int64_t now_ns, int64_t n, const int64_t* rows, const d
   const FastArgs fa = r.fast_args();
   // one profiling class: dm_kernel_times "decide"
   DM_HIP(c, c->timed(KC_DECIDE, st, [&] { return launch_round(r, plan, p, q, fa, st); }), "decide requests");
-  DM_HIP(c, download(shas.data(), (const double*)r.gets.p, 0, n, st), "read decisions");
-  DM_HIP(c, download(ssub.data(), (const int64_t*)r.exp.p, 0, n, st), "read decisions");
-  if (int rs = c->synced("decide requests")) return rs;
-  for (int64_t i = 0; i < n; ++i) {
-    gets[plan.order[(size_t)i]] = shas[(size_t)i];
-    expiry_ns[plan.order[(size_t)i]] = ssub[(size_t)i];
+  // the decisions' copies into the staging vectors (their first use is over: the uploads above
+  // are enqueued behind copies of their own), and their way into the caller's order
+  auto read_decisions = [&]() -> hipError_t {
+    const hipError_t e = download(shas.data(), (const double*)r.gets.p, 0, n, st);
+    return e == hipSuccess ? download(ssub.data(), (const int64_t*)r.exp.p, 0, n, st) : e;
+  };
+  auto give_decisions = [&] {
+    for (int64_t i = 0; i < n; ++i) {
+      gets[plan.order[(size_t)i]] = shas[(size_t)i];
+      expiry_ns[plan.order[(size_t)i]] = ssub[(size_t)i];
+    }
+  };
+  if (!assign) {
+    DM_HIP(c, read_decisions(), "read decisions");
+    if (int rs = c->synced("decide requests")) return rs;
+    give_decisions();
+    return DM_OK;
   }
-  return DM_OK;
+  const AssignSel a = assign_selection(plan, rows);
+  DM_HIP(c, r.ensure_assign(a), "assign buffers");
+  DM_HIP(c, upload(r.a_sel, a.sel.data(), a.sel.size(), st), "stage selection");
+  DM_HIP(c, launch_assign_gather(q, r.assign_args(a), st), "gather assigns");
+  std::vector<double> ssafe(safe ? (size_t)n : 0);
+  UpsertTail tail;
+  tail.enqueue = [&]() -> int {
+    if (safe) {
+      DM_HIP(c, launch_safe_capacity(n, r.rows.p, c->row_index(), c->cfg.p, c->cold.p, c->agg.p, r.safe.p, st),
+             "safe capacity");
+      DM_HIP(c, download(ssafe.data(), (const double*)r.safe.p, 0, n, st), "read safe capacity");
+    }
+    DM_HIP(c, read_decisions(), "read decisions");
+    return DM_OK;
+  };
+  tail.landed = [&] {
+    give_decisions();
+    for (int64_t i = 0; safe && i < n; ++i) safe[plan.order[(size_t)i]] = ssafe[(size_t)i];
+  };
+  return upsert_round(c, a.m(), r.a_rows.p, r.a_has.p, r.a_wants.p, r.a_sub.p, r.a_exp.p, tail);
+}
+
+int dm_decide(dm_ctx* c, int64_t now_ns, int64_t n, const int64_t* rows, const double* has, const double* wants,
+              const int64_t* subclients, double* gets, int64_t* expiry_ns) {
+  return decide(c, false, now_ns, n, rows, has, wants, subclients, gets, expiry_ns, nullptr);
+}
+
+int dm_decide_assign(dm_ctx* c, int64_t now_ns, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                     const int64_t* subclients, double* gets, int64_t* expiry_ns, double* safe_capacity) {
+  return decide(c, true, now_ns, n, rows, has, wants, subclients, gets, expiry_ns, safe_capacity);
 }

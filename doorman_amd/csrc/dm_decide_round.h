@@ -67,6 +67,26 @@ struct DecideRound {
     return a;
   }
 
+  // dm_decide_assign's buffers, which a round that ends with its Assign adds (dm_decide_assign.h
+  // AssignBuf names them and assign_count sizes them; dm_decide itself never touches them): the
+  // selection, the compact columns the upsert's row step reads in place, the requests' safe
+  // capacities in grouped order.
+  DBuf<int64_t> a_sel, a_rows, a_sub, a_exp;
+  DBuf<double> a_has, a_wants, safe;
+  hipError_t ensure_assign(const AssignSel& a) {
+    using B = AssignBuf;
+    hipError_t e = hipSuccess;
+    auto need = [&](auto& buf, B id) {
+      if (e == hipSuccess) e = buf.ensure((size_t)assign_count(a, id));
+    };
+    need(a_sel, B::sel), need(a_rows, B::rows), need(a_has, B::has), need(a_wants, B::wants);
+    need(a_sub, B::sub), need(a_exp, B::exp), need(safe, B::safe);
+    return e;
+  }
+  AssignArgs assign_args(const AssignSel& a) const {
+    return AssignArgs{a.m(), a_sel.p, a_rows.p, a_has.p, a_wants.p, a_sub.p, a_exp.p};
+  }
+
   // The round's two kinds of sort over the plan's areas: each fast item's wants (keys into
   // keys_s), and every event block as a segment of one pair sort (bounds: the begins, then the
   // ends).  temp null: the storage they need, into *bytes.

@@ -320,6 +320,14 @@ struct ResAgg {  // 32 B, read and written by every tick
   int64_t follow_exp;
 };
 
+// SetSafeCapacity's value (resource.go:81-96) from a resource's records: the configured safe
+// capacity (ResCold, NaN: none is set), else the capacity (ResCfg) shared among the store's
+// count (ResAgg).  The one statement of it, for the host (dm_read_resources) and the device
+// (dm_decide_assign's k_safe_capacity): an IEEE division either side, so the bits agree.
+__host__ __device__ inline double safe_capacity_of(double capacity, double configured, int64_t count) {
+  return configured != configured ? capacity / (double)count : configured;
+}
+
 // dm_store_relayout (dm_relayout.hip): the old table and its index, the new layout and
 // the fresh columns the moved rows are written into.  Rows are handled in scan blocks
 // of 2^kRowBlkShift old rows (one 256-thread workgroup each, every wave 16 x 64
@@ -501,6 +509,19 @@ struct ReqArgs {
   double* sc_wants;
   int32_t* sc_sub;  // subclients of a live row, -1 for a row absent after Clean
   const struct FastRes* fast;  // the fast path's verdict per slot (k_decide skips items it decided)
+};
+
+// dm_decide_assign's gather (dm_decide_assign.hip): the selection (dm_decide_assign.h
+// AssignSel: the grouped positions of the requests whose values the store takes) and the
+// compact columns the upsert's row step reads, one entry per selected request.
+struct AssignArgs {
+  int64_t m;
+  const int64_t* sel;
+  int64_t* rows;
+  double* has;  // the selected requests' gets: what the row has after the round
+  double* wants;
+  int64_t* sub;
+  int64_t* exp;
 };
 
 // dm_decide's fast path (dm_decide_fast.hip) for a resource with many requests in a

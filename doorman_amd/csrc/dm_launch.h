@@ -158,6 +158,11 @@ hipError_t fd_sort_keys(void* temp, size_t* bytes, const double* in, double* out
 hipError_t fd_sort_pairs(void* temp, size_t* bytes, const double* kin, double* kout, const int32_t* vin,
                          int32_t* vout, int64_t n, int nseg, const int64_t* begin, const int64_t* end,
                          hipStream_t st);
+// dm_decide_assign.hip: the selected requests' values into the compact columns; the safe
+// capacity of each of n requests' resources (rows: the requests' rows, in the store's range)
+hipError_t launch_assign_gather(const ReqArgs& q, const AssignArgs& a, hipStream_t st);
+hipError_t launch_safe_capacity(int64_t n, const int64_t* rows, const RowIndex& ix, const ResCfg* cfg,
+                                const ResCold* cold, const ResAgg* agg, double* safe, hipStream_t st);
 // dm_relayout.hip (launch_rl_scan: the in-place scan dm_clean.hip shares)
 hipError_t launch_rl_scan(int64_t* v, int64_t n, hipStream_t st);
 hipError_t launch_relayout(const RelayoutArgs& a, int32_t* nblk, ResAgg* n_agg, bool compact, hipStream_t st);

@@ -300,7 +300,7 @@ int dm_read_resources(dm_ctx* c, int64_t r0, int64_t n, int64_t* count, double* 
     if (sum_has) sum_has[i] = v[i].sum_has;
     if (sum_wants) sum_wants[i] = v[i].sum_wants;
     // SetSafeCapacity (resource.go:81-96) after the tick's Clean: configured, or capacity / Count
-    if (safe) safe[i] = std::isnan(cc[i].safe_capacity) ? cf[i].capacity / (double)v[i].count : cc[i].safe_capacity;
+    if (safe) safe[i] = safe_capacity_of(cf[i].capacity, cc[i].safe_capacity, v[i].count);
   }
   return DM_OK;
 }

@@ -208,10 +208,15 @@ static int mask_kernels(dm_ctx* c, UpdateStage& S, const UpdSrc& src, int64_t fi
 }
 
 // A single call's end: its flags word back and the wait (the call is synchronous on return, so
-// the caller may free its buffers and set 0 is idle again), then what the word says.
-static int single_end(dm_ctx* c, UpdateStage& S, UpdPart part, WriteEnd& we, int64_t n) {
+// the caller may free its buffers and set 0 is idle again), then what the word says.  tail (a
+// round's Assign, upsert_round below): what else the call's one wait covers is enqueued before
+// the flags' copy, and its results are taken as soon as the wait is over, whatever the word says.
+static int single_end(dm_ctx* c, UpdateStage& S, UpdPart part, WriteEnd& we, int64_t n, const UpsertTail* tail = nullptr) {
+  if (tail)
+    if (int rc = tail->enqueue()) return rc;
   DM_HIP(c, S.fetch_flags(1, c->stream), "update flags");
   if (int rs = c->synced("update")) return rs;
+  if (tail) tail->landed();
   const uint32_t f = S.h_flags.p[0];
   const UpdOutcome o = update_outcome(part, f, false);
   if (o.code != DM_OK) return c->fail(o.code, o.msg);
@@ -260,10 +265,13 @@ static int update_enter(dm_ctx* c) {
 }
 
 // A single call that names n > 0 rows, from its pointer checks on (a column the call does not
-// take: nullptr, which every step passes over; stage: the staging's name in a failure).
+// take: nullptr, which every step passes over; stage: the staging's name in a failure).  tail:
+// the columns are the context's own device buffers (no pointer check), and the call ends as
+// single_end says.
 static int single_rows(dm_ctx* c, bool device, UpdPart part, RowWrite kind, const char* stage, int64_t n,
-                       const int64_t* rows, const double* has, const double* wants, const int64_t* sub, const int64_t* exp) {
-  if (device) {
+                       const int64_t* rows, const double* has, const double* wants, const int64_t* sub, const int64_t* exp,
+                       const UpsertTail* tail = nullptr) {
+  if (device && !tail) {
     DM_DEVICE_PTR(c, rows, n * 8, "rows");
     DM_DEVICE_PTR(c, has, n * 8, "has");
     DM_DEVICE_PTR(c, wants, n * 8, "wants");
@@ -280,7 +288,16 @@ static int single_rows(dm_ctx* c, bool device, UpdPart part, RowWrite kind, cons
   DM_HIP(c, c->row_bits.ensure(c->N, c->stream), "row bitmap");
   DM_HIP(c, S.reset_flags(1, c->stream), "update flags");
   if (int rc = row_part(c, S, src, we, part, n, cols, 5, nullptr)) return rc;
-  return single_end(c, S, part, we, n);
+  return single_end(c, S, part, we, n, tail);
+}
+
+// A round's Assign (dm_decide_assign, dm_decide.cpp): dm_store_upsert_device's body from
+// single_rows on, for a caller that has entered (DM_ENTER, ready) and whose n > 0 rows, unique
+// by its selection, lie in the round's own compact columns, written by kernels already on the
+// context stream.
+int dm::upsert_round(dm_ctx* c, int64_t n, const int64_t* rows, const double* has, const double* wants,
+                     const int64_t* sub, const int64_t* exp, const UpsertTail& tail) {
+  return single_rows(c, true, UpdPart::upsert, RowWrite::upsert, "stage upsert", n, rows, has, wants, sub, exp, &tail);
 }
 
 static int upsert(dm_ctx* c, bool device, int64_t n, const int64_t* rows, const double* has, const double* wants,

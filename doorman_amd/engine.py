@@ -519,6 +519,20 @@ class Engine:
                                     _ptr(exp)))
         return gets, exp
 
+    def decide_assign(self, now_ns: int, rows, has, wants, subclients, safe: bool = False):
+        """dm_decide_assign: decide() ended with the Assign (store.go:153-167): each distinct
+        requested row takes its last request's (gets, wants, subclients, expiry_ns), as
+        decide() followed by that upsert() leaves the store.  Returns (gets, expiry_ns), and
+        with safe also each request's safe capacity after the round's Assigns
+        (resource.go:81-96): (gets, expiry_ns, safe_capacity)."""
+        rows = _c(rows, np.int64)
+        a = [_c(has, np.float64), _c(wants, np.float64), _c(subclients, np.int64)]
+        gets, exp = np.empty(len(rows)), np.empty(len(rows), np.int64)
+        sc = np.empty(len(rows)) if safe else None
+        self._chk(self._L.dm_decide_assign(self._ctx, int(now_ns), len(rows), _ptr(rows), *[_ptr(x) for x in a],
+                                           _ptr(gets), _ptr(exp), _ptr(sc)))
+        return (gets, exp, sc) if safe else (gets, exp)
+
     def leases(self, off: int = 0, n: int | None = None):
         n = self.n_leases - off if n is None else n
         gets, exp = np.empty(n), np.empty(n, np.int64)

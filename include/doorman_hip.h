@@ -377,9 +377,31 @@ int dm_apportion(dm_ctx* ctx, int64_t now_ns, uint32_t flags);
  * reference's.  A row may be requested more than once (a client's later request
  * sees its earlier one).  gets[k] and expiry_ns[k] (now + lease length) are the
  * leases; the device store is not changed -- Assign the final ones with
- * dm_store_upsert.  Subclients in [0, 2^31 - 1).  Synchronous. */
+ * dm_store_upsert, or decide and assign in one call with dm_decide_assign.
+ * Subclients in [0, 2^31 - 1).  Synchronous. */
 int dm_decide(dm_ctx* ctx, int64_t now_ns, int64_t n, const int64_t* rows, const double* has, const double* wants,
               const int64_t* subclients, double* gets, int64_t* expiry_ns);
+
+/* dm_decide, ended as the reference ends Resource.Decide: with store.Assign (store.go:
+ * 153-167).  Arguments, checks, request order, gets and expiry_ns are dm_decide's.  On
+ * return the store is in the state dm_decide followed by one dm_store_upsert leaves it
+ * in, the upsert holding one entry per distinct requested row with the values of that
+ * row's last request in the caller's order (has = its gets, its wants, its subclients,
+ * its expiry_ns): rows, counts, dense state, row epoch and flags alike; a resource's
+ * running sums are moved by the upsert's kernels, so they are those bits where one row
+ * of it was assigned and agree as two runs of the upsert agree where several were.
+ * The round's Clean is not written back: lapsed rows nobody asked for stay for the next
+ * tick or dm_store_clean.  safe_capacity (or NULL): per request SetSafeCapacity's value
+ * (resource.go:81-96) for its resource after the round's Assigns -- the configured safe
+ * capacity, else capacity / the store's count (dm_read_resources' rule and bits).
+ * The decisions stay in device memory between the round and the Assign, and the host
+ * waits for the context stream once.  A round dm_decide rejects returns its code and
+ * changes nothing; should the Assign be rejected as dm_store_upsert would reject those
+ * values, its code and message are returned, the store is untouched and gets and
+ * expiry_ns are filled.  n == 0: DM_OK.  Synchronous. */
+int dm_decide_assign(dm_ctx* ctx, int64_t now_ns, int64_t n, const int64_t* rows, const double* has,
+                     const double* wants, const int64_t* subclients, double* gets, int64_t* expiry_ns,
+                     double* safe_capacity);
 
 /* lease outputs of the last dm_apportion: gets (Lease.Has), expiry in unix ns
  * (DM_RELEASED for released rows); any pointer may be NULL */
@@ -662,7 +684,8 @@ int dm_set_profiling(dm_ctx* ctx, int on);
    (above that the bin runs as with the bit clear).  Subclient counts other than one do not end
    the mode.  Every other writer starts a row epoch as ever, under either bit:
    dm_store_apply_async (its NaN flag arrives two batches late), dm_decide, dm_store_clean,
-   dm_store_relayout, dm_store_load, dm_config_load and dm_hier_root_tick.
+   dm_store_relayout, dm_store_load, dm_config_load and dm_hier_root_tick (dm_decide_assign
+   starts one as dm_decide does, and its Assign then ends as a dm_store_upsert does).
    DM_KEEP_FREE_SLOTS (4) keeps no call; it selects the tick's forms alone.  With the bit clear
    a dense workgroup-bin resource that holds released rows (free slots) runs through the
    general path every tick and never holds a key.  With it set such a resource, while it has no
